@@ -160,7 +160,13 @@ def parse():
                     help='write {sample id: sha256 of its uint8 output} of this rank\'s last timed step to <path>.rank<r>.json and the '
                          'uint8 images to <path>.rank<r>.npy (tests/test_gpu_bench_ranks.py compares the ranks of an N = 2 run with the '
                          'single-process run id by id)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the headline loop returned in its last timed step to DIR/<name>.npy (float32, at most 64 MB in all; a '
+                         'fixed, seeded sample of a larger output) so that two builds can be compared output for output')
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    return a
 
 
 def free_port():
@@ -179,6 +185,32 @@ def max_over_ranks(dt, use_dist, backend, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt
+
+
+def dump_outputs(dirname, arrays, suffix, budget):
+    """--dump-outputs: every tensor of ``arrays`` as float32 ``dirname/<name><suffix>.npy``.  When they exceed ``budget`` bytes in all, each
+    keeps a fixed, seeded sample of its leading-dimension rows (its share of the budget), their row numbers beside it in
+    ``<name><suffix>_index.npy`` (float64).  -> a record for the JSON line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {name: t.detach().cpu().numpy().astype(np.float32) for name, t in arrays.items()}
+    total = sum(v.nbytes for v in host.values())
+    budget -= 1024 * 2 * len(host)                                          # the .npy headers
+    rec = {}
+    for name, v in host.items():
+        entry = {'shape': list(v.shape), 'source_dtype': str(arrays[name].dtype).replace('torch.', '')}
+        if total > budget:
+            rows = v.reshape(v.shape[0] if v.ndim else 1, -1)
+            if rows.shape[1] * 4 + 8 > budget * v.nbytes // total:         # one row alone is over the share: sample single elements
+                rows = rows.reshape(-1, 1)
+            k = budget * v.nbytes // total // (rows.shape[1] * 4 + 8)
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=k, replace=False))
+            np.save(os.path.join(dirname, f'{name}{suffix}_index.npy'), idx.astype(np.float64))
+            v = rows[idx].reshape((k,) + (v.shape[1:] if rows.shape[1] > 1 else ()))
+            entry['sampled_rows'] = int(k)
+        np.save(os.path.join(dirname, f'{name}{suffix}.npy'), v)
+        rec[name + suffix] = entry
+    return {'dir': dirname, 'arrays': rec}
 
 
 def class_tables(tsum, psteps, f16_peak=None):
@@ -550,6 +582,8 @@ def worker(local_rank, a, spawned_world=None, port=None):
         graph_info['used'] = use_graph
         if not use_graph:
             gpipe = None
+    # the noise of the timed steps: the same draws whatever the warm-up, graph capture and trial consumed (--dump-outputs compares runs)
+    torch.manual_seed(world + rank)
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -586,6 +620,7 @@ def worker(local_rank, a, spawned_world=None, port=None):
         # the images themselves: a sample's output depends on its batch-mates at the 1e-6 level through the batch-global style RMS of
         # stylegan.py:147, so digests of one id agree across batch compositions only up to a few truncation flips
         np.save(f'{a.digest_out}.rank{rank}.npy', o8)
+    dumped = dump_outputs(a.dump_outputs, {'composite': out}, '' if world == 1 else f'_rank{rank}', 64_000_000 // world) if a.dump_outputs else None
     # one batch alone on one stream (latency of a step; not the headline)
     lat_ms = None
     if rank == 0:
@@ -752,6 +787,8 @@ def worker(local_rank, a, spawned_world=None, port=None):
             'fp16_blocks_eval': fp16_eval,
             'train_step': train,
         }
+        if dumped is not None:
+            line['dump_outputs'] = dumped
         if not a.no_cpu_baseline and world == 1:
             try:
                 line['cpu_baseline'] = cpu_baseline(res, batch, a.cpu_images or batch, a.cpu_forwards, a.noise_mode, seed=0)
