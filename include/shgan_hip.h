@@ -302,6 +302,19 @@ int shg_mask_raster_f32(const int* records, const int* offsets, const int* flips
  * feats [B,D] float32 (float64 when is_f64), weights [B] or NULL, DP >= D+1 a multiple of 32. */
 int shg_fid_accumulate_f64(const void* feats, int is_f64, const float* weights, double* S, int B, int D, int DP, void* stream);
 
+/* ---- evaluation image metrics (lib/evaluator/eva_psnr.py, for_dataset=None, rgb_range=1; eva_ssim._ssim, size_average=False).
+ * pred, gt [B,C,H,W] contiguous; each operand is uint8 when its lut [256] (value of every code: float64 for pred, float32 for gt) is
+ * given, float32 otherwise; the element value is then v*scale + bias (the evaluator's fake/255 and (real+1)/2).  As in the reference's
+ * evaluator batch, PSNR takes pred in float64 and gt in float32; SSIM takes both in float32.  psnr [B] = -10 log10(mean (pred-gt)^2), +inf
+ * when the mean is 0; ssim [B] = mean of the SSIM map (window_size-tap Gaussian, sigma 1.5, zero padding window_size/2, C1 = 0.01^2,
+ * C2 = 0.03^2).  window_size odd in [1, 31]; psnr_only skips SSIM (ssim may be NULL).  scratch: shg_image_metrics_scratch_bytes
+ * bytes (per-tile fp64 partial sums, reduced per image in a fixed order: results are bitwise reproducible and independent of the
+ * batch an image sits in).  shg_image_metrics_scratch_bytes returns 0 for invalid arguments. */
+size_t shg_image_metrics_scratch_bytes(int B, int H, int W, int window_size);
+int shg_image_metrics(const void* pred, const double* pred_lut, float pred_scale, float pred_bias, const void* gt, const float* gt_lut,
+                      float gt_scale, float gt_bias, int B, int C, int H, int W, int window_size, int psnr_only, void* scratch,
+                      size_t scratch_bytes, double* psnr, double* ssim, void* stream);
+
 /* ---- next row N3 (training-side critic, forward only): minibatch_std_layer (stylegan.py:686-704).
  * x [N,C,H,W] -> y [N,C+F,H,W]; N % G == 0, C % F == 0; stat [N/G * F] is caller-owned scratch. */
 int shg_minibatch_std_f32(const float* x, float* y, float* stat, int N, int C, int H, int W, int G, int F, void* stream);

@@ -360,11 +360,17 @@ class EvalLoop:
     generator; a sixth (a statistics stream, the first form of this loop) made the staging stream share a hardware queue with a
     generator stream and the hole-count read waited for a whole batch (MEASUREMENTS.md, round 6).  ``latent_fn(ids, B) -> z``
     replaces ``torch.randn`` (tests: per-item latents so that a result can be compared id by id); ``on_batch(ids, images_u8, event)``
-    hands every finished batch to a consumer (host metrics) without ending the loop."""
+    hands every finished batch to a consumer (host metrics) without ending the loop.
+
+    ``metrics=('psnr', 'ssim')`` (or a subset) adds the image-quality evaluators of the reference (eva_psnr.py / eva_ssim.py on the
+    evaluator batch of shgan_default.py:279-291): per batch, on the batch's own stream, one HIP launch pair (image_metrics.py) writes the
+    per-image values of the composite against ``real`` into a per-rank float64 buffer at the batch's position; ``gather`` all-gathers
+    those buffers once, re-interleaves them to dataset order and sets ``image_metrics`` -- independent of ``keep_images``.
+    ``metrics_fn(pred, gt, window_size, psnr_out, ssim_out)`` replaces the kernel (CPU tests)."""
 
     def __init__(self, G, device, resolution, n_items, rank=0, world=1, noise_mode='random', seed=0, depth=None, feature_fn=None,
                  fid_dim=2048, latent_fn=None, device_masks=True, hole_range=(0, 1), keep_images=True, on_batch=None, step_fn=None,
-                 fid_accumulate_fn=None, feeder_stream=False, timing=False):
+                 fid_accumulate_fn=None, feeder_stream=False, timing=False, metrics=None, ssim_window=11, metrics_fn=None):
         from .datasets import DeviceFeeder
         self.timing, self.batch_done_events = timing, []      # timing: one timing event per finished batch (bench: steady-state rate)
         self.G, self.device, self.res = G, torch.device(device), int(resolution)
@@ -379,6 +385,12 @@ class EvalLoop:
         self.fid = None                 # their sum, after gather()
         self.images = (torch.empty((len(self.ids), 3, self.res, self.res), dtype=torch.uint8, device=self.device) if keep_images else None)
         self.seen = 0
+        self.metrics = None             # image_metrics.MetricsAccumulator of this rank's shard
+        self.image_metrics = None       # after gather(): {'psnr': mean, 'psnr_per_image': [n_items], ...} in dataset order
+        if metrics:
+            from .image_metrics import MetricsAccumulator
+            self.metrics = MetricsAccumulator(len(self.ids), self.device, metrics=tuple(metrics), window_size=ssim_window,
+                                              metrics_fn=metrics_fn)
 
     def _fid_part(self, key):
         from .fid_stats import FidStats
@@ -404,14 +416,16 @@ class EvalLoop:
             gen = self.step_fn if self.step_fn is not None else (lambda x_, z_, o_: run_generator(G, x_, z_, noise_mode=self.noise_mode, out=o_))
             dst = buf[k0:k0 + b] if buf is not None else None
 
-            def step(x4_, z_, dst=dst, k0=k0):
+            def step(x4_, z_, real_=None, dst=dst, k0=k0):
                 out = gen(x4_, z_, dst)
                 if self.feature_fn is not None:
                     cur = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == 'cuda' else None
                     part = self._fid_parts.get(cur) or self._fid_part(None)
                     part.add_shard(self.feature_fn(out), k0, self.rank, self.world, self.n_items)
+                if real_ is not None:
+                    self.metrics.add(out, real_, k0)
                 return out
-            out = pipe.run(step, x4, z)
+            out = pipe.run(step, x4, z, real) if self.metrics is not None else pipe.run(step, x4, z)
             if self.timing and self.device.type == 'cuda':
                 tev = torch.cuda.Event(enable_timing=True)
                 tev.record(pipe.last_stream or torch.cuda.current_stream(self.device))
@@ -428,7 +442,9 @@ class EvalLoop:
 
     def gather(self):
         """-> (uint8 images [n_items,3,R,R] in dataset order on the device, FidStats summed over the ranks | None).  One
-        ``all_gather_into_tensor`` + ``zipzap_device``; one ``all_reduce`` of the moments.  Every rank must have run its whole shard."""
+        ``all_gather_into_tensor`` + ``zipzap_device``; one ``all_reduce`` of the moments.  Every rank must have run its whole shard.
+        With ``metrics`` also one ``all_gather_into_tensor`` of the per-image values -> ``self.image_metrics`` (the reference's
+        ``compute()``: dataset order, ``[0:sample_n]``, mean)."""
         import torch.distributed as dist
         if self.seen != len(self.ids):
             raise ValueError(f'EvalLoop.gather: {self.seen} of {len(self.ids)} items of this rank\'s shard were processed')
@@ -447,7 +463,24 @@ class EvalLoop:
             images = zipzap_device(full, self.n_items)
         if self.local_fid() is not None:
             self.fid.all_reduce()
+        if self.metrics is not None:
+            self.image_metrics = self._gather_metrics(use)
         return images, self.fid
+
+    def _gather_metrics(self, use):
+        import torch.distributed as dist
+        from .image_metrics import finish_metrics
+        names = list(self.metrics.values)
+        local = torch.stack([self.metrics.values[m] for m in names], dim=1)         # [n_local, M] float64
+        if use:
+            via_host = dist.get_backend() == 'gloo' and local.is_cuda
+            src = local.cpu() if via_host else local
+            full = torch.empty((self.world,) + tuple(src.shape), dtype=src.dtype, device=src.device)
+            dist.all_gather_into_tensor(full.view((-1,) + tuple(src.shape[1:])), src)
+            full = full.to(self.device)
+        else:
+            full = local[None]
+        return finish_metrics({m: full[:, :, j] for j, m in enumerate(names)}, self.n_items)
 
     def local_fid(self):
         """This rank's moments (the per-stream partial accumulators added up; no collective)."""
