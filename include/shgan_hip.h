@@ -315,6 +315,17 @@ int shg_image_metrics(const void* pred, const double* pred_lut, float pred_scale
                       float gt_scale, float gt_bias, int B, int C, int H, int W, int window_size, int psnr_only, void* scratch,
                       size_t scratch_bytes, double* psnr, double* ssim, void* stream);
 
+/* ---- Places2 evaluation input: FixResolutionLoader's PIL Image.resize([R, R], BICUBIC) (ds_places2.py:90-103) of a ragged batch, 8 bits
+ * per channel, bit-exact to Pillow, + the formatter's horizontal flip of the resized image (FreeFormMaskFormatter, :214-229).
+ * src: src_bytes bytes holding B HWC RGB uint8 images back to back; dst: uint8 [B,3,R,R].  table: device int32 [table_elems] = B
+ * descriptors of 12 ints {h, w, byte offset in src, flip, h-bounds, h-coefs, KH, v-bounds, v-coefs, KV, band rows, column chunk} followed
+ * by the per-axis fixed-point tables they point at (bounds [R][2] = first tap, taps; coefficients [R][K], 22 fractional bits; layout and
+ * builder: sh-gan_amd/resize.py).  Grid chunks x bands x B: every image's R / column chunk and R / band rows must not exceed them;
+ * lds_bytes (<= 49152) >= 3 x (source rows of a band) x (column chunk rounded up to 4) for every band.  A
+ * descriptor or tap range outside src / table leaves that image's bytes unwritten (never an out-of-bounds access). */
+int shg_resize_bicubic_u8(const void* src, long src_bytes, const int* table, long table_elems, void* dst, int B, int R, int chunks, int bands,
+                          int lds_bytes, void* stream);
+
 /* ---- next row N3 (training-side critic, forward only): minibatch_std_layer (stylegan.py:686-704).
  * x [N,C,H,W] -> y [N,C+F,H,W]; N % G == 0, C % F == 0; stat [N/G * F] is caller-owned scratch. */
 int shg_minibatch_std_f32(const float* x, float* y, float* stat, int N, int C, int H, int W, int G, int F, void* stream);

@@ -10,7 +10,7 @@ import torch  # noqa: F401  (must be imported first: the .so binds to torch's al
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libshgan_hip.so')
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 c_fp = ctypes.c_void_p      # device pointers travel as void*
 c_i = ctypes.c_int
@@ -109,6 +109,7 @@ _SIGS = {
     'shg_fid_accumulate_f64': [c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_image_metrics_scratch_bytes': [c_i] * 4,
     'shg_image_metrics': [c_fp, c_fp, c_f, c_f, c_fp, c_fp, c_f, c_f] + [c_i] * 6 + [c_fp, ctypes.c_size_t, c_fp, c_fp, c_fp],
+    'shg_resize_bicubic_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
     'shg_minibatch_std_f32': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
     'shg_conv2d_f16': [c_fp, c_fp, c_fp, c_fp] + [c_i] * 12 + [c_fp],
     'shg_conv2d_f16_needs_clear': [c_i] * 5,

@@ -127,7 +127,7 @@ class DeviceFeeder:
 
         feeder = DeviceFeeder(device, resolution=512, device_masks=True)
         for x4, real, mask, ids in feeder(loader):      # loader yields (x [B,3,R,R] in [-1,1], mask [B,1,R,R] or None, ids)
-            img = G(x=x4, z=..., c=...)
+            img = G(x=x4, z=..., c=...)                 # or RaggedU8Batch (Places2: images of their own sizes, resized on the device)
 
     The H2D copies of batch k+1 run on a copy stream while batch k's kernels execute (pinned staging buffers, one event per batch);
     ``device_masks`` draws the freeform masks on the device instead of taking the formatter's (same distribution and, for the same
@@ -161,9 +161,24 @@ class DeviceFeeder:
             d = t.to(self.device, non_blocking=True)
         return d
 
+    def _resize_on_device(self, batch):
+        """RaggedU8Batch -> uint8 [B,3,R,R] on the device: the packed bytes are uploaded like any other input and resized
+        (resize.resize_bicubic_u8, Pillow's bicubic bit for bit, then the flips) on the staging stream, behind their upload."""
+        from .resize import resize_bicubic_u8
+        if self.device.type != 'cuda':
+            raise ValueError('DeviceFeeder: ragged uint8 batches are resized on a HIP device (there is no host path)')
+        data = self._to_device(batch.data)
+        st = self.copy_stream if self.copy_stream is not None else torch.cuda.current_stream(self.device)
+        return resize_bicubic_u8(data, batch.shapes, self.resolution, flip=batch.flip, stream=st)
+
     def _stage(self, batch):
-        x, mask, ids = (batch[0], batch[1], batch[2]) if len(batch) == 3 else (batch[0], None, batch[1])
-        xd = self._to_device(x.contiguous())
+        if isinstance(batch, RaggedU8Batch):
+            mask, ids = batch.masks, batch.ids
+            xd = self._resize_on_device(batch)
+            x = xd
+        else:
+            x, mask, ids = (batch[0], batch[1], batch[2]) if len(batch) == 3 else (batch[0], None, batch[1])
+            xd = self._to_device(x.contiguous())
         md = None
         if not self.device_masks:
             if mask is None:
@@ -215,3 +230,123 @@ class DeviceFeeder:
             staged = nxt
         if staged is not None:
             yield self._finish(staged)
+
+
+# ------------------------------------------------------------------------------------------------
+# Places2 (lib/data_factory/ds_places2.py): images of their own sizes, resized to R x R on the device
+# ------------------------------------------------------------------------------------------------
+
+_PLACES2_TAGS = {
+    # tagging_normal: under root_dir
+    'train': ('data_large', '00train', ()), 'challenge': ('data_challenge', '01challenge', ()), 'val': ('val_large', '50val', ()),
+    'test': ('test_large', '90test', ()),
+    # tagging_small / tagging_small_512: under root_dir/places2_small
+    'strain': ('train_large', '01strain', ('places2_small',)), 'sval': ('val_large', '51sval', ('places2_small',)),
+    'stest': ('test_large', '91stest', ('places2_small',)),
+    'strain512': ('train_512', '02strain', ('places2_small',)), 'sval512': ('val_512', '52val', ('places2_small',)),
+    'stest512': ('test_512', '92test', ('places2_small',)),
+    # tagging_fromtf
+    'test_fromtf': ('test_fromtf/image', '93test_fromtf', ()),
+}
+
+
+def places2_list(root_dir, mode):
+    """load_info of ``places2`` (ds_places2.py:19-77) in ds_base's order (sorted by unique_id, common/ds_base.py:50-51): every .jpg / .png
+    under the mode's directory (``+``-joined modes concatenate), unique_id = '-'.join([maintag] + subdir.split('/')[4:] + [stem]) -- the
+    reference's id, taken literally from the path string as given (its [4:] assumes a root four components deep)."""
+    info = []
+    for m in mode.split('+'):
+        if m not in _PLACES2_TAGS:
+            raise ValueError(m)
+        imdir, maintag, mid = _PLACES2_TAGS[m]
+        imdir = os.path.join(root_dir, *mid, imdir)
+        for subdir, _, files in os.walk(imdir):
+            for fi in files:
+                impath = os.path.join(subdir, fi)
+                if not (impath.endswith('.jpg') or impath.endswith('.png')):
+                    continue
+                uid = '-'.join([maintag] + subdir.split('/')[4:] + [os.path.splitext(fi)[0]])
+                info.append({'unique_id': uid, 'filename': fi, 'image_path': impath})
+    info = sorted(info, key=lambda x: x['unique_id'])
+    for idx, e in enumerate(info):
+        e['idx'] = idx
+    return info
+
+
+class Places2(torch.utils.data.Dataset):
+    """``places2`` + ``FixResolutionLoader`` + ``FreeFormMaskFormatter`` (ds_places2.py:90-103,214-229) with the resize moved to the
+    device: an item is {'image': uint8 [H,W,3] at the file's own size (``Image.open(...).convert('RGB')``, no EXIF rotation, as the
+    reference), 'flip': the formatter's flip decision (one ``npr.rand()`` draw when ``random_flip``), 'unique_id'} and, with
+    ``host_masks``, 'mask' = ``RandomMask(resolution, hole_range)[0]`` drawn after the flip, as the formatter does.  ``collate_ragged``
+    batches items into a ``RaggedU8Batch``; ``DeviceFeeder`` resizes it (Pillow's bicubic bit for bit) and flips on the device.
+    Without ``host_masks`` the masks come from the device (``DeviceFeeder(device_masks=True)``, the same numpy draws)."""
+
+    def __init__(self, root_dir, mode, resolution=512, random_flip=False, hole_range=(0, 1), host_masks=False, try_sample=None, repeat=1):
+        self.load_info = places2_list(root_dir, mode)
+        if try_sample is not None:
+            self.load_info = self.load_info[:try_sample]
+        self.resolution, self.random_flip, self.hole_range = int(resolution), bool(random_flip), list(hole_range)
+        self.host_masks, self.repeat = bool(host_masks), repeat
+
+    def __len__(self):
+        return len(self.load_info) * self.repeat
+
+    def __getitem__(self, idx):
+        from PIL import Image
+        e = self.load_info[idx % len(self.load_info)]
+        with Image.open(e['image_path']) as im:
+            u8 = np.asarray(im.convert('RGB'))
+        item = {'image': u8, 'flip': bool(self.random_flip and npr.rand() < 0.5), 'unique_id': e['unique_id']}
+        if self.host_masks:
+            item['mask'] = _data.RandomMask(self.resolution, self.hole_range)[0]
+        return item
+
+
+def places2_val256_inpainting(root_dir, **kw):
+    """configs/dataset/places2.yaml ``places2_val256_inpainting``."""
+    return Places2(root_dir, 'val', resolution=256, random_flip=False, hole_range=(0.0, 1.0), **kw)
+
+
+def places2_val512_inpainting(root_dir, **kw):
+    """configs/dataset/places2.yaml ``places2_val512_inpainting``."""
+    return Places2(root_dir, 'val', resolution=512, random_flip=False, hole_range=(0.0, 1.0), **kw)
+
+
+def places2_challenge256_inpainting(root_dir, **kw):
+    """configs/dataset/places2.yaml ``places2_challenge256_inpainting``."""
+    return Places2(root_dir, 'challenge', resolution=256, random_flip=True, hole_range=(0.0, 1.0), **kw)
+
+
+def places2_challenge512_inpainting(root_dir, **kw):
+    """configs/dataset/places2.yaml ``places2_challenge512_inpainting``."""
+    return Places2(root_dir, 'challenge', resolution=512, random_flip=True, hole_range=(0.0, 1.0), **kw)
+
+
+class RaggedU8Batch:
+    """A batch of decoded images of their own sizes: ``data`` uint8 [sum h*w*3] (HWC RGB images back to back, pinned when built in a
+    process that owns the device), ``shapes`` int32 [B,3] = (h, w, byte offset), ``flip`` bool [B], ``ids``, ``masks`` float32 [B,R,R] or
+    None.  ``DeviceFeeder`` / ``EvalLoop.run`` take it in place of an image tensor; ``pin_memory`` lets a DataLoader pin it."""
+
+    def __init__(self, data, shapes, flip, ids, masks=None):
+        self.data, self.shapes, self.flip, self.ids, self.masks = data, shapes, flip, list(ids), masks
+
+    def __len__(self):
+        return int(self.shapes.shape[0])
+
+    def pin_memory(self):
+        if not self.data.is_pinned():
+            self.data = self.data.pin_memory()
+        return self
+
+
+def collate_ragged(items):
+    """Places2 items -> RaggedU8Batch (``torch.utils.data.DataLoader(collate_fn=collate_ragged)``)."""
+    from .resize import pack_images
+    data, shapes = pack_images([it['image'] for it in items])
+    flip = torch.tensor([bool(it['flip']) for it in items], dtype=torch.bool)
+    masks = None
+    if all('mask' in it for it in items) and items:
+        masks = torch.from_numpy(np.stack([np.asarray(it['mask'], np.float32) for it in items]))
+    if torch.utils.data.get_worker_info() is None and torch.cuda.is_available():
+        data = data.pin_memory()
+    return RaggedU8Batch(data, shapes, flip, [it['unique_id'] for it in items], masks)

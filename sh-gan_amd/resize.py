@@ -1,0 +1,186 @@
+"""Places2 evaluation input on the device: Pillow-exact bicubic resize of decoded uint8 images (``FixResolutionLoader``,
+lib/data_factory/ds_places2.py:90-103: ``Image.resize([R, R], BICUBIC)`` of an RGB image, 8 bits per channel).
+
+Pillow's 8-bit resample (``ImagingResample``) is integer arithmetic on coefficient tables computed in double precision:
+  * per axis (in -> out): scale = in/out, fs = max(scale, 1), support = 2 fs; output index i has center (i + .5) scale, taps
+    [xmin, xmax) with xmin = max(0, (int)(center - support + .5)), xmax = min(in, (int)(center + support + .5)), weights
+    bicubic((x - center + .5) / fs) (a = -0.5) normalised by their sequential sum, then fixed point with 22 fractional bits;
+  * horizontal pass first (only when w != R), vertical second (only when h != R), each ``(1 << 21 + sum u8 * k) >> 22`` clipped to
+    0..255 -- the intermediate is uint8.
+The tables are built here (double precision, the taps accumulated in Pillow's order: vectorised over output indices, looped over
+taps), cached per (in, out) pair, and uploaded with the batch; the kernel (csrc/resize.hip) only adds integers, so the device result
+is bit-exact by construction.  An axis that keeps its size gets the one-tap identity table (k = 1 << 22), which is Pillow's skipped
+pass in the same arithmetic.  ``resize_reference`` is the same two passes in numpy (CPU tests)."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+
+PRECISION_BITS = 22
+LDS_BYTES = 49152                    # csrc/resize.hip RS_LDS_BYTES: the horizontally resampled band of one workgroup
+DESC_INTS = 12                       # csrc/resize.hip: per-image descriptor
+_COEF_CACHE = {}
+
+
+def _bicubic(x):
+    a = -0.5
+    x = np.abs(x)
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1,
+                    np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
+
+
+def bicubic_coeffs(in_size, out_size):
+    """-> (bounds int32 [out, 2] = (xmin, n), k int32 [out, K]) of Pillow's 8-bit bicubic resample along one axis; cached."""
+    key = (int(in_size), int(out_size))
+    hit = _COEF_CACHE.get(key)
+    if hit is not None:
+        return hit
+    n_in, n_out = key
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f'bicubic_coeffs: sizes must be >= 1 (got {n_in} -> {n_out})')
+    if n_in == n_out:                                       # Pillow skips the pass: the identity in the same arithmetic
+        bounds = np.stack([np.arange(n_out), np.ones(n_out, np.int64)], axis=1).astype(np.int32)
+        k = np.full((n_out, 1), 1 << PRECISION_BITS, np.int32)
+    else:
+        scale = n_in / n_out
+        fs = max(scale, 1.0)
+        support = 2.0 * fs
+        ss = 1.0 / fs
+        ksize = int(np.ceil(support)) * 2 + 1
+        center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+        xmin = np.maximum(np.trunc(center - support + 0.5), 0).astype(np.int64)
+        xmax = np.minimum(np.trunc(center + support + 0.5), n_in).astype(np.int64)
+        n = xmax - xmin
+        pre = np.zeros((n_out, ksize), np.float64)
+        ww = np.zeros(n_out, np.float64)
+        for j in range(ksize):                              # sequential sum over taps, as Pillow's loop
+            w = np.where(j < n, _bicubic(((j + xmin) - center + 0.5) * ss), 0.0)
+            pre[:, j] = w
+            ww = ww + w
+        pre = np.where(ww[:, None] != 0.0, pre / np.where(ww == 0.0, 1.0, ww)[:, None], pre)
+        fx = pre * float(1 << PRECISION_BITS)
+        k = np.where(pre < 0, np.trunc(-0.5 + fx), np.trunc(0.5 + fx)).astype(np.int32)
+        bounds = np.stack([xmin, n], axis=1).astype(np.int32)
+    bounds.setflags(write=False)
+    k.setflags(write=False)
+    _COEF_CACHE[key] = (bounds, k)
+    return bounds, k
+
+
+def _pass(src, bounds, k, axis):
+    """One resample pass of Pillow's 8-bit arithmetic along ``axis`` of a uint8 array (int64 accumulation; the int32 bound is a test)."""
+    src = np.moveaxis(src, axis, 0).astype(np.int64)
+    acc = np.full((k.shape[0],) + src.shape[1:], 1 << (PRECISION_BITS - 1), np.int64)
+    xmin, n = bounds[:, 0].astype(np.int64), bounds[:, 1].astype(np.int64)
+    tail = (slice(None),) + (None,) * (src.ndim - 1)
+    for j in range(k.shape[1]):
+        idx = np.minimum(xmin + j, src.shape[0] - 1)
+        kj = np.where(j < n, k[:, j], 0).astype(np.int64)
+        acc += src[idx] * kj[tail]
+    out = np.clip(acc >> PRECISION_BITS, 0, 255).astype(np.uint8)
+    return np.moveaxis(out, 0, axis)
+
+
+def resize_reference(img, R, flip=False):
+    """Host reference: uint8 HWC RGB -> uint8 [3, R, R] (horizontal pass, uint8 intermediate, vertical pass; then the flip)."""
+    img = np.asarray(img, np.uint8)
+    h, w = img.shape[:2]
+    mid = img if w == R else _pass(img, *bicubic_coeffs(w, R), axis=1)
+    out = mid if h == R else _pass(mid, *bicubic_coeffs(h, R), axis=0)
+    if flip:
+        out = out[:, ::-1]
+    return np.ascontiguousarray(out.transpose(2, 0, 1))
+
+
+def _tiling(h, R):
+    """(band rows TB, column chunk CW, LDS bytes) of one image: the tallest band (fewest source rows resampled twice by neighbouring
+    bands) whose source rows, resampled to a chunk of at most 128 columns, fit the workgroup's LDS (3 planes x rows x chunk, uint8)."""
+    bounds, _ = bicubic_coeffs(h, R)
+    lo, hi = bounds[:, 0].astype(np.int64), (bounds[:, 0] + bounds[:, 1]).astype(np.int64)
+    for tb in (16, 8, 4, 2, 1):
+        tb = min(tb, R)
+        starts = np.arange(0, R, tb)
+        span = int((hi[np.minimum(starts + tb, R) - 1] - lo[starts]).max())
+        for cw in (min(R, 128), 64, 32, 16):
+            lds = 3 * span * ((cw + 3) // 4 * 4)
+            if cw <= R and lds <= LDS_BYTES:
+                return tb, cw, lds
+    raise ValueError(f'resize: a {h}-row image is too tall to resample to {R} rows in one workgroup band')
+
+
+def build_table(shapes, R, flip=None):
+    """Host side of one launch: shapes int [B, 3] = (h, w, byte offset of the HWC image) -> (int32 table, chunks, bands, LDS bytes).
+    table = B descriptors of DESC_INTS ints (h, w, offset, flip, horizontal bounds / coefficients / width, vertical bounds /
+    coefficients / width, band rows, column chunk), then each distinct (in, R) pair's bounds and coefficients once."""
+    shapes = np.asarray(shapes, np.int64).reshape(-1, 3)
+    B = shapes.shape[0]
+    flip = np.zeros(B, np.int64) if flip is None else np.asarray(flip).astype(np.int64).reshape(B)
+    desc = np.zeros((B, DESC_INTS), np.int64)
+    parts, placed, pos = [], {}, B * DESC_INTS
+
+    def place(n_in):
+        nonlocal pos
+        if n_in not in placed:
+            bounds, k = bicubic_coeffs(n_in, R)
+            placed[n_in] = (pos, pos + bounds.size, k.shape[1])
+            parts.extend([bounds.reshape(-1), k.reshape(-1)])
+            pos += bounds.size + k.size
+        return placed[n_in]
+
+    chunks = bands = lds_bytes = 1
+    for i, (h, w, off) in enumerate(shapes):
+        if h < 1 or w < 1 or off < 0:
+            raise ValueError(f'resize: image {i} has shape {h}x{w} at offset {off}')
+        tb, cw, lds = _tiling(int(h), R)
+        desc[i] = (h, w, off, flip[i] != 0) + place(int(w)) + place(int(h)) + (tb, cw)
+        chunks, bands, lds_bytes = max(chunks, -(-R // cw)), max(bands, -(-R // tb)), max(lds_bytes, lds)
+    if pos >= 2 ** 31:
+        raise ValueError('resize: coefficient table too large')
+    table = np.concatenate([desc.reshape(-1).astype(np.int32)] + [p.astype(np.int32) for p in parts])
+    return table, chunks, bands, max(lds_bytes, 12)
+
+
+def resize_bicubic_u8(packed, shapes, R, flip=None, stream=None):
+    """packed: uint8 HIP tensor holding B HWC RGB images back to back; shapes: host int [B, 3] = (h, w, byte offset) (numpy or a CPU
+    tensor); flip: host [B] flags (horizontal flip of the resized image) or None -> uint8 [B, 3, R, R] on packed's device, computed on
+    ``stream`` (default: the current stream).  The coefficient table travels with the launch (pinned, asynchronous)."""
+    if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.uint8):
+        raise _lib.ShgError('resize_bicubic_u8: packed must be a uint8 HIP tensor: libshgan_hip has no CPU path')
+    packed = packed.contiguous().view(-1)
+    shapes = shapes.numpy() if isinstance(shapes, torch.Tensor) else shapes
+    flip = flip.numpy() if isinstance(flip, torch.Tensor) else flip
+    R = int(R)
+    table, chunks, bands, lds_bytes = build_table(shapes, R, flip)
+    B = np.asarray(shapes).reshape(-1, 3).shape[0]
+    dev = packed.device
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        tab = torch.from_numpy(table)
+        tab = (tab.pin_memory() if torch.cuda.is_available() else tab).to(dev, non_blocking=True)
+        out = torch.empty((B, 3, R, R), dtype=torch.uint8, device=dev)
+        check(_lib.get_lib().shg_resize_bicubic_u8(ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(tab.data_ptr()),
+                                                   tab.numel(), ctypes.c_void_p(out.data_ptr()), B, R, chunks, bands, lds_bytes,
+                                                   ctypes.c_void_p(st.cuda_stream)), 'resize_bicubic_u8')
+    return out
+
+
+def pack_images(images):
+    """list of uint8 HWC RGB arrays -> (packed uint8 tensor [sum h w 3], shapes int32 [B, 3] = (h, w, offset))."""
+    shapes = np.zeros((len(images), 3), np.int64)
+    off = 0
+    for i, im in enumerate(images):
+        h, w = im.shape[:2]
+        if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
+            raise ValueError('pack_images: images must be uint8 HWC RGB')
+        shapes[i] = (h, w, off)
+        off += h * w * 3
+    if off >= 2 ** 31:
+        raise ValueError('pack_images: a batch holds at most 2 GiB of pixels')
+    packed = torch.empty(off, dtype=torch.uint8)
+    buf = packed.numpy()
+    for im, (h, w, o) in zip(images, shapes):
+        buf[o:o + h * w * 3] = np.ascontiguousarray(im).reshape(-1)
+    return packed, torch.from_numpy(shapes.astype(np.int32))
