@@ -293,9 +293,13 @@ int shg_assemble_input_u8(const uint8_t* real, const float* mask, const float* l
  * reference's order and emits 8-word int32 records per mask (RECT / DISC / QUAD + 4 EDGE / POINT, see csrc/mask_raster.hip);
  * the device draws them exactly as Pillow's ImageDraw.line(width) / ellipse would.  records [total][8], offsets [B+1],
  * flips [B][2], disc_table [max_half+1][2*max_half+1][2]; mask [B,1,s,s] (1 keep / 0 hole), holes [B] += hole pixel counts
- * (zero it first).  s: multiple of 32, <= 512. */
+ * (zero it first).  s: multiple of 32 in [32, 1024]. */
 int shg_mask_raster_f32(const int* records, const int* offsets, const int* flips, const int* disc_table, int max_half, float* mask,
                         int* holes, int B, int s, void* stream);
+/* The same with content boxes (OpenImages' FreeFormMaskFormatter, ds_openimages.py:148-166): boxes [B][2] = (h', w') int32 (device);
+ * keep (1.0) is written at every x >= w' or y >= h'.  holes counts the mask BEFORE this fill (RandomMask's rejection loop). */
+int shg_mask_raster_box_f32(const int* records, const int* offsets, const int* flips, const int* disc_table, int max_half, const int* boxes,
+                            float* mask, int* holes, int B, int s, void* stream);
 
 /* ---- next row N1: FID statistics (lib/evaluator/eva_fid.py:251-263).  S [DP,DP] float64 += sum_b w_b [x_b,1][x_b,1]^T on the
  * fp64 matrix cores: S[:D,:D] = sum x x^T, S[:D,D] = sum x, S[D,D] = count (tiles on / above the diagonal only).
@@ -324,6 +328,12 @@ int shg_image_metrics(const void* pred, const double* pred_lut, float pred_scale
  * lds_bytes (<= 49152) >= 3 x (source rows of a band) x (column chunk rounded up to 4) for every band.  A
  * descriptor or tap range outside src / table leaves that image's bytes unwritten (never an out-of-bounds access). */
 int shg_resize_bicubic_u8(const void* src, long src_bytes, const int* table, long table_elems, void* dst, int B, int R, int chunks, int bands,
+                          int lds_bytes, void* stream);
+/* OpenImages evaluation input: FixResolutionLoader of ds_openimages.py:63-81 -- each image resized (same 8-bit bicubic) to its own box
+ * (h', w') <= R that keeps its aspect ratio (its own size when it fits), pasted at the top-left of a zero R x R canvas; flip mirrors the
+ * whole canvas (FreeFormMaskFormatter, :148-166).  Same arguments, but descriptors of 14 ints {the 12 above, h', w'} with per-axis
+ * tables of w' / h' entries (builder: resize.build_fit_table).  Every byte of dst [B,3,R,R], padding included, is written by the launch. */
+int shg_resize_fit_pad_u8(const void* src, long src_bytes, const int* table, long table_elems, void* dst, int B, int R, int chunks, int bands,
                           int lds_bytes, void* stream);
 
 /* ---- next row N3 (training-side critic, forward only): minibatch_std_layer (stylegan.py:686-704).

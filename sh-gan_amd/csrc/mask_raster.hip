@@ -10,13 +10,15 @@
 //   SEG   (5, x0, y0, x1, y1, width, hypot lo, hypot hi)   the same segment with the quad built HERE (the host only supplies
 //                                                   hypot(dx, dy) as a double: libm's value, not the device's)
 // mask = keep layer AND NOT (brush layer, flipped up-down / left-right per the two flip flags), 1 = keep, 0 = hole.
-// One thread per image row: the row lives in registers as a bit vector (<= 512 columns), records are read with
-// wave-uniform addresses.  Integer / float32 arithmetic only, every float product and sum rounded separately (no FMA):
-// results are bit-exact with the reference's masks (tests/golden/integer_paths.npz).
+// One thread per image row: the row lives in registers as a bit vector of W words (W = 16 for s <= 512, W = 32 for s <= 1024;
+// every index into a row array is a compile-time constant, so the rows stay in VGPRs), records are read with wave-uniform
+// addresses.  With content boxes (h', w') per mask (OpenImages' FreeFormMaskFormatter, ds_openimages.py:148-166), the store pass
+// writes keep at x >= w' or y >= h'; the hole count is taken before that fill (RandomMask's rejection loop sees the whole mask).
+// Integer / float32 arithmetic only, every float product and sum rounded separately (no FMA): results are bit-exact with the
+// reference's masks (tests/golden/integer_paths.npz, tests/golden/openimages_fit.npz at 1024).
 #include "shg_common.h"
 #include <math.h>
 
-#define MR_WORDS 16          // 512 columns
 #define MR_REC 8
 
 struct MaskParams {
@@ -27,16 +29,18 @@ struct MaskParams {
     int max_half;
     float* mask;             // [B,1,s,s]
     int* holes;              // [B] number of zero pixels
+    const int* boxes;        // [B][2] content box (h', w') or null
     int B, s;
 };
 
-__device__ __forceinline__ void mr_span(unsigned (&row)[MR_WORDS], int x0, int x1, int s) {
+template <int W>
+__device__ __forceinline__ void mr_span(unsigned (&row)[W], int x0, int x1, int s) {
     // Pillow's hline8 clipping: [x0, x1] inclusive, clipped to the canvas
     if (x0 < 0) x0 = 0;
     if (x1 >= s) x1 = s - 1;
     if (x0 > x1) return;
 #pragma unroll
-    for (int w = 0; w < MR_WORDS; ++w) {
+    for (int w = 0; w < W; ++w) {
         const int lo = max(x0, 32 * w), hi = min(x1, 32 * w + 31);
         if (lo <= hi) {
             const int nb = hi - lo + 1;
@@ -88,7 +92,8 @@ __device__ __forceinline__ void mr_wide_line(MrEdge (&e)[4], int x0, int y0, int
 }
 
 // Pillow's polygon_generic restricted to one scan line y of a 4-edge polygon; [ymin, YMAX] is the clamped scan range.
-__device__ __forceinline__ void mr_quad_row(unsigned (&row)[MR_WORDS], const MrEdge (&e)[4], int y, int YMAX, int s) {
+template <int W>
+__device__ __forceinline__ void mr_quad_row(unsigned (&row)[W], const MrEdge (&e)[4], int y, int YMAX, int s) {
 #pragma clang fp contract(off)
     // edge table = the non-horizontal edges in order; tix[t] = edge index of table slot t
     int tix[4], nt = 0;
@@ -164,6 +169,7 @@ __device__ __forceinline__ void mr_quad_row(unsigned (&row)[MR_WORDS], const MrE
     (void)get;
 }
 
+template <int W, bool BOX>
 __global__ __launch_bounds__(256) void mask_raster_kernel(const MaskParams p) {
     const int b = blockIdx.x;
     const int y = blockIdx.y * 256 + threadIdx.x;                // output row
@@ -171,9 +177,14 @@ __global__ __launch_bounds__(256) void mask_raster_kernel(const MaskParams p) {
     const bool live = y < s;
     const int f0 = p.flips[2 * b], f1 = p.flips[2 * b + 1];
     const int yb = f0 ? s - 1 - y : y;                           // brush-layer row that lands on output row y
-    unsigned keep[MR_WORDS], brush[MR_WORDS];
+    int rem = s;                                                 // columns of row y inside the content box (keep is written outside)
+    if (BOX) {
+        rem = y < p.boxes[2 * b] ? p.boxes[2 * b + 1] : 0;
+        asm volatile("" : "+v"(rem));                            // one VGPR through the record loop, not the box pointer's SGPRs
+    }
+    unsigned keep[W], brush[W];
 #pragma unroll
-    for (int w = 0; w < MR_WORDS; ++w) { keep[w] = 0u; brush[w] = 0u; }      // keep[] collects the PUNCHED columns
+    for (int w = 0; w < W; ++w) { keep[w] = 0u; brush[w] = 0u; }      // keep[] collects the PUNCHED columns
     const int r0 = p.off[b], r1 = p.off[b + 1];
     const int dstride = 2 * p.max_half + 1;
     for (int r = r0; r < r1;) {
@@ -228,17 +239,21 @@ __global__ __launch_bounds__(256) void mask_raster_kernel(const MaskParams p) {
     int holes = 0;
     float* out = p.mask + ((long)b * s + y) * s;
 #pragma unroll
-    for (int w = 0; w < MR_WORDS; ++w) {
+    for (int w = 0; w < W; ++w) {
         if (w >= nw) break;
         unsigned bw = brush[w];
         if (f1) {                                                // left-right flip of the brush layer: column x <- s-1-x
             unsigned src = 0u;
 #pragma unroll
-            for (int t = 0; t < MR_WORDS; ++t) if (t == nw - 1 - w) src = brush[t];
+            for (int t = 0; t < W; ++t) if (t == nw - 1 - w) src = brush[t];
             bw = __brev(src);
         }
-        const unsigned hole = keep[w] | bw;                      // punched by a rectangle or painted by the brush
+        unsigned hole = keep[w] | bw;                            // punched by a rectangle or painted by the brush
         holes += __popc(hole);
+        if (BOX) {
+            const int cin = min(max(rem - 32 * w, 0), 32);       // columns of this word inside the content box
+            hole &= cin == 32 ? 0xffffffffu : (1u << cin) - 1u;
+        }
 #pragma unroll
         for (int k4 = 0; k4 < 8; ++k4) {
             float4 v;
@@ -252,17 +267,35 @@ __global__ __launch_bounds__(256) void mask_raster_kernel(const MaskParams p) {
     atomicAdd(p.holes + b, holes);
 }
 
+static int mr_launch(const int* records, const int* offsets, const int* flips, const int* disc_table, int max_half, float* mask,
+                     int* holes, const int* boxes, int B, int s, void* stream) {
+    SHG_CHECK_ARG(records && offsets && flips && disc_table && mask && holes, "mask_raster: null pointer");
+    SHG_CHECK_ARG(B >= 1 && B <= 65535 && s >= 32 && s <= 1024 && s % 32 == 0, "mask_raster: s must be a multiple of 32 in [32, 1024]");
+    SHG_CHECK_ARG((reinterpret_cast<uintptr_t>(mask) & 15) == 0, "mask_raster: mask must be 16-byte aligned");
+    MaskParams p;
+    p.rec = records; p.off = offsets; p.flips = flips; p.disc = disc_table; p.max_half = max_half;
+    p.mask = mask; p.holes = holes; p.boxes = boxes; p.B = B; p.s = s;
+    const dim3 grid(B, shg_cdiv(s, 256)), block(256);
+    const hipStream_t st = (hipStream_t)stream;
+    if (s <= 512 && !boxes) hipLaunchKernelGGL((mask_raster_kernel<16, false>), grid, block, 0, st, p);
+    else if (s <= 512) hipLaunchKernelGGL((mask_raster_kernel<16, true>), grid, block, 0, st, p);
+    else if (!boxes) hipLaunchKernelGGL((mask_raster_kernel<32, false>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((mask_raster_kernel<32, true>), grid, block, 0, st, p);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}
+
 // records [total][8] int32, offsets [B+1], flips [B][2], disc table [max_half+1][2*max_half+1][2] (all device memory);
 // mask [B,1,s,s] float32 out (1 = keep, 0 = hole), holes [B] int32 must be zero on entry (the kernel adds the hole counts).
 extern "C" int shg_mask_raster_f32(const int* records, const int* offsets, const int* flips, const int* disc_table, int max_half,
                                    float* mask, int* holes, int B, int s, void* stream) {
-    SHG_CHECK_ARG(records && offsets && flips && disc_table && mask && holes, "mask_raster: null pointer");
-    SHG_CHECK_ARG(B >= 1 && B <= 65535 && s >= 32 && s <= 512 && s % 32 == 0, "mask_raster: s must be a multiple of 32 in [32, 512]");
-    SHG_CHECK_ARG((reinterpret_cast<uintptr_t>(mask) & 15) == 0, "mask_raster: mask must be 16-byte aligned");
-    MaskParams p;
-    p.rec = records; p.off = offsets; p.flips = flips; p.disc = disc_table; p.max_half = max_half;
-    p.mask = mask; p.holes = holes; p.B = B; p.s = s;
-    hipLaunchKernelGGL(mask_raster_kernel, dim3(B, shg_cdiv(s, 256)), dim3(256), 0, (hipStream_t)stream, p);
-    SHG_CHECK_LAUNCH();
-    return SHG_OK;
+    return mr_launch(records, offsets, flips, disc_table, max_half, mask, holes, nullptr, B, s, stream);
+}
+
+// The same with content boxes [B][2] = (h', w') int32 (device memory): keep is written at every x >= w' or y >= h'; the hole counts are
+// those of the mask before this fill.
+extern "C" int shg_mask_raster_box_f32(const int* records, const int* offsets, const int* flips, const int* disc_table, int max_half,
+                                       const int* boxes, float* mask, int* holes, int B, int s, void* stream) {
+    SHG_CHECK_ARG(boxes, "mask_raster: null pointer");
+    return mr_launch(records, offsets, flips, disc_table, max_half, mask, holes, boxes, B, s, stream);
 }

@@ -127,7 +127,8 @@ class DeviceFeeder:
 
         feeder = DeviceFeeder(device, resolution=512, device_masks=True)
         for x4, real, mask, ids in feeder(loader):      # loader yields (x [B,3,R,R] in [-1,1], mask [B,1,R,R] or None, ids)
-            img = G(x=x4, z=..., c=...)                 # or RaggedU8Batch (Places2: images of their own sizes, resized on the device)
+            img = G(x=x4, z=..., c=...)                 # or RaggedU8Batch (Places2: images of their own sizes, resized on the device;
+                                                        # OpenImages, ``fit``: resized to their boxes and padded, boxed masks)
 
     The H2D copies of batch k+1 run on a copy stream while batch k's kernels execute (pinned staging buffers, one event per batch);
     ``device_masks`` draws the freeform masks on the device instead of taking the formatter's (same distribution and, for the same
@@ -163,19 +164,24 @@ class DeviceFeeder:
 
     def _resize_on_device(self, batch):
         """RaggedU8Batch -> uint8 [B,3,R,R] on the device: the packed bytes are uploaded like any other input and resized
-        (resize.resize_bicubic_u8, Pillow's bicubic bit for bit, then the flips) on the staging stream, behind their upload."""
-        from .resize import resize_bicubic_u8
+        (resize.resize_bicubic_u8, Pillow's bicubic bit for bit, then the flips; a ``fit`` batch: resize.resize_fit_pad_u8, resized
+        to its boxes and padded) on the staging stream, behind their upload."""
+        from .resize import resize_bicubic_u8, resize_fit_pad_u8
         if self.device.type != 'cuda':
             raise ValueError('DeviceFeeder: ragged uint8 batches are resized on a HIP device (there is no host path)')
         data = self._to_device(batch.data)
         st = self.copy_stream if self.copy_stream is not None else torch.cuda.current_stream(self.device)
-        return resize_bicubic_u8(data, batch.shapes, self.resolution, flip=batch.flip, stream=st)
+        fn = resize_fit_pad_u8 if batch.fit else resize_bicubic_u8
+        return fn(data, batch.shapes, self.resolution, flip=batch.flip, stream=st)
 
     def _stage(self, batch):
+        boxes = None
         if isinstance(batch, RaggedU8Batch):
             mask, ids = batch.masks, batch.ids
             xd = self._resize_on_device(batch)
             x = xd
+            if batch.fit:
+                boxes = np.asarray(batch.content_size, dtype=np.int32).reshape(-1, 2)
         else:
             x, mask, ids = (batch[0], batch[1], batch[2]) if len(batch) == 3 else (batch[0], None, batch[1])
             xd = self._to_device(x.contiguous())
@@ -189,16 +195,20 @@ class DeviceFeeder:
             if tuple(m.shape) != (x.shape[0], x.shape[2], x.shape[3]):
                 raise ValueError(f'DeviceFeeder: masks {tuple(m.shape)} do not match the images {tuple(x.shape)} -- the formatter\'s '
                                  f'mask_resolution must equal the image resolution ({x.shape[2]}x{x.shape[3]})')
+            if boxes is not None:                 # the formatter's box fill (idempotent on OpenImages' host masks, which carry it)
+                m = m.clone()
+                for k, box in enumerate(boxes):
+                    fill_outside_box(m[k], box)
             md = self._to_device(m[:, None].contiguous())
         ev = None
         if self.copy_stream is not None:
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
-        return xd, md, ids, ev
+        return xd, md, ids, ev, boxes
 
     def _finish(self, staged):
         from . import eval_harness, masks as _masks
-        xd, md, ids, ev = staged
+        xd, md, ids, ev, boxes = staged
         if ev is not None:
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(ev)
@@ -210,13 +220,15 @@ class DeviceFeeder:
             # input staging only (on the caller's stream the read waited behind whatever else the caller had queued there)
             if self.copy_stream is not None:
                 with torch.cuda.stream(self.copy_stream):
-                    md = _masks.random_masks(xd.shape[0], self.resolution, hole_range=self.hole_range, device=self.device).to(torch.float32)
+                    md = _masks.random_masks(xd.shape[0], self.resolution, hole_range=self.hole_range, device=self.device,
+                                             boxes=boxes).to(torch.float32)
                     md = md.reshape(xd.shape[0], 1, self.resolution, self.resolution)
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_stream(self.copy_stream)
                 md.record_stream(cur)
             else:
-                md = _masks.random_masks(xd.shape[0], self.resolution, hole_range=self.hole_range, device=self.device).to(torch.float32)
+                md = _masks.random_masks(xd.shape[0], self.resolution, hole_range=self.hole_range, device=self.device,
+                                         boxes=boxes).to(torch.float32)
                 md = md.reshape(xd.shape[0], 1, self.resolution, self.resolution)
         x4 = eval_harness.assemble_input(xd, md)
         return x4, xd, md, ids
@@ -322,13 +334,112 @@ def places2_challenge512_inpainting(root_dir, **kw):
     return Places2(root_dir, 'challenge', resolution=512, random_flip=True, hole_range=(0.0, 1.0), **kw)
 
 
+# ------------------------------------------------------------------------------------------------
+# OpenImages (lib/data_factory/ds_openimages.py): images larger than R are resized to fit, then padded to R x R on the device
+# ------------------------------------------------------------------------------------------------
+
+_OPENIMAGES_DIRS = {'train': 'train', 'val': 'validation'}
+
+
+def openimages_list(root_dir, mode):
+    """load_info of ``openimages`` (ds_openimages.py:20-48) in ds_base's order (sorted by unique_id): every .jpg / .png under
+    root_dir/train ('train') or root_dir/validation ('val'), unique_id = '-'.join(subdir.split('/')[4:] + [stem]) -- no main tag,
+    unlike Places2; taken literally from the path string as given."""
+    if mode not in _OPENIMAGES_DIRS:
+        raise ValueError(mode)
+    imdir = os.path.join(root_dir, _OPENIMAGES_DIRS[mode])
+    info = []
+    for subdir, _, files in os.walk(imdir):
+        for fi in files:
+            impath = os.path.join(subdir, fi)
+            if not (impath.endswith('.jpg') or impath.endswith('.png')):
+                continue
+            uid = '-'.join(subdir.split('/')[4:] + [os.path.splitext(fi)[0]])
+            info.append({'unique_id': uid, 'filename': fi, 'image_path': impath})
+    info = sorted(info, key=lambda x: x['unique_id'])
+    for idx, e in enumerate(info):
+        e['idx'] = idx
+    return info
+
+
+def _decode_rgb_unbounded(path):
+    """``Image.open(path).convert('RGB')`` with Pillow's decompression-bomb check off, as the reference's module sets
+    ``PIL.Image.MAX_IMAGE_PIXELS = None`` -- here only for this decode: the process-wide limit is restored afterwards."""
+    from PIL import Image
+    old = Image.MAX_IMAGE_PIXELS
+    Image.MAX_IMAGE_PIXELS = None
+    try:
+        with Image.open(path) as im:
+            return np.asarray(im.convert('RGB'))
+    finally:
+        Image.MAX_IMAGE_PIXELS = old
+
+
+def fill_outside_box(mask, content_size):
+    """The box fill of OpenImages' FreeFormMaskFormatter (ds_openimages.py:161-163), in place on a [.., R, R] mask: keep (1) at every
+    column >= w' and every row >= h'."""
+    h, w = int(content_size[0]), int(content_size[1])
+    mask[..., :, w:] = 1.0
+    mask[..., h:, :] = 1.0
+    return mask
+
+
+class OpenImages(torch.utils.data.Dataset):
+    """``openimages`` + ``FixResolutionLoader`` + ``FreeFormMaskFormatter`` (ds_openimages.py:63-81,148-166) with the resize and the
+    padding moved to the device: an item is {'image': uint8 [H,W,3] at the file's own size (``Image.open(...).convert('RGB')``, no
+    decompression-bomb limit), 'flip' (one ``npr.rand()`` draw when ``random_flip``), 'unique_id', 'content_size': (h', w') =
+    ``resize.fit_size`` -- the box the image fills at the top-left of the R x R canvas} and, with ``host_masks``, 'mask' =
+    ``RandomMask(resolution, hole_range)[0]`` drawn after the flip, then set to 1 at columns >= w' and rows >= h'.
+
+    The reference's quirk is kept: the fill uses the UNFLIPPED box even when the flip has moved the content to the right edge, and
+    RandomMask's hole-ratio test sees the whole mask, before the fill.  ``collate_ragged`` makes a ``RaggedU8Batch`` with ``fit`` set;
+    ``DeviceFeeder`` resizes, pads and flips it on the device and, with device masks, applies the same fill there."""
+
+    def __init__(self, root_dir, mode, resolution=1024, random_flip=False, hole_range=(0, 1), host_masks=False, try_sample=None,
+                 repeat=1):
+        self.load_info = openimages_list(root_dir, mode)
+        if try_sample is not None:
+            self.load_info = self.load_info[:try_sample]
+        self.resolution, self.random_flip, self.hole_range = int(resolution), bool(random_flip), list(hole_range)
+        self.host_masks, self.repeat = bool(host_masks), repeat
+
+    def __len__(self):
+        return len(self.load_info) * self.repeat
+
+    def __getitem__(self, idx):
+        from .resize import fit_size
+        e = self.load_info[idx % len(self.load_info)]
+        u8 = _decode_rgb_unbounded(e['image_path'])
+        try:
+            box = fit_size(u8.shape[0], u8.shape[1], self.resolution)
+        except ValueError as err:
+            raise ValueError(f'{e["image_path"]}: {err}') from None
+        item = {'image': u8, 'flip': bool(self.random_flip and npr.rand() < 0.5), 'unique_id': e['unique_id'], 'content_size': box}
+        if self.host_masks:
+            item['mask'] = fill_outside_box(_data.RandomMask(self.resolution, self.hole_range)[0], box)
+        return item
+
+
+def openimages_val_1024(root_dir, **kw):
+    """configs/dataset/openimages.yaml ``openimages_val_1024``."""
+    return OpenImages(root_dir, 'val', resolution=1024, random_flip=False, hole_range=(0.0, 1.0), **kw)
+
+
+def openimages_train_1024(root_dir, **kw):
+    """configs/dataset/openimages.yaml ``openimages_train_1024``."""
+    return OpenImages(root_dir, 'train', resolution=1024, random_flip=True, hole_range=(0.0, 1.0), **kw)
+
+
 class RaggedU8Batch:
     """A batch of decoded images of their own sizes: ``data`` uint8 [sum h*w*3] (HWC RGB images back to back, pinned when built in a
     process that owns the device), ``shapes`` int32 [B,3] = (h, w, byte offset), ``flip`` bool [B], ``ids``, ``masks`` float32 [B,R,R] or
-    None.  ``DeviceFeeder`` / ``EvalLoop.run`` take it in place of an image tensor; ``pin_memory`` lets a DataLoader pin it."""
+    None.  ``DeviceFeeder`` / ``EvalLoop.run`` take it in place of an image tensor; ``pin_memory`` lets a DataLoader pin it.
+    ``fit`` (OpenImages): the images are resized to ``content_size`` int32 [B,2] = (h', w') and padded to R x R instead of resized to
+    R x R (Places2: ``fit`` False, ``content_size`` None)."""
 
-    def __init__(self, data, shapes, flip, ids, masks=None):
+    def __init__(self, data, shapes, flip, ids, masks=None, fit=False, content_size=None):
         self.data, self.shapes, self.flip, self.ids, self.masks = data, shapes, flip, list(ids), masks
+        self.fit, self.content_size = bool(fit), content_size
 
     def __len__(self):
         return int(self.shapes.shape[0])
@@ -340,7 +451,8 @@ class RaggedU8Batch:
 
 
 def collate_ragged(items):
-    """Places2 items -> RaggedU8Batch (``torch.utils.data.DataLoader(collate_fn=collate_ragged)``)."""
+    """Places2 or OpenImages items -> RaggedU8Batch (``torch.utils.data.DataLoader(collate_fn=collate_ragged)``); items with a
+    'content_size' (OpenImages) make a ``fit`` batch."""
     from .resize import pack_images
     data, shapes = pack_images([it['image'] for it in items])
     flip = torch.tensor([bool(it['flip']) for it in items], dtype=torch.bool)
@@ -349,4 +461,8 @@ def collate_ragged(items):
         masks = torch.from_numpy(np.stack([np.asarray(it['mask'], np.float32) for it in items]))
     if torch.utils.data.get_worker_info() is None and torch.cuda.is_available():
         data = data.pin_memory()
-    return RaggedU8Batch(data, shapes, flip, [it['unique_id'] for it in items], masks)
+    fit = bool(items) and all('content_size' in it for it in items)
+    if not fit and any('content_size' in it for it in items):
+        raise ValueError('collate_ragged: a batch mixes OpenImages items (content_size) with items resized to R x R')
+    content_size = torch.tensor([list(it['content_size']) for it in items], dtype=torch.int32).reshape(-1, 2) if fit else None
+    return RaggedU8Batch(data, shapes, flip, [it['unique_id'] for it in items], masks, fit=fit, content_size=content_size)

@@ -181,11 +181,13 @@ def disc_span_table():
     return _disc_table
 
 
-def rasterize(records, offsets, flips, s, device='cuda'):
+def rasterize(records, offsets, flips, s, device='cuda', boxes=None):
     """records [total,8] int32, offsets [B+1], flips [B,2] (host arrays) -> (mask float32 [B,1,s,s] with 1 = keep / 0 = hole,
-    hole counts int32 [B]) on ``device``: one H2D copy of the primitive lists, one kernel."""
-    if s > 512 or s % 32 != 0:
-        raise _lib.ShgError('mask rasteriser: s must be a multiple of 32, at most 512')
+    hole counts int32 [B]) on ``device``: one H2D copy of the primitive lists, one kernel.  ``boxes`` [B,2] = content (h', w') per
+    mask or None: keep is written at x >= w' or y >= h' (FreeFormMaskFormatter of ds_openimages.py:148-166); the hole counts are
+    those of the whole mask, before that fill."""
+    if s < 32 or s > 1024 or s % 32 != 0:
+        raise _lib.ShgError('mask rasteriser: s must be a multiple of 32 in [32, 1024]')
     if records.shape[0] and int(records[records[:, 0] == DISC, 3].max(initial=0)) > MAX_HALF:
         raise _lib.ShgError('mask rasteriser: disc radius beyond the span table')
     dev = torch.device(device)
@@ -196,12 +198,16 @@ def rasterize(records, offsets, flips, s, device='cuda'):
     rec_h = np.ascontiguousarray(records.reshape(-1), dtype=np.int32) if records.shape[0] else np.zeros(REC, np.int32)
     off_h = np.asarray(offsets, dtype=np.int32)
     flip_h = np.asarray(flips, dtype=np.int32).reshape(-1)
-    n_rec, n_off, n_flip = rec_h.size, off_h.size, flip_h.size
+    box_h = np.zeros(0, np.int32) if boxes is None else np.asarray(boxes, dtype=np.int32).reshape(-1)
+    if boxes is not None and box_h.size != 2 * b:
+        raise _lib.ShgError(f'mask rasteriser: boxes must be [{b}, 2] (got {box_h.size} values)')
+    n_rec, n_off, n_flip, n_box = rec_h.size, off_h.size, flip_h.size, box_h.size
     o_off = (n_rec + 3) // 4 * 4                         # 16-byte aligned sections
     o_flip = o_off + (n_off + 3) // 4 * 4
-    stage = torch.empty(o_flip + n_flip, dtype=torch.int32, pin_memory=(dev.type == 'cuda'))
+    o_box = o_flip + (n_flip + 3) // 4 * 4
+    stage = torch.empty(o_box + n_box, dtype=torch.int32, pin_memory=(dev.type == 'cuda'))
     sv = stage.numpy()
-    sv[:n_rec], sv[o_off:o_off + n_off], sv[o_flip:o_flip + n_flip] = rec_h, off_h, flip_h
+    sv[:n_rec], sv[o_off:o_off + n_off], sv[o_flip:o_flip + n_flip], sv[o_box:o_box + n_box] = rec_h, off_h, flip_h, box_h
     stage_d = stage.to(dev, non_blocking=True)
     rec_d, off_d, flip_d = stage_d[:n_rec], stage_d[o_off:o_off + n_off], stage_d[o_flip:o_flip + n_flip]
     tab_d = _table_on(dev)
@@ -211,9 +217,15 @@ def rasterize(records, offsets, flips, s, device='cuda'):
     for t, nm in ((rec_d, 'records'), (off_d, 'offsets'), (flip_d, 'flips'), (tab_d, 'table'), (holes, 'holes')):
         L.req(t, nm, dtype=torch.int32)
     L.req(mask, 'mask')
+    lib = _lib.get_lib()
     with L:
-        check(_lib.get_lib().shg_mask_raster_f32(kernels._ptr(rec_d), kernels._ptr(off_d), kernels._ptr(flip_d), kernels._ptr(tab_d),
-                                                 MAX_HALF, kernels._ptr(mask), kernels._ptr(holes), b, s, L.stream()), 'mask_raster')
+        if boxes is None:
+            check(lib.shg_mask_raster_f32(kernels._ptr(rec_d), kernels._ptr(off_d), kernels._ptr(flip_d), kernels._ptr(tab_d), MAX_HALF,
+                                          kernels._ptr(mask), kernels._ptr(holes), b, s, L.stream()), 'mask_raster')
+        else:
+            box_d = stage_d[o_box:o_box + n_box]
+            check(lib.shg_mask_raster_box_f32(kernels._ptr(rec_d), kernels._ptr(off_d), kernels._ptr(flip_d), kernels._ptr(tab_d), MAX_HALF,
+                                              kernels._ptr(box_d), kernels._ptr(mask), kernels._ptr(holes), b, s, L.stream()), 'mask_raster')
     return mask, holes
 
 
@@ -227,9 +239,13 @@ def _table_on(dev):
     return _tables[key]
 
 
-def random_masks(n, s, hole_range=(0, 1), device='cuda', batch=64):
+def random_masks(n, s, hole_range=(0, 1), device='cuda', batch=64, boxes=None):
     """``n`` masks of ``RandomMask(s, hole_range)`` drawn from numpy's global RNG, rasterised on ``device``:
-    float32 [n,1,s,s].  Same masks (and same final RNG state) as n sequential calls of the reference function."""
+    float32 [n,1,s,s].  Same masks (and same final RNG state) as n sequential calls of the reference function.  ``boxes`` [n,2] =
+    content (h', w') of mask i or None: keep is then written at x >= w' or y >= h' after the draw (the box fill of OpenImages'
+    ``FreeFormMaskFormatter``); the rejection loop sees the hole ratio of the whole mask, as the reference's does."""
+    if boxes is not None:
+        boxes = np.asarray(boxes, dtype=np.int32).reshape(n, 2)
     out = []
     while len(out) < n:
         want = min(batch, n - len(out))
@@ -240,7 +256,8 @@ def random_masks(n, s, hole_range=(0, 1), device='cuda', batch=64):
             recs.append(r)
             offs.append(offs[-1] + len(r))
             flips.append((int(f0), int(f1)))
-        mask, holes = rasterize(np.concatenate(recs, axis=0) if offs[-1] else np.zeros((0, REC), np.int32), offs, flips, s, device)
+        bx = None if boxes is None else boxes[len(out):len(out) + want]
+        mask, holes = rasterize(np.concatenate(recs, axis=0) if offs[-1] else np.zeros((0, REC), np.int32), offs, flips, s, device, bx)
         ratio = holes.cpu().numpy().astype(np.float64) / float(s * s)        # the one synchronisation per batch
         ok = ~((ratio <= hole_range[0]) | (ratio >= hole_range[1])) if hole_range is not None else np.ones(want, bool)
         if ok.all():

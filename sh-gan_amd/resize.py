@@ -10,7 +10,11 @@ Pillow's 8-bit resample (``ImagingResample``) is integer arithmetic on coefficie
 The tables are built here (double precision, the taps accumulated in Pillow's order: vectorised over output indices, looped over
 taps), cached per (in, out) pair, and uploaded with the batch; the kernel (csrc/resize.hip) only adds integers, so the device result
 is bit-exact by construction.  An axis that keeps its size gets the one-tap identity table (k = 1 << 22), which is Pillow's skipped
-pass in the same arithmetic.  ``resize_reference`` is the same two passes in numpy (CPU tests)."""
+pass in the same arithmetic.  ``resize_reference`` is the same two passes in numpy (CPU tests).
+
+OpenImages (``FixResolutionLoader`` of lib/data_factory/ds_openimages.py:63-81) resizes only images larger than R, to the box
+``fit_size`` keeps their aspect ratio in, and pastes the result at the top-left of a zero R x R canvas: ``build_fit_table`` /
+``resize_fit_pad_u8`` (one launch, padding included) and the numpy ``fit_reference``."""
 import ctypes
 
 import numpy as np
@@ -22,6 +26,7 @@ from ._lib import check
 PRECISION_BITS = 22
 LDS_BYTES = 49152                    # csrc/resize.hip RS_LDS_BYTES: the horizontally resampled band of one workgroup
 DESC_INTS = 12                       # csrc/resize.hip: per-image descriptor
+FIT_DESC_INTS = 14                   # csrc/resize.hip: per-image descriptor of the fit-and-pad launch (+ h', w')
 _COEF_CACHE = {}
 
 
@@ -95,6 +100,35 @@ def resize_reference(img, R, flip=False):
     return np.ascontiguousarray(out.transpose(2, 0, 1))
 
 
+def fit_size(h, w, R):
+    """-> (h', w'): the size FixResolutionLoader (ds_openimages.py:68-72) gives an h x w image at resolution R.  Only images with a side
+    above R are resized, to ``(R, int(h * R / w))`` (w > h) or ``(int(w * R / h), R)``, in float64 exactly as written there -- not
+    ``h * R // w``: at R = 1024 a 1122 x 1122 image gets (h', w') = (1024, 1023), one column short of the canvas.  A box of 0 pixels
+    raises the ValueError Pillow's resize raises."""
+    h, w, R = int(h), int(w), int(R)
+    if w > R or h > R:
+        ratio = R / w if w > h else R / h
+        w, h = (R, int(h * ratio)) if w > h else (int(w * ratio), R)
+        if w <= 0 or h <= 0:
+            raise ValueError('height and width must be > 0')
+    return h, w
+
+
+def fit_reference(img, R, flip=False):
+    """Host reference of the OpenImages input: uint8 HWC RGB -> uint8 [3, R, R] = the image resized to ``fit_size`` (Pillow's 8-bit
+    bicubic, as resize_reference) at the top-left of a zero canvas, the whole canvas mirrored when ``flip``."""
+    img = np.asarray(img, np.uint8)
+    h, w = img.shape[:2]
+    oh, ow = fit_size(h, w, R)
+    mid = img if w == ow else _pass(img, *bicubic_coeffs(w, ow), axis=1)
+    out = mid if h == oh else _pass(mid, *bicubic_coeffs(h, oh), axis=0)
+    canvas = np.zeros((R, R, 3), np.uint8)
+    canvas[:oh, :ow] = out
+    if flip:
+        canvas = canvas[:, ::-1]
+    return np.ascontiguousarray(canvas.transpose(2, 0, 1))
+
+
 def _tiling(h, R):
     """(band rows TB, column chunk CW, LDS bytes) of one image: the tallest band (fewest source rows resampled twice by neighbouring
     bands) whose source rows, resampled to a chunk of at most 128 columns, fit the workgroup's LDS (3 planes x rows x chunk, uint8)."""
@@ -109,6 +143,57 @@ def _tiling(h, R):
             if cw <= R and lds <= LDS_BYTES:
                 return tb, cw, lds
     raise ValueError(f'resize: a {h}-row image is too tall to resample to {R} rows in one workgroup band')
+
+
+def _fit_tiling(h, oh, R):
+    """_tiling for an image of h rows resampled to oh <= R box rows on an R-row canvas: the bands cover the canvas, the LDS holds the
+    source rows of the box part of a band."""
+    bounds, _ = bicubic_coeffs(h, oh)
+    lo, hi = bounds[:, 0].astype(np.int64), (bounds[:, 0] + bounds[:, 1]).astype(np.int64)
+    for tb in (16, 8, 4, 2, 1):
+        tb = min(tb, R)
+        starts = np.arange(0, oh, tb)
+        span = int((hi[np.minimum(starts + tb, oh) - 1] - lo[starts]).max())
+        for cw in (min(R, 128), 64, 32, 16):
+            lds = 3 * span * ((cw + 3) // 4 * 4)
+            if cw <= R and lds <= LDS_BYTES:
+                return tb, cw, lds
+    raise ValueError(f'resize: a {h}-row image is too tall to resample to {oh} rows in one workgroup band')
+
+
+def build_fit_table(shapes, R, flip=None):
+    """Host side of one fit-and-pad launch: shapes int [B, 3] = (h, w, byte offset) -> (int32 table, chunks, bands, LDS bytes).
+    table = B descriptors of FIT_DESC_INTS ints (build_table's 12, then the box h', w' of ``fit_size``), then each distinct (in, out)
+    pair's bounds and coefficients once (an image that keeps its size on an axis gets the identity table of that size)."""
+    shapes = np.asarray(shapes, np.int64).reshape(-1, 3)
+    B = shapes.shape[0]
+    R = int(R)
+    flip = np.zeros(B, np.int64) if flip is None else np.asarray(flip).astype(np.int64).reshape(B)
+    desc = np.zeros((B, FIT_DESC_INTS), np.int64)
+    parts, placed, pos = [], {}, B * FIT_DESC_INTS
+
+    def place(n_in, n_out):
+        nonlocal pos
+        key = (n_in, n_out)
+        if key not in placed:
+            bounds, k = bicubic_coeffs(n_in, n_out)
+            placed[key] = (pos, pos + bounds.size, k.shape[1])
+            parts.extend([bounds.reshape(-1), k.reshape(-1)])
+            pos += bounds.size + k.size
+        return placed[key]
+
+    chunks = bands = lds_bytes = 1
+    for i, (h, w, off) in enumerate(shapes):
+        if h < 1 or w < 1 or off < 0:
+            raise ValueError(f'resize: image {i} has shape {h}x{w} at offset {off}')
+        oh, ow = fit_size(h, w, R)
+        tb, cw, lds = _fit_tiling(int(h), oh, R)
+        desc[i] = (h, w, off, flip[i] != 0) + place(int(w), ow) + place(int(h), oh) + (tb, cw, oh, ow)
+        chunks, bands, lds_bytes = max(chunks, -(-R // cw)), max(bands, -(-R // tb)), max(lds_bytes, lds)
+    if pos >= 2 ** 31:
+        raise ValueError('resize: coefficient table too large')
+    table = np.concatenate([desc.reshape(-1).astype(np.int32)] + [p.astype(np.int32) for p in parts])
+    return table, chunks, bands, max(lds_bytes, 12)
 
 
 def build_table(shapes, R, flip=None):
@@ -164,6 +249,28 @@ def resize_bicubic_u8(packed, shapes, R, flip=None, stream=None):
         check(_lib.get_lib().shg_resize_bicubic_u8(ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(tab.data_ptr()),
                                                    tab.numel(), ctypes.c_void_p(out.data_ptr()), B, R, chunks, bands, lds_bytes,
                                                    ctypes.c_void_p(st.cuda_stream)), 'resize_bicubic_u8')
+    return out
+
+
+def resize_fit_pad_u8(packed, shapes, R, flip=None, stream=None):
+    """The OpenImages input: packed / shapes / flip / stream as resize_bicubic_u8 -> uint8 [B, 3, R, R], image i resized to
+    ``fit_size(h, w, R)`` at the top-left of a zero canvas (the whole canvas mirrored when flip[i]).  One launch writes every byte."""
+    if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.uint8):
+        raise _lib.ShgError('resize_fit_pad_u8: packed must be a uint8 HIP tensor: libshgan_hip has no CPU path')
+    packed = packed.contiguous().view(-1)
+    shapes = shapes.numpy() if isinstance(shapes, torch.Tensor) else shapes
+    flip = flip.numpy() if isinstance(flip, torch.Tensor) else flip
+    R = int(R)
+    table, chunks, bands, lds_bytes = build_fit_table(shapes, R, flip)
+    B = np.asarray(shapes).reshape(-1, 3).shape[0]
+    dev = packed.device
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        tab = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
+        out = torch.empty((B, 3, R, R), dtype=torch.uint8, device=dev)
+        check(_lib.get_lib().shg_resize_fit_pad_u8(ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(tab.data_ptr()),
+                                                   tab.numel(), ctypes.c_void_p(out.data_ptr()), B, R, chunks, bands, lds_bytes,
+                                                   ctypes.c_void_p(st.cuda_stream)), 'resize_fit_pad_u8')
     return out
 
 
