@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark (BASELINE.json): SH-GAN generator forward, images/s at 512x512 batch 16 per GPU.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs / --digest-out when
+asked, and prints one JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, the run's configuration).  Everything else
+the benchmark measures runs only with --full, after the headline loop and outside its timing: the one-batch-alone latency, the
+instrumented per-kernel pass (roofline / hbm / shu), the evaluation-loop block, the 256x32 and fp16 configurations, the training steps
+and the CPU baseline.
 
 N > 1 without a launcher: this script spawns its own N ranks (torch.multiprocessing.spawn, one per GPU, as the
 reference's main.py:83-89 does); under ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`` it
@@ -16,10 +22,11 @@ the data path (weak scaling); the timed region is bracketed by barrier + synchro
 The K timed steps are K independent batches, as in the evaluation loop of the product (eval_harness.sharded_eval): they are issued
 round-robin on --pipeline-depth HIP streams (default 3; eval_harness.StreamPipeline), so that the few microseconds every one of the
 ~150 launch boundaries of a forward pass idles the chip are filled by the next batch's kernels.  ms_per_step = wall time / K;
-the time of one batch alone on one stream is reported as pipeline.ms_per_step_single_stream (--pipeline-depth 1 makes it the headline).
+with --full, the time of one batch alone on one stream is reported as pipeline.ms_per_step_single_stream (--pipeline-depth 1 makes it
+the headline).
 
-The headline loop runs WITHOUT instrumentation.  A second, untimed pass then brackets every kernel launch with HIP
-events on the launch stream (kernels.KernelTimer) and rank 0 prints ONE JSON line with
+The headline loop runs WITHOUT instrumentation.  With --full, a second, untimed pass then brackets every kernel launch with HIP
+events on the launch stream (kernels.KernelTimer), and rank 0's ONE JSON line also carries
   roofline      the dominant kernel (conv_wino4_kernel, Winograd F(4x4,3x3)): flops the matrix cores EXECUTE (36 multiplies per
                 4x4 block = 1/4 of the direct form) / HIP-event time / dense fp32-MFMA peak; the direct-form ("algorithmic")
                 rate is reported beside it under its own key, per convolution class;
@@ -127,7 +134,7 @@ def cpu_baseline(resolution, bench_batch, n_images, forwards, noise_mode, seed, 
                        f'{noise_mode!r}, oracle/shgan_oracle.py (torch CPU fp32, {threads} threads)')
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=30)
@@ -135,18 +142,23 @@ def parse():
     ap.add_argument('--resolution', type=int, default=512)
     ap.add_argument('--batch', type=int, default=None, help='per-GPU batch (default 16 @512, 32 @256)')
     ap.add_argument('--noise-mode', default='random')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-images', type=int, default=None, help='images per CPU forward (default: the full bench batch, SURVEY 8d)')
-    ap.add_argument('--cpu-forwards', type=int, default=3, help='timed CPU forwards after one warm-up (SURVEY 8d: >= 3)')
-    ap.add_argument('--no-second-config', action='store_true', help='skip the 256x256 batch-32 block (BASELINE config 2)')
-    ap.add_argument('--no-train-step', action='store_true', help='skip the config-5 training-step block')
-    ap.add_argument('--no-eval-loop', action='store_true', help='skip the config-4 evaluation-loop block')
-    ap.add_argument('--eval-loop', action='store_true', help='N > 1: run the evaluation-loop block too (its all-gather / all-reduce then span the ranks)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure everything else: one-batch-alone latency, the instrumented per-kernel pass, the '
+                         'evaluation loop, the 256x32 and fp16 configurations, the training steps, the CPU baseline (the options below '
+                         'marked "--full" select among them)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--cpu-images', type=int, default=None, help='--full: images per CPU forward (default: the full bench batch, SURVEY 8d)')
+    ap.add_argument('--cpu-forwards', type=int, default=3, help='--full: timed CPU forwards after one warm-up (SURVEY 8d: >= 3)')
+    ap.add_argument('--no-second-config', action='store_true', help='--full: skip the 256x256 batch-32 block (BASELINE config 2)')
+    ap.add_argument('--no-train-step', action='store_true', help='--full: skip the config-5 training-step block')
+    ap.add_argument('--no-eval-loop', action='store_true', help='--full: skip the config-4 evaluation-loop block')
+    ap.add_argument('--eval-loop', action='store_true',
+                    help='implies --full; N > 1: run the evaluation-loop block too (its all-gather / all-reduce then span the ranks)')
     ap.add_argument('--all-blocks', action='store_true',
-                    help='N > 1: also run the informational second_config / train_step blocks (default: N = 1 only, so that a scaling run '
-                         'measures the headline and nothing can stand between it and its JSON line)')
-    ap.add_argument('--train-batch', type=int, default=8)
-    ap.add_argument('--train-steps', type=int, default=3)
+                    help='implies --full; N > 1: also run the informational second_config / train_step blocks (default: N = 1 only, so that a '
+                         'scaling run measures the headline and nothing can stand between it and its JSON line)')
+    ap.add_argument('--train-batch', type=int, default=8, help='--full: per-GPU batch of the training-step block')
+    ap.add_argument('--train-steps', type=int, default=3, help='--full: timed steps of the training-step block')
     ap.add_argument('--watchdog', type=int, default=0,
                     help='seconds: every rank dumps the Python stacks of all its threads to stderr every so often (faulthandler) -- says where a '
                          'multi-rank run is waiting; 0 = off')
@@ -155,7 +167,7 @@ def parse():
                          'captures and is not slower than the eager loop in a short trial')
     ap.add_argument('--pipeline-depth', type=int, default=None,
                     help='HIP streams the consecutive (independent) batches are issued on round-robin; 1 = one stream')
-    ap.add_argument('--profile-steps', type=int, default=3, help='steps of the instrumented second pass (0 = skip)')
+    ap.add_argument('--profile-steps', type=int, default=3, help='--full: steps of the instrumented second pass (0 = skip)')
     ap.add_argument('--digest-out', default=None,
                     help='write {sample id: sha256 of its uint8 output} of this rank\'s last timed step to <path>.rank<r>.json and the '
                          'uint8 images to <path>.rank<r>.npy (tests/test_gpu_bench_ranks.py compares the ranks of an N = 2 run with the '
@@ -163,9 +175,11 @@ def parse():
     ap.add_argument('--dump-outputs', default=None, metavar='DIR',
                     help='write what the headline loop returned in its last timed step to DIR/<name>.npy (float32, at most 64 MB in all; a '
                          'fixed, seeded sample of a larger output) so that two builds can be compared output for output')
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error('--steps must be at least 1')
+    if a.eval_loop or a.all_blocks:            # they ask for blocks of the full run: a run given either one is a --full run
+        a.full = True
     return a
 
 
@@ -478,6 +492,94 @@ def train_block(a, dev, rank, world, barrier, use_dist, backend, fp16=False):
             'conv_kernel_ms': round(sum(v['ms_per_step'] for k, v in cls.items() if k.startswith('conv')), 2) if cls else None}
 
 
+def kernel_report(tsum, psteps, res, batch, ms):
+    """--full: the roofline / hbm / shu blocks of the JSON line from the instrumented pass (kernels.KernelTimer summary ``tsum`` of
+    ``psteps`` steps); ``ms`` = the headline's ms_per_step."""
+    def cls_conv(name):
+        d = tsum.get(name)
+        if not d or d['ms'] <= 0:
+            return None
+        sec = d['ms'] * 1e-3
+        return {'launches_per_step': d['calls'] // psteps, 'ms_per_step': round(d['ms'] / psteps, 3),
+                'avg_launch_us': round(d['ms'] / d['calls'] * 1e3, 1),
+                'executed_tflops': round(d['executed'] / sec / 1e12, 2),
+                'frac_of_fp32_mfma_peak': round(d['executed'] / sec / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
+                'direct_form_tflops': round(d['work'] / sec / 1e12, 2)}
+
+    def cls_hbm(name):
+        d = tsum.get(name)
+        if not d or d['ms'] <= 0:
+            return None
+        gbs = d['work'] / (d['ms'] * 1e-3) / 1e9
+        return {'launches_per_step': d['calls'] // psteps, 'ms_per_step': round(d['ms'] / psteps, 3),
+                'algorithmic_GB_per_step': round(d['work'] / psteps / 1e9, 3), 'achieved_GBps': round(gbs, 1),
+                'frac_of_hbm_peak': round(gbs / PEAK_HBM_GBS, 4)}
+
+    conv = {k: v for k, v in ((n_, cls_conv(n_)) for n_ in sorted(tsum) if n_.startswith('conv_')) if v}
+    hbm = {k: v for k, v in ((n, cls_hbm(n)) for n in ('upfirdn2d', 'fir_up_planar', 'torgb', 'fromrgb', 'composite_u8'))
+           if v}
+
+    def shu_block():
+        # the Spectral Hint Unit's three launches, each against the roof that bounds it: the spectral stage (1x1 conv + ReLU + band
+        # filter: 64-wide GEMMs per spectral pixel) is matrix work on the fp32 MFMA; the two transform stages are short dependent
+        # chains per 64x64 plane (row DFT, column DFT as MFMA passes with a barrier between) on a few MB -- latency-bound: their time
+        # is the figure, the byte rate is listed only to show they are nowhere near HBM
+        st = {}
+        floors = shu_floors()
+        for name, kind in (('shu_rfft2', 'latency'), ('shu_spectral', 'mfma'), ('shu_irfft2', 'latency')):
+            d = tsum.get(name)
+            if not d or d['ms'] <= 0:
+                continue
+            e = {'us_per_step': round(d['ms'] / psteps * 1e3, 1), 'launches_per_step': d['calls'] // psteps, 'bound': kind}
+            if kind == 'mfma':
+                tf = d['work'] / (d['ms'] * 1e-3) / 1e12
+                e.update(executed_tflops=round(tf, 2), frac_of_fp32_mfma_peak=round(tf / PEAK_FP32_MFMA_TFLOPS, 4))
+            else:
+                e['algorithmic_GBps'] = round(d['work'] / (d['ms'] * 1e-3) / 1e9, 1)
+            if name in floors:
+                pr, sk, em = floors[name]
+                e.update(floor_us=sk, empty_launch_us=em, back_to_back_us=pr, frac_of_floor=round(sk / pr, 3))
+            st[name] = e
+        if not st:
+            return None
+        return {'ms_per_step': round(sum(v['us_per_step'] for v in st.values()) / 1e3, 4), 'stages': st,
+                'floor_source': 'profiles/r06_shu_floor.txt' if floors else None,
+                'floor_note': 'floor_us = a skeleton launch of the same grid / LDS / load-store footprint without arithmetic, back_to_back_us = the product '
+                              'kernel in the same probe (no per-launch events), frac_of_floor = floor / product there; us_per_step is this run\'s '
+                              'HIP-event time inside the generator (launch gaps included)' if floors else None}
+    shu = shu_block()
+    conv_ms = sum(tsum[k]['ms'] for k in tsum if k.startswith('conv_'))
+    conv_exec = sum(tsum[k]['executed'] for k in tsum if k.startswith('conv_'))
+    conv_alg = sum(tsum[k]['work'] for k in tsum if k.startswith('conv_'))
+    # the dominant kernel = the convolution class with the largest share of the step
+    DOM = {'conv_wino4': ('conv_wino4_kernel', 'Winograd F(4x4,3x3), 3x3 stride-1 layers: 36/144 of the direct-form flops'),
+           'conv_wino': ('conv_wino_kernel', 'Winograd F(2x2,3x3), 3x3 stride-1 layers: 16/36 of the direct-form flops')}
+    dom_name = max((k for k in conv if k in DOM), key=lambda k: conv[k]['ms_per_step'], default=None)
+    dom = conv.get(dom_name)
+    traffic, traffic_src = pmc_traffic(res, batch, DOM[dom_name][0]) if dom_name else (None, None)
+    roof = {'bound': 'mfma', 'kernel': f'{DOM[dom_name][0]} ({DOM[dom_name][1]}; the largest share of a step)' if dom_name else None,
+            'achieved': dom['executed_tflops'] if dom else None, 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
+            'frac': dom['frac_of_fp32_mfma_peak'] if dom else None,
+            'definition': 'flops executed on the matrix cores (Winograd: the multiplies of the transformed products, not the direct-form '
+                          'count) / HIP-event time of the launches in the instrumented pass / dense fp32 MFMA peak (157.3 TFLOP/s at '
+                          '2.4 GHz; under this load the chip sustains about 2.1 GHz)',
+            'avg_launch_us': dom['avg_launch_us'] if dom else None,
+            'direct_form_tflops': dom['direct_form_tflops'] if dom else None,
+            'traffic': traffic, 'traffic_unit': 'GB per launch (HBM read+write, PMC FETCH_SIZE*2 + WRITE_SIZE)',
+            'traffic_source': f'constant of the committed profile {traffic_src}, not measured in this run' if traffic_src else None,
+            'traffic_classes': pmc_traffic_classes(res, batch),
+            'classes': conv,
+            'all_conv': {'ms_per_step': round(conv_ms / psteps, 3) if psteps else None,
+                         'executed_tflops': round(conv_exec / (conv_ms * 1e-3) / 1e12, 2) if conv_ms else None,
+                         'frac_of_fp32_mfma_peak': round(conv_exec / (conv_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4) if conv_ms else None,
+                         'direct_form_tflops': round(conv_alg / (conv_ms * 1e-3) / 1e12, 2) if conv_ms else None},
+            'whole_step': {'executed_gflop_per_step': round(conv_exec / psteps / 1e9, 1) if psteps else None,
+                           'executed_tflops_over_wall': round(conv_exec / psteps / (ms * 1e-3) / 1e12, 2) if psteps else None,
+                           'frac_of_fp32_mfma_peak': round(conv_exec / psteps / (ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4) if psteps else None,
+                           'direct_form_gflop_per_image': GFLOP_PER_IMAGE.get(res)}}
+    return {'roofline': roof, 'hbm': {'bound': 'hbm', 'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'classes': hbm}, 'shu': shu}
+
+
 def worker(local_rank, a, spawned_world=None, port=None):
     """One rank.  ``spawned_world`` is set when this process was started by bench.py's own spawn."""
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')     # dmabuf IPC: RCCL / device-memory sharing across processes needs it on this driver
@@ -621,9 +723,9 @@ def worker(local_rank, a, spawned_world=None, port=None):
         # stylegan.py:147, so digests of one id agree across batch compositions only up to a few truncation flips
         np.save(f'{a.digest_out}.rank{rank}.npy', o8)
     dumped = dump_outputs(a.dump_outputs, {'composite': out}, '' if world == 1 else f'_rank{rank}', 64_000_000 // world) if a.dump_outputs else None
-    # one batch alone on one stream (latency of a step; not the headline)
+    # ---- --full only, after the headline and outside its timing: one batch alone on one stream (latency of a step)
     lat_ms = None
-    if rank == 0:
+    if a.full and rank == 0:
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(3):
@@ -632,9 +734,9 @@ def worker(local_rank, a, spawned_world=None, port=None):
         lat_ms = (time.perf_counter() - t1) / 3 * 1e3
     barrier()
 
-    # ---- second pass (not part of the headline): per-kernel-class HIP-event times
+    # ---- --full only, second pass: per-kernel-class HIP-event times
     tsum = {}
-    psteps = max(0, a.profile_steps)
+    psteps = max(0, a.profile_steps) if a.full else 0
     if rank == 0 and psteps:
         timer = kernels.KernelTimer()
         kernels.set_timer(timer)
@@ -647,8 +749,8 @@ def worker(local_rank, a, spawned_world=None, port=None):
     del pipe, gpipe
     torch.cuda.empty_cache()
     second = train = fp16_eval = evloop = None
-    extra = world == 1 or a.all_blocks
-    if (extra or a.eval_loop) and not a.no_eval_loop:
+    extra = a.full and (world == 1 or a.all_blocks)
+    if a.full and (extra or a.eval_loop) and not a.no_eval_loop:
         try:
             evloop = eval_loop_block(G, res, batch, a.steps, a, dev, rank, world, barrier, use_dist, backend)
         except Exception as e:             # informational block: never lose the headline over it
@@ -672,93 +774,10 @@ def worker(local_rank, a, spawned_world=None, port=None):
     if rank == 0:
         ms = dt / a.steps * 1e3
         ips = world * batch * a.steps / dt
-
-        def cls_conv(name):
-            d = tsum.get(name)
-            if not d or d['ms'] <= 0:
-                return None
-            sec = d['ms'] * 1e-3
-            return {'launches_per_step': d['calls'] // psteps, 'ms_per_step': round(d['ms'] / psteps, 3),
-                    'avg_launch_us': round(d['ms'] / d['calls'] * 1e3, 1),
-                    'executed_tflops': round(d['executed'] / sec / 1e12, 2),
-                    'frac_of_fp32_mfma_peak': round(d['executed'] / sec / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
-                    'direct_form_tflops': round(d['work'] / sec / 1e12, 2)}
-
-        def cls_hbm(name):
-            d = tsum.get(name)
-            if not d or d['ms'] <= 0:
-                return None
-            gbs = d['work'] / (d['ms'] * 1e-3) / 1e9
-            return {'launches_per_step': d['calls'] // psteps, 'ms_per_step': round(d['ms'] / psteps, 3),
-                    'algorithmic_GB_per_step': round(d['work'] / psteps / 1e9, 3), 'achieved_GBps': round(gbs, 1),
-                    'frac_of_hbm_peak': round(gbs / PEAK_HBM_GBS, 4)}
-
-        conv = {k: v for k, v in ((n_, cls_conv(n_)) for n_ in sorted(tsum) if n_.startswith('conv_')) if v}
-        hbm = {k: v for k, v in ((n, cls_hbm(n)) for n in ('upfirdn2d', 'fir_up_planar', 'torgb', 'fromrgb', 'composite_u8'))
-               if v}
-
-        def shu_block():
-            # the Spectral Hint Unit's three launches, each against the roof that bounds it: the spectral stage (1x1 conv + ReLU + band
-            # filter: 64-wide GEMMs per spectral pixel) is matrix work on the fp32 MFMA; the two transform stages are short dependent
-            # chains per 64x64 plane (row DFT, column DFT as MFMA passes with a barrier between) on a few MB -- latency-bound: their time
-            # is the figure, the byte rate is listed only to show they are nowhere near HBM
-            st = {}
-            floors = shu_floors()
-            for name, kind in (('shu_rfft2', 'latency'), ('shu_spectral', 'mfma'), ('shu_irfft2', 'latency')):
-                d = tsum.get(name)
-                if not d or d['ms'] <= 0:
-                    continue
-                e = {'us_per_step': round(d['ms'] / psteps * 1e3, 1), 'launches_per_step': d['calls'] // psteps, 'bound': kind}
-                if kind == 'mfma':
-                    tf = d['work'] / (d['ms'] * 1e-3) / 1e12
-                    e.update(executed_tflops=round(tf, 2), frac_of_fp32_mfma_peak=round(tf / PEAK_FP32_MFMA_TFLOPS, 4))
-                else:
-                    e['algorithmic_GBps'] = round(d['work'] / (d['ms'] * 1e-3) / 1e9, 1)
-                if name in floors:
-                    pr, sk, em = floors[name]
-                    e.update(floor_us=sk, empty_launch_us=em, back_to_back_us=pr, frac_of_floor=round(sk / pr, 3))
-                st[name] = e
-            if not st:
-                return None
-            return {'ms_per_step': round(sum(v['us_per_step'] for v in st.values()) / 1e3, 4), 'stages': st,
-                    'floor_source': 'profiles/r06_shu_floor.txt' if floors else None,
-                    'floor_note': 'floor_us = a skeleton launch of the same grid / LDS / load-store footprint without arithmetic, back_to_back_us = the product '
-                                  'kernel in the same probe (no per-launch events), frac_of_floor = floor / product there; us_per_step is this run\'s '
-                                  'HIP-event time inside the generator (launch gaps included)' if floors else None}
-        shu = shu_block()
-        conv_ms = sum(tsum[k]['ms'] for k in tsum if k.startswith('conv_'))
-        conv_exec = sum(tsum[k]['executed'] for k in tsum if k.startswith('conv_'))
-        conv_alg = sum(tsum[k]['work'] for k in tsum if k.startswith('conv_'))
-        # the dominant kernel = the convolution class with the largest share of the step
-        DOM = {'conv_wino4': ('conv_wino4_kernel', 'Winograd F(4x4,3x3), 3x3 stride-1 layers: 36/144 of the direct-form flops'),
-               'conv_wino': ('conv_wino_kernel', 'Winograd F(2x2,3x3), 3x3 stride-1 layers: 16/36 of the direct-form flops')}
-        dom_name = max((k for k in conv if k in DOM), key=lambda k: conv[k]['ms_per_step'], default=None)
-        dom = conv.get(dom_name)
-        traffic, traffic_src = pmc_traffic(res, batch, DOM[dom_name][0]) if dom_name else (None, None)
-        roof = {'bound': 'mfma', 'kernel': f'{DOM[dom_name][0]} ({DOM[dom_name][1]}; the largest share of a step)' if dom_name else None,
-                'achieved': dom['executed_tflops'] if dom else None, 'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
-                'frac': dom['frac_of_fp32_mfma_peak'] if dom else None,
-                'definition': 'flops executed on the matrix cores (Winograd: the multiplies of the transformed products, not the direct-form '
-                              'count) / HIP-event time of the launches in the instrumented pass / dense fp32 MFMA peak (157.3 TFLOP/s at '
-                              '2.4 GHz; under this load the chip sustains about 2.1 GHz)',
-                'avg_launch_us': dom['avg_launch_us'] if dom else None,
-                'direct_form_tflops': dom['direct_form_tflops'] if dom else None,
-                'traffic': traffic, 'traffic_unit': 'GB per launch (HBM read+write, PMC FETCH_SIZE*2 + WRITE_SIZE)',
-                'traffic_source': f'constant of the committed profile {traffic_src}, not measured in this run' if traffic_src else None,
-                'traffic_classes': pmc_traffic_classes(res, batch),
-                'classes': conv,
-                'all_conv': {'ms_per_step': round(conv_ms / psteps, 3) if psteps else None,
-                             'executed_tflops': round(conv_exec / (conv_ms * 1e-3) / 1e12, 2) if conv_ms else None,
-                             'frac_of_fp32_mfma_peak': round(conv_exec / (conv_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4) if conv_ms else None,
-                             'direct_form_tflops': round(conv_alg / (conv_ms * 1e-3) / 1e12, 2) if conv_ms else None},
-                'whole_step': {'executed_gflop_per_step': round(conv_exec / psteps / 1e9, 1) if psteps else None,
-                               'executed_tflops_over_wall': round(conv_exec / psteps / (ms * 1e-3) / 1e12, 2) if psteps else None,
-                               'frac_of_fp32_mfma_peak': round(conv_exec / psteps / (ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4) if psteps else None,
-                               'direct_form_gflop_per_image': GFLOP_PER_IMAGE.get(res)}}
         line = {
             'metric': 'generator images/sec', 'value': round(ips, 3), 'unit': 'images/s', 'n_gpus': world,
             'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': round(ms, 3), 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'full': a.full,
             'config': {'workload': f'FFHQ-{res} generator forward + u8 composite, random-init, batch {batch} per GPU',
                        'resolution': res, 'batch_per_gpu': batch, 'global_batch': batch * world, 'noise_mode': a.noise_mode,
                        'parallelism': f'batch-shard x{world}', 'launcher': 'self-spawn' if spawned_world else
@@ -776,20 +795,16 @@ def worker(local_rank, a, spawned_world=None, port=None):
                          'note': 'the K timed steps are independent batches issued round-robin on `depth` HIP streams '
                                  '(eval_harness.StreamPipeline, the evaluation loop of the product): the launch-boundary gaps of '
                                  'one batch are filled by the kernels of the next; ms_per_step = wall time / K (throughput), '
-                                 'ms_per_step_single_stream = one batch alone (latency)'},
-            'timing': 'headline loop uninstrumented; roofline/hbm from a separate instrumented pass of '
-                      f'{psteps} steps (HIP events on the launch stream)',
-            'roofline': roof,
-            'hbm': {'bound': 'hbm', 'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'classes': hbm},
-            'shu': shu,
-            'eval_loop': evloop,
-            'second_config': second,
-            'fp16_blocks_eval': fp16_eval,
-            'train_step': train,
+                                 'ms_per_step_single_stream = one batch alone (latency; --full)'},
+            'timing': 'headline loop uninstrumented' + (f'; roofline/hbm from a separate instrumented pass of {psteps} steps (HIP events on '
+                                                        'the launch stream)' if a.full else ''),
         }
+        if a.full:
+            line.update(kernel_report(tsum, psteps, res, batch, ms))
+            line.update(eval_loop=evloop, second_config=second, fp16_blocks_eval=fp16_eval, train_step=train)
         if dumped is not None:
             line['dump_outputs'] = dumped
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             try:
                 line['cpu_baseline'] = cpu_baseline(res, batch, a.cpu_images or batch, a.cpu_forwards, a.noise_mode, seed=0)
                 if second is not None:
@@ -797,7 +812,7 @@ def worker(local_rank, a, spawned_world=None, port=None):
             except Exception as e:   # the baseline is informational; never lose the GPU number over it
                 line['cpu_baseline'] = {'value': None, 'unit': 'images/s', 'cores': os.cpu_count(), 'kind': 'port',
                                         'sample': f'failed: {e!r}'}
-        else:
+        elif a.full:
             line['cpu_baseline'] = None
         print(json.dumps(line), flush=True)
     if use_dist:

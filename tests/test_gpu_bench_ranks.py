@@ -68,13 +68,13 @@ def test_bench_two_ranks_share_one_device(tmp_path):
 def test_bench_four_ranks_oversubscribed_on_one_device(tmp_path):
     """The launch shape of a multi-GPU scaling run (``--gpus N``), oversubscribed on the one device of the test box (256^2, batch 2 per rank,
     gloo): four spawned ranks rendezvous, the all-reduced rank count is 4, rank r holds the ids r, r + 4 (ds_sampler.py:67), the HIP-graph
-    decision is common to all ranks, every rank reports its own step and host-enqueue time, and -- with ``--eval-loop`` -- the evaluation
+    decision is common to all ranks, every rank reports its own step and host-enqueue time, and -- with ``--full --eval-loop`` -- the evaluation
     loop's end-of-run collectives (all-gather of the uint8 results, all-reduce of the FID moments) span the four ranks.  Four ranks keep the
     processes with the device open (the ranks and this one) at five."""
     n = 4
     common = [c for c in COMMON if c != '--no-eval-loop']
     common[common.index('--batch') + 1] = '2'
-    line, dig, _ = _bench(tmp_path, 'four', n, common + ['--eval-loop'])
+    line, dig, _ = _bench(tmp_path, 'four', n, common + ['--full', '--eval-loop'])
     cfg = line['config']
     assert line['n_gpus'] == n and cfg['global_batch'] == 2 * n and cfg['launcher'] == 'self-spawn'
     assert cfg['ranks_all_reduced'] == n and cfg['ranks_share_devices'] and cfg['collective_backend'] == 'gloo'
@@ -89,12 +89,12 @@ def test_bench_four_ranks_oversubscribed_on_one_device(tmp_path):
 
 
 def test_bench_two_ranks_training_blocks(tmp_path):
-    """``--gpus 2 --all-blocks``: the config-5 blocks with an active gradient all-reduce (gloo here, two ranks on the one device).  Guards
+    """``--gpus 2 --full --all-blocks``: the config-5 blocks with an active gradient all-reduce (gloo here, two ranks on the one device).  Guards
     two things round 6 found on this very command: the instrumented iteration must run on EVERY rank (rank 0 alone stood in its all-reduce
     while rank 1 waited in the next barrier: the run hung until its timeout), and the HIP-graph form with more than one rank -- two graphs
     per phase around the host-side bucket all-reduce -- is captured, timed beside the eager loop and the faster one reported."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--all-blocks', '--train-steps', '1', '--steps', '2', '--warmup', '1',
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--full', '--all-blocks', '--train-steps', '1', '--steps', '2', '--warmup', '1',
                         '--no-cpu-baseline', '--no-second-config', '--no-eval-loop', '--profile-steps', '0', '--watchdog', '600'], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     assert p.returncode == 0, p.stdout.decode()[-3000:]

@@ -32,7 +32,7 @@ def test_bench_two_ranks_over_rccl():
     if WORLD == 1:                                # one device: bench.py joins a one-rank RCCL group as a torch.distributed.run rank
         env.update(RANK='0', LOCAL_RANK='0', WORLD_SIZE='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=_free_port())
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(WORLD), '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
-                        '--no-second-config', '--all-blocks', '--train-steps', '1'], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1200)
+                        '--no-second-config', '--full', '--all-blocks', '--train-steps', '1'], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1200)
     assert p.returncode == 0, p.stdout.decode()[-3000:]
     line = json.loads([ln for ln in p.stdout.decode().splitlines() if ln.startswith('{')][-1])
     assert line['n_gpus'] == WORLD and line['config']['collective_backend'] == 'nccl' and line['config']['ranks_all_reduced'] == WORLD

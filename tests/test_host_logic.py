@@ -326,3 +326,18 @@ def test_bench_reads_its_committed_profiles():
     assert gb and gb > 0.5 and src == os.path.join('profiles', 'traffic_512x16.json')
     cls = bench.pmc_traffic_classes(512, 16)
     assert 'conv_wino4_kernel' in cls and cls['conv_wino4_kernel']['read_GB_per_launch'] > 0
+
+
+def test_bench_full_option():
+    """A plain bench run measures the headline alone; the other blocks run with ``--full``, which the options that ask for some of those
+    blocks on N > 1 imply (they would otherwise be ignored without a word)."""
+    import importlib.util
+    import os
+    from conftest import ROOT
+    spec = importlib.util.spec_from_file_location('shg_bench_for_test', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.parse(['--steps', '2']).full is False
+    assert bench.parse(['--full', '--eval-loop', '--all-blocks']).full is True
+    for opt in ('--eval-loop', '--all-blocks'):
+        assert bench.parse(['--gpus', '2', opt]).full is True

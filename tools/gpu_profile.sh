@@ -1,12 +1,12 @@
 #!/bin/bash
-# rocprofv3 kernel-trace + stats of the default bench; summaries land in gpurun_out/prof_<tag>/
+# rocprofv3 kernel-trace + stats of the bench with all its blocks (--full); the summaries land in $OUT (prof_<tag>/)
 TAG=${1:-r01}
 mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o bench -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline ${BENCH_ARGS} > $OUT/bench_stdout.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o bench -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline ${BENCH_ARGS} > $OUT/bench_stdout.log 2>&1
 echo "rocprof exit $?" >> $OUT/bench_stdout.log
 find $OUT -name "*stats*" | head
 F=$(find $OUT -name "*kernel_stats.csv" | head -1)
