@@ -306,6 +306,35 @@ int shg_mask_raster_box_f32(const int* records, const int* offsets, const int* f
  * feats [B,D] float32 (float64 when is_f64), weights [B] or NULL, DP >= D+1 a multiple of 32. */
 int shg_fid_accumulate_f64(const void* feats, int is_f64, const float* weights, double* S, int B, int D, int DP, void* stream);
 
+/* ---- FID detector: the feature extractor of Inception-v3 `inception-2015-12-05` (eva_fid.py:30,145-158), float32 NCHW
+ * (sh-gan_amd/inception.py drives it; csrc/inception.hip).
+ * shg_inception_frontend_f32: x [B,3,H,W] -> y [B,3,299,299] = (resize(v) - 128) / 128, v = lut[x] when lut [256] is given (x uint8),
+ *   else x*scale + bias (x float32, two roundings); resize = TF1 legacy bilinear, source = i * size / 299, no half-pixel offset, border
+ *   clamp; none when H = W = 299.
+ * shg_inception_weight_prep_f32: BN-folded w [O,I,kh,kw], bias [O] -> wp [Kp][Np] (shg_inception_packed_weight_elems floats, Kp = I*kh*kw
+ *   rounded up to 16, Np = O rounded up to 64, k = (ky*kw + kx)*I + c, zero outside), bp [Np]; once per detector.
+ * shg_inception_conv_f32: G <= SHG_INC_MAX_GROUPS independent convolutions in one launch, each y[:, y_coff:y_coff+O] =
+ *   relu(conv2d(x[:, x_coff:x_coff+I], w, stride (sh,sw), pad (ph,pw)) + bias) on exact-fp32 MFMA; x [B][x_ctot][H][W],
+ *   y [B][y_ctot][OH][OW], kernel <= 7 x 7, stride 1 or 2, pad < kernel, w 16-byte aligned.  splitk > 1 splits K over that many
+ *   workgroups, partial sums in `workspace` (shg_inception_conv_workspace_bytes; 0 when no group splits) added in split order.
+ * shg_inception_pool_f32: 3 x 3 pool of x [B,C,H,W] into y[:, y_coff:y_coff+C] of [B,y_ctot,OH,OW]; mode 0 max, 1 average over the
+ *   in-bounds taps (count_include_pad=False); stride 1 or 2, pad 0 or 1.
+ * shg_inception_mean_f32: y [B,C] = mean of x [B,C,HW] over HW (fixed summation order: independent of B). */
+#define SHG_INC_MAX_GROUPS 8
+typedef struct {
+    const float* x; const float* w; const float* bias; float* y;
+    int I, H, W, x_ctot, x_coff;
+    int O, kh, kw, sh, sw, ph, pw, OH, OW, y_ctot, y_coff;
+    int splitk;
+} shg_inc_conv_desc;
+int shg_inception_frontend_f32(const void* x, const float* lut, float scale, float bias, float* y, int B, int H, int W, void* stream);
+long shg_inception_packed_weight_elems(int O, int I, int kh, int kw);
+int shg_inception_weight_prep_f32(const float* w, const float* bias, float* wp, float* bp, int O, int I, int kh, int kw, void* stream);
+size_t shg_inception_conv_workspace_bytes(const shg_inc_conv_desc* groups, int G, int B);
+int shg_inception_conv_f32(const shg_inc_conv_desc* groups, int G, int B, void* workspace, size_t ws_bytes, void* stream);
+int shg_inception_pool_f32(const float* x, float* y, int B, int C, int H, int W, int mode, int stride, int pad, int y_ctot, int y_coff, void* stream);
+int shg_inception_mean_f32(const float* x, float* y, int B, int C, int HW, void* stream);
+
 /* ---- evaluation image metrics (lib/evaluator/eva_psnr.py, for_dataset=None, rgb_range=1; eva_ssim._ssim, size_average=False).
  * pred, gt [B,C,H,W] contiguous; each operand is uint8 when its lut [256] (value of every code: float64 for pred, float32 for gt) is
  * given, float32 otherwise; the element value is then v*scale + bias (the evaluator's fake/255 and (real+1)/2).  As in the reference's

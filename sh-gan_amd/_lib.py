@@ -10,7 +10,7 @@ import torch  # noqa: F401  (must be imported first: the .so binds to torch's al
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'libshgan_hip.so')
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 c_fp = ctypes.c_void_p      # device pointers travel as void*
 c_i = ctypes.c_int
@@ -29,6 +29,11 @@ class DenseGroup(ctypes.Structure):          # shg_dense_group
 class StyleGroup(ctypes.Structure):          # shg_style_group
     _fields_ = [('styles', c_fp), ('wsq', c_fp), ('s_out', c_fp), ('dcoef', c_fp),
                 ('ld', c_i), ('I', c_i), ('O', c_i), ('OP', c_i), ('demod', c_i), ('pre_gain', c_f)]
+
+
+class IncConv(ctypes.Structure):             # shg_inc_conv_desc
+    _fields_ = [('x', c_fp), ('w', c_fp), ('bias', c_fp), ('y', c_fp)] + [
+        (n, c_i) for n in ('I', 'H', 'W', 'x_ctot', 'x_coff', 'O', 'kh', 'kw', 'sh', 'sw', 'ph', 'pw', 'OH', 'OW', 'y_ctot', 'y_coff', 'splitk')]
 
 
 # name -> argtypes (restype is int unless noted); mirrors include/shgan_hip.h one to one
@@ -108,6 +113,13 @@ _SIGS = {
     'shg_mask_raster_f32': [c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i, c_fp],
     'shg_mask_raster_box_f32': [c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_fp, c_i, c_i, c_fp],
     'shg_fid_accumulate_f64': [c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_fp],
+    'shg_inception_frontend_f32': [c_fp, c_fp, c_f, c_f, c_fp, c_i, c_i, c_i, c_fp],
+    'shg_inception_packed_weight_elems': [c_i] * 4,
+    'shg_inception_weight_prep_f32': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
+    'shg_inception_conv_workspace_bytes': [ctypes.POINTER(IncConv), c_i, c_i],
+    'shg_inception_conv_f32': [ctypes.POINTER(IncConv), c_i, c_i, c_fp, ctypes.c_size_t, c_fp],
+    'shg_inception_pool_f32': [c_fp, c_fp] + [c_i] * 9 + [c_fp],
+    'shg_inception_mean_f32': [c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_image_metrics_scratch_bytes': [c_i] * 4,
     'shg_image_metrics': [c_fp, c_fp, c_f, c_f, c_fp, c_fp, c_f, c_f] + [c_i] * 6 + [c_fp, ctypes.c_size_t, c_fp, c_fp, c_fp],
     'shg_resize_bicubic_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
@@ -171,6 +183,8 @@ def get_lib():
     lib.shg_conv2d_wgrad_wino_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_conv2d_wgrad_f16_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_image_metrics_scratch_bytes.restype = ctypes.c_size_t
+    lib.shg_inception_conv_workspace_bytes.restype = ctypes.c_size_t
+    lib.shg_inception_packed_weight_elems.restype = c_l
     lib.shg_conv2d_f16_packed_weight_elems.restype = c_l
     lib.shg_conv_wino4_weight_elems.restype = c_l
     ver = lib.shg_abi_version()

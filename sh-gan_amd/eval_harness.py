@@ -366,11 +366,16 @@ class EvalLoop:
     evaluator batch of shgan_default.py:279-291): per batch, on the batch's own stream, one HIP launch pair (image_metrics.py) writes the
     per-image values of the composite against ``real`` into a per-rank float64 buffer at the batch's position; ``gather`` all-gathers
     those buffers once, re-interleaves them to dataset order and sets ``image_metrics`` -- independent of ``keep_images``.
-    ``metrics_fn(pred, gt, window_size, psnr_out, ssim_out)`` replaces the kernel (CPU tests)."""
+    ``metrics_fn(pred, gt, window_size, psnr_out, ssim_out)`` replaces the kernel (CPU tests).
+
+    ``fid_real=True`` adds the real side of the FID (eva_fid.py's ``compute_fid`` without its cache file): per batch, on the batch's own
+    stream, ``feature_fn(real, input_range='pm1')`` (the detector maps [-1, 1] floats, or a loader's decoded uint8 pixels, as the
+    reference's ``real*127.5 + 127.5``) into per-stream partial moments, padded duplicates weighing 0; ``gather`` all-reduces both sides
+    once each (``self.fid`` fake, ``self.fid_real`` real) and ``fid_value()`` gives the FID."""
 
     def __init__(self, G, device, resolution, n_items, rank=0, world=1, noise_mode='random', seed=0, depth=None, feature_fn=None,
                  fid_dim=2048, latent_fn=None, device_masks=True, hole_range=(0, 1), keep_images=True, on_batch=None, step_fn=None,
-                 fid_accumulate_fn=None, feeder_stream=False, timing=False, metrics=None, ssim_window=11, metrics_fn=None):
+                 fid_accumulate_fn=None, feeder_stream=False, timing=False, metrics=None, ssim_window=11, metrics_fn=None, fid_real=False):
         from .datasets import DeviceFeeder
         self.timing, self.batch_done_events = timing, []      # timing: one timing event per finished batch (bench: steady-state rate)
         self.G, self.device, self.res = G, torch.device(device), int(resolution)
@@ -383,6 +388,11 @@ class EvalLoop:
         self.fid_dim, self._fid_fn = fid_dim, fid_accumulate_fn
         self._fid_parts = {}            # stream id -> FidStats (partial sums of the batches that ran on that stream)
         self.fid = None                 # their sum, after gather()
+        if fid_real and feature_fn is None:
+            raise ValueError('EvalLoop: fid_real needs a feature_fn (the detector)')
+        self.fid_real_on = bool(fid_real)
+        self._fid_real_parts = {}       # the same for the real images (fid_real)
+        self.fid_real = None
         self.images = (torch.empty((len(self.ids), 3, self.res, self.res), dtype=torch.uint8, device=self.device) if keep_images else None)
         self.seen = 0
         self.metrics = None             # image_metrics.MetricsAccumulator of this rank's shard
@@ -392,11 +402,12 @@ class EvalLoop:
             self.metrics = MetricsAccumulator(len(self.ids), self.device, metrics=tuple(metrics), window_size=ssim_window,
                                               metrics_fn=metrics_fn)
 
-    def _fid_part(self, key):
+    def _fid_part(self, key, real=False):
         from .fid_stats import FidStats
-        if key not in self._fid_parts:
-            self._fid_parts[key] = FidStats(self.fid_dim, device=self.device, accumulate_fn=self._fid_fn)
-        return self._fid_parts[key]
+        parts = self._fid_real_parts if real else self._fid_parts
+        if key not in parts:
+            parts[key] = FidStats(self.fid_dim, device=self.device, accumulate_fn=self._fid_fn)
+        return parts[key]
 
     def run(self, loader):
         """``loader`` yields this rank's items in ``shard_ids`` order as (images [B,3,R,R] uint8 or float32 in [-1,1], ids) or
@@ -408,6 +419,8 @@ class EvalLoop:
         if self.feature_fn is not None:                                    # accumulators exist before a side stream touches them
             for key in [None] + [st.cuda_stream for st in pipe.streams]:
                 self._fid_part(key)
+                if self.fid_real_on:
+                    self._fid_part(key, real=True)
         for x4, real, mask, ids in self.feeder(loader):
             b, k0 = x4.shape[0], self.seen
             if k0 + b > len(self.ids):
@@ -422,10 +435,13 @@ class EvalLoop:
                     cur = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == 'cuda' else None
                     part = self._fid_parts.get(cur) or self._fid_part(None)
                     part.add_shard(self.feature_fn(out), k0, self.rank, self.world, self.n_items)
-                if real_ is not None:
+                    if self.fid_real_on:
+                        part = self._fid_real_parts.get(cur) or self._fid_part(None, real=True)
+                        part.add_shard(self.feature_fn(real_, input_range='pm1'), k0, self.rank, self.world, self.n_items)
+                if real_ is not None and self.metrics is not None:
                     self.metrics.add(out, real_, k0)
                 return out
-            out = pipe.run(step, x4, z, real) if self.metrics is not None else pipe.run(step, x4, z)
+            out = pipe.run(step, x4, z, real) if (self.metrics is not None or self.fid_real_on) else pipe.run(step, x4, z)
             if self.timing and self.device.type == 'cuda':
                 tev = torch.cuda.Event(enable_timing=True)
                 tev.record(pipe.last_stream or torch.cuda.current_stream(self.device))
@@ -463,6 +479,8 @@ class EvalLoop:
             images = zipzap_device(full, self.n_items)
         if self.local_fid() is not None:
             self.fid.all_reduce()
+        if self.fid_real_on and self.local_fid_real() is not None:
+            self.fid_real.all_reduce()
         if self.metrics is not None:
             self.image_metrics = self._gather_metrics(use)
         return images, self.fid
@@ -491,6 +509,26 @@ class EvalLoop:
                 base.S += p.S
             self.fid, self._fid_parts = base, {}
         return self.fid
+
+    def local_fid_real(self):
+        """The same for the real side (``fid_real``)."""
+        if self._fid_real_parts:
+            parts = list(self._fid_real_parts.values())
+            base = self.fid_real if self.fid_real is not None else parts.pop(0)
+            for p in parts:
+                base.S += p.S
+            self.fid_real, self._fid_real_parts = base, {}
+        return self.fid_real
+
+    def fid_value(self):
+        """The FID of the gathered moments (after ``gather``; ``fid_real=True``): ``fid_from_stats`` on the fake and real sides'
+        ``mean_cov`` -- the reference's ``compute_fid`` (eva_fid.py:243-263) without the cache file of real statistics."""
+        from .fid_stats import fid_from_stats
+        if not self.fid_real_on or self.fid is None or self.fid_real is None:
+            raise ValueError('EvalLoop.fid_value: needs fid_real=True, a feature_fn and a finished gather()')
+        _, mu_f, sg_f = self.fid.mean_cov()
+        _, mu_r, sg_r = self.fid_real.mean_cov()
+        return fid_from_stats(mu_f, sg_f, mu_r, sg_r)
 
 
 class PinnedU8Loader:

@@ -14,8 +14,8 @@ MI355X-first form:
   * ``gather_features``: the reference's own semantics when the features themselves are wanted in dataset order --
     one ``all_gather_into_tensor`` + the zipzap re-interleave instead of 3 x world broadcasts;
   * ``fid_from_stats``: the host tail (``scipy.linalg.sqrtm``), as eva_fid.py:259-261.
-The Inception-v3 feature detector itself is a TorchScript download (eva_fid.py:30,145-158) and cannot be pinned offline:
-everything from the [B,2048] features onwards is implemented and tested here."""
+The reference's Inception-v3 feature detector is a TorchScript download (eva_fid.py:30,145-158); the same network runs on
+HIP kernels in inception.py, with weights loaded from a torchvision-layout state_dict."""
 import numpy as np
 import torch
 
