@@ -149,12 +149,6 @@ _SIGS = {
 _lib = None
 
 
-def use_library(path):
-    """Point the loader at another build of the same ABI (tools/ use the -DSHG_ABLATE timing-study library)."""
-    global _lib, LIB_PATH
-    _lib, LIB_PATH = None, path
-
-
 class ShgError(RuntimeError):
     """Raised when a C-ABI call returns a negative status (mirrors TORCH_CHECK -> RuntimeError)."""
 

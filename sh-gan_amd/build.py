@@ -11,8 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
-LIBNAME = 'libshgan_hip.so'
-VARDIR = os.path.join(os.path.dirname(HERE), 'tools', '_variants')      # study builds (-DSHG_ABLATE, A/B knobs) live with the tools, never beside the product library
+LIB = os.path.join(LIBDIR, 'libshgan_hip.so')
 SOURCES = ['capi.hip', 'upfirdn2d.hip', 'pointwise.hip', 'dense.hip', 'conv_mfma.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_wino_poly.hip', 'conv_wgrad.hip', 'conv_wgrad_wino.hip', 'conv_f16.hip', 'conv_f16_ring.hip', 'conv_f16_upring.hip', 'conv_f16_down.hip', 'shu.hip', 'mask_raster.hip', 'fid_stats.hip', 'image_metrics.hip', 'resize.hip', 'inception.hip']
 # per-source extras: the Winograd weight-gradient transforms are scalar fp32 chains beside MFMAs -- SLP-packed (v_pk_*) forms cost register
 # moves and issue slots there
@@ -30,7 +29,7 @@ def _hipcc():
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 
 
-def _digest(extra=()):
+def _digest():
     """sha256 over every kernel source, the public C header (an ABI struct edit must trigger a rebuild) and the flags."""
     h = hashlib.sha256()
     for d in (CSRC, INCLUDE):
@@ -38,39 +37,25 @@ def _digest(extra=()):
             with open(os.path.join(d, name), 'rb') as fh:
                 h.update(name.encode())
                 h.update(fh.read())
-    h.update(' '.join(list(FLAGS) + [f'{k}:{v}' for k, v in sorted(SRC_FLAGS.items())] + list(extra)).encode())
+    h.update(' '.join(list(FLAGS) + [f'{k}:{v}' for k, v in sorted(SRC_FLAGS.items())]).encode())
     return h.hexdigest()
 
 
-def lib_path(ablate=False, variant=None):
-    if variant:
-        return os.path.join(VARDIR, f'libshgan_hip_{variant}.so')
-    return os.path.join(VARDIR, 'libshgan_hip_ablate.so') if ablate else os.path.join(LIBDIR, LIBNAME)
-
-
-def build(force=False, verbose=True, ablate=False, variant=None, defines=()):
-    """``ablate=True`` builds the timing-study variant (-DSHG_ABLATE: the SHG_*_DBG / SHG_CONV_VARIANT environment switches
-    that make kernels skip work) as a SEPARATE library for tools/; the product library has no such switches.
-    ``variant='name', defines=['-DX=1']`` builds libshgan_hip_<name>.so with extra compile-time knobs for A/B runs in tools/."""
+def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
-    outdir = VARDIR if (ablate or variant) else LIBDIR
-    os.makedirs(outdir, exist_ok=True)
-    extra = (['-DSHG_ABLATE'] if ablate else []) + list(defines)
-    if variant:
-        ablate = True            # (shares the .abl.o object names / separate stamp below)
-    stamp = os.path.join(outdir, f'.build_digest_{variant}' if variant else ('.build_digest_ablate' if ablate else '.build_digest'))
-    dig = _digest(extra)
-    if not force and os.path.exists(lib_path(ablate, variant)) and os.path.exists(stamp) and open(stamp).read().strip() == dig:
+    stamp = os.path.join(LIBDIR, '.build_digest')
+    dig = _digest()
+    if not force and os.path.exists(LIB) and os.path.exists(stamp) and open(stamp).read().strip() == dig:
         if verbose:
-            print(f'[build] {os.path.basename(lib_path(ablate, variant))} up to date')
-        return lib_path(ablate, variant)
+            print(f'[build] {os.path.basename(LIB)} up to date')
+        return LIB
     hipcc = _hipcc()
     objs = []
     procs = []
     for src in SOURCES:
-        obj = os.path.join(outdir, src.replace('.hip', (f'.{variant}.o' if variant else '.abl.o') if ablate else '.o'))
+        obj = os.path.join(LIBDIR, src.replace('.hip', '.o'))
         objs.append(obj)
-        cmd = [hipcc] + FLAGS + SRC_FLAGS.get(src, []) + extra + ['-c', os.path.join(CSRC, src), '-o', obj]
+        cmd = [hipcc] + FLAGS + SRC_FLAGS.get(src, []) + ['-c', os.path.join(CSRC, src), '-o', obj]
         if verbose:
             print('[build]', ' '.join(cmd))
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
@@ -81,7 +66,7 @@ def build(force=False, verbose=True, ablate=False, variant=None, defines=()):
             raise RuntimeError(f'hipcc failed on {src}')
         if verbose and out.strip():
             print(out.decode(errors='replace'))
-    cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', lib_path(ablate, variant)] + objs
+    cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB] + objs
     if verbose:
         print('[build]', ' '.join(cmd))
     subprocess.check_call(cmd)
@@ -89,10 +74,8 @@ def build(force=False, verbose=True, ablate=False, variant=None, defines=()):
         os.remove(obj)
     with open(stamp, 'w') as fh:
         fh.write(dig)
-    return lib_path(ablate, variant)
+    return LIB
 
 
 if __name__ == '__main__':
-    var = [a.split('=', 1)[1] for a in sys.argv if a.startswith('--variant=')]
-    build(force='--force' in sys.argv, ablate='--ablate' in sys.argv, variant=var[0] if var else None,
-          defines=[a for a in sys.argv[1:] if a.startswith('-D')])
+    build(force='--force' in sys.argv)

@@ -29,28 +29,6 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef float f16x __attribute__((ext_vector_type(16)));
 
-#ifndef SHG_F16_ADEPTH
-#define SHG_F16_ADEPTH 1
-#endif
-#ifndef SHG_F16_EG
-#define SHG_F16_EG 4
-#endif
-#ifndef SHG_F16_ABL
-#define SHG_F16_ABL 0   // timing-study builds only (tools/_variants, tools/f16_abl.sh): 1 no B reads, 2 no A loads, 4 no staging, 8 no epilogue, 16 no loop barriers
-#endif
-
-#ifdef SHG_F16_TRACE
-// timeline study (python sh-gan_amd/build.py --variant=f16trace -DSHG_F16_TRACE=1, tools/f16_trace.py): every 61st workgroup of channel group 0
-// records clock64() of wave 0 at: entry | first chunk in LDS | first chunk multiplied | all chunks multiplied | stores issued | stores drained
-__device__ long long shg_f16_trace_buf[256 * 8];
-extern "C" int shg_f16_trace_read(long long* host) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(shg_f16_trace_buf), sizeof(shg_f16_trace_buf));
-}
-#define F16_TRACE(slot) do { if (blockIdx.y == 0 && blockIdx.x % 61 == 0 && blockIdx.x / 61 < 256 && threadIdx.x == 0) shg_f16_trace_buf[(blockIdx.x / 61) * 8 + (slot)] = clock64(); } while (0)
-#else
-#define F16_TRACE(slot) do { } while (0)
-#endif
-
 namespace f16 {
 
 constexpr int TH = 8, TW = 16;       // output-pixel tile of a workgroup (4 waves x 2 rows x 16 columns)
@@ -134,12 +112,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MB == 2 &&
             }
         }
     };
-    F16_TRACE(0);
     fetch(0);
     fetch_w(0);
     for (int c0 = 0; c0 < p.I; c0 += KC) {
-        if (!(SHG_F16_ABL & 16)) __syncthreads();
-        if (!(SHG_F16_ABL & 4) || c0 == 0)
+        __syncthreads();
 #pragma unroll
         for (int it = 0; it < SIT; ++it) {
             const int pp = (tid >> 2) + it * 64;
@@ -152,13 +128,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MB == 2 &&
                 if (pi < WPC) *(h8*)(wlds + pi * 512 + lane * 8) = wstage[it];
             }
         }
-        if (!(SHG_F16_ABL & 16)) __syncthreads();
-        if (c0 == 0) F16_TRACE(1);
-        if (c0 + KC < p.I && !(SHG_F16_ABL & 4)) { fetch(c0 + KC); fetch_w(c0 + KC); }
+        __syncthreads();
+        if (c0 + KC < p.I) { fetch(c0 + KC); fetch_w(c0 + KC); }
         // Weight operands: unconditional loads (the packed tensor is zero-padded to whole MB groups of blocks and I % 32 == 0), those of
         // tap t+1 requested before the MFMAs of tap t -- a conditional load would be waited for on the spot (vmcnt(0) per MFMA pair).
         const _Float16* wc = wl + ((long)ob0 * p.wslots * c16n + (c0 >> 4)) * 512;
-        constexpr int AD = SHG_F16_ADEPTH;                          // operand prefetch distance in taps (ring of AD + 1 slots)
+        constexpr int AD = 1;                                       // operand prefetch distance in taps (ring of AD + 1 slots)
         h8 a[AD + 1][2][MB];
         if constexpr (!WLDS) {
 #pragma unroll
@@ -175,7 +150,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MB == 2 &&
                 for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                     for (int m = 0; m < MB; ++m) a[t % (AD + 1)][ks][m] = *(const h8*)(wlds + ((m * NT + t) * 2 + ks) * 512 + lane * 8);
-            } else if (t + AD < NT && !((SHG_F16_ABL & 2) && c0)) {
+            } else if (t + AD < NT) {
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -188,7 +163,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MB == 2 &&
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-                for (int q = 0; q < NB; ++q) b[ks][q] = (SHG_F16_ABL & 1) ? a[0][ks][0] : *(const h8*)(bp + q * p.s_in * p.PW * PSTR + ks * 16);
+                for (int q = 0; q < NB; ++q) b[ks][q] = *(const h8*)(bp + q * p.s_in * p.PW * PSTR + ks * 16);
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -196,23 +171,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MB == 2 &&
 #pragma unroll
                     for (int q = 0; q < NB; ++q) acc[m][q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[t % (AD + 1)][ks][m], b[ks][q], acc[m][q], 0, 0, 0);
         }
-        if (c0 == 0) F16_TRACE(2);
     }
-    F16_TRACE(3);
     // C/D layout: column (pixel) = lane & 31, row (channel) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  A lane holds 4-channel runs of ONE
     // pixel: stored directly, every store instruction would touch 64 different 128-byte lines with 8 bytes each.  The tile is therefore
     // transposed through LDS (pixel-major, 16 bytes of padding per pixel) and leaves as whole 16-byte pieces of contiguous channel runs.
     constexpr int OPS = MB * 32 + 8;
-    if (SHG_F16_ABL & 8) {
-        float sacc = 0.f;
-#pragma unroll
-        for (int m = 0; m < MB; ++m)
-#pragma unroll
-            for (int q = 0; q < NB; ++q)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sacc += acc[m][q][r];
-        if (sacc != 1234.5f) return;
-    }
     float bv[MB][4][4];                                             // bias of a lane's channels (no-tail launches), requested before the barrier
     const bool pre_bias = p.bias && !p.tail;
 #pragma unroll
@@ -225,7 +188,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MB == 2 &&
                 bv[m][qq][e] = pre_bias ? p.bias[o < p.O ? o : p.O - 1] : 0.f;
             }
     __syncthreads();
-    F16_TRACE(6);
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
         const int pl = NB == 1 ? ry * TW + rx : (ry + q) * TWK + rx;
@@ -241,12 +203,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MB == 2 &&
             }
     }
     __syncthreads();
-    F16_TRACE(7);
     constexpr int PCS = MB * 4;                                   // 16-byte pieces per pixel
     if ((p.O & 7) == 0) {
         // whole 8-channel pieces: all LDS reads first, every operand load unconditional (clamped address), only the store predicated -- a
-        // rolled loop with early exits spent 550 cycles per piece (tools/f16_trace.py: LDS latency + address arithmetic in series)
-        constexpr int EIT = TH * TWK * PCS / 256, EG = EIT < SHG_F16_EG ? EIT : SHG_F16_EG;    // pieces per thread, in groups of EG (registers)
+        // rolled loop with early exits spent 550 cycles per piece (clock trace: LDS latency + address arithmetic in series)
+        constexpr int EIT = TH * TWK * PCS / 256, EG = EIT < 4 ? EIT : 4;    // pieces per thread, in groups of EG (registers)
         for (int i0 = 0; i0 < EIT; i0 += EG) {
         h8 vv[EG];
 #pragma unroll
@@ -328,11 +289,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MB == 2 &&
             for (int k = 0; k < 8; ++k)
                 if (o + k < p.O) yp[k] = v[k];
     }
-#ifdef SHG_F16_TRACE
-    F16_TRACE(4);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    F16_TRACE(5);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -646,8 +602,10 @@ __global__ __launch_bounds__(256) void updn4_f16_kernel(const UfdH p) {
     }
 }
 
-template <int FS, int RB>  // FS = 4: the 4x4 filter, fully unrolled with unconditional (clamped) loads; FS = 0: any size, guarded loop; RB output rows per lane
+// Same-size FIR of any filter size (up to 64 taps), guarded loop; the 4x4 filter of the model takes fir4_march_f16_kernel below.
+constexpr int FIR_SAME_RB = 2;                               // output rows per lane
 __global__ __launch_bounds__(256) void fir_same_f16_kernel(const UfdH p) {
+    constexpr int RB = FIR_SAME_RB;
     __shared__ float sf[64];
     for (int k = threadIdx.x; k < p.fh * p.fw; k += 256) {
         const int ky = k / p.fw, kx = k - ky * p.fw;
@@ -671,46 +629,6 @@ __global__ __launch_bounds__(256) void fir_same_f16_kernel(const UfdH p) {
             for (int a = 0; a < 4; ++a)
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[b][a][q] = 0.f;
-        if constexpr (FS == 4) {
-            // every load is issued (addresses clamped, out-of-range vectors zeroed afterwards): 35 independent loads in flight per lane
-            // instead of one guarded load at a time -- the guarded loop was 72 % parked on memory at 2.0 TB/s
-            h8 xin[3 + RB][7];
-#pragma unroll
-            for (int ry = 0; ry < 3 + RB; ++ry) {
-                const int iy = oy0 + ry - p.py0, iyc = iy < 0 ? 0 : (iy >= p.H ? p.H - 1 : iy);
-                const _Float16* row = p.x + ((long)n * p.H + iyc) * p.W * p.C + c8 * 8;
-#pragma unroll
-                for (int cx = 0; cx < 7; ++cx) {
-                    const int ix = ox0 + cx - p.px0, ixc = ix < 0 ? 0 : (ix >= p.W ? p.W - 1 : ix);
-                    xin[ry][cx] = *(const h8*)(row + (long)ixc * p.C);
-                }
-            }
-#pragma unroll
-            for (int ry = 0; ry < 3 + RB; ++ry) {
-                const int iy = oy0 + ry - p.py0;
-#pragma unroll
-                for (int cx = 0; cx < 7; ++cx) {
-                    const int ix = ox0 + cx - p.px0;
-                    const float m = (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) ? 1.f : 0.f;
-                    float xf[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) xf[q] = (float)xin[ry][cx][q] * m;
-#pragma unroll
-                    for (int b = 0; b < RB; ++b) {
-                        const int ky = ry - b;
-                        if (ky < 0 || ky >= 4) continue;
-#pragma unroll
-                        for (int a = 0; a < 4; ++a) {
-                            const int kx = cx - a;
-                            if (kx < 0 || kx >= 4) continue;
-                            const float fk = sf[ky * 4 + kx];
-#pragma unroll
-                            for (int q = 0; q < 8; ++q) v[b][a][q] += xf[q] * fk;
-                        }
-                    }
-                }
-            }
-        } else
         for (int ry = 0; ry < p.fh + RB - 1; ++ry) {                  // input row oy0 + ry - py0 feeds output row b with tap ky = ry - b
             const int iy = oy0 + ry - p.py0;
             if (iy < 0 || iy >= p.H) continue;
@@ -758,7 +676,8 @@ __global__ __launch_bounds__(256) void fir_same_f16_kernel(const UfdH p) {
 // compiler emits packed fp32 math.  The 4x4 filter of the model is an outer product (upfirdn2d.setup_filter of [1,3,3,1]); every thread factors the
 // taps itself (pivot row / column) and a filter that is NOT rank one takes the plain 16-tap loop below, same launch.  Column masks are folded into the
 // horizontal coefficients once per lane, out-of-range rows are loaded from a clamped address and multiplied by zero.  The 2 x 4-output
-// lanes of fir_same_f16_kernel spent 206 VALU operations per output piece (105 us of pure issue at 64 ch x 513^2 x 8) and ran at 2.3 TB/s.
+// lanes of the unrolled 4x4 form that preceded it spent 206 VALU operations per output piece (105 us of pure issue at 64 ch x 513^2 x 8) and ran
+// at 2.3 TB/s.
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef _Float16 hh2 __attribute__((ext_vector_type(2)));
 
@@ -879,10 +798,7 @@ __global__ __launch_bounds__(256) void fir4_march_f16_kernel(const UfdH p, int r
 // the whole grid-stride loop) -- eight scalar operand loads and a 64-bit modulo per 16-byte piece ran at 2.0-3.1 TB/s of read + write traffic, this
 // form at 5.4-6.3 (tools/conv_f16_bench.py).  EU > 1 requests several pieces before the first use: no gain (4.8 TB/s at 4), the pass is not
 // short of loads in flight.
-#ifndef SHG_F16_EU
-#define SHG_F16_EU 1
-#endif
-constexpr int EU = SHG_F16_EU;
+constexpr int EU = 1;
 
 __device__ __forceinline__ void load8f(const float* p, float (&v)[8]) {
     const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
@@ -1321,9 +1237,6 @@ extern "C" int shg_conv2d_f16_needs_clear(int H, int W, int crop, int OH, int OW
 // stride 1, 372 / 449 / 381 at stride 2 -- whose 260-register build held ONE workgroup per CU (346 TFLOP/s) until amdgpu_waves_per_eu(2) brought it to
 // 255 without spills; the load-bound 1x1 layers at 1024: 126 / 211 / 237 / 253 at 512 channels)
 static long wgrad_f16_slices(long tiles, long nblocks, long wgs) {
-#ifdef SHG_ABLATE
-    if (const char* e = getenv("SHG_WGRAD16_WGS")) wgs = atol(e);       // study switch (python sh-gan_amd/build.py --ablate: tools/_variants)
-#endif
     long slices = (wgs + tiles - 1) / tiles;
     if (slices > nblocks) slices = nblocks;
     return slices < 1 ? 1 : slices;
@@ -1388,24 +1301,18 @@ extern "C" int shg_upfirdn2d_f16(const void* x, const float* f, void* y, int N, 
     SHG_CHECK_ARG(OW >= 1 && OH >= 1, "upfirdn2d_f16: empty output");
     f16::UfdH p{(const _Float16*)x, f, (_Float16*)y, N, C, H, W, OH, OW, fh, fw, upx, upy, downx, downy, padx0, pady0, flip, gain};
     const bool same = upx == 1 && upy == 1 && downx == 1 && downy == 1;
-    const int rb = 2;                                        // (one row per lane was measured too: 287 vs 221 us at 64 ch x 513^2)
+    const int rb = f16::FIR_SAME_RB;                         // (one row per lane was measured too: 287 vs 221 us at 64 ch x 513^2)
     const long total = same ? (long)N * ((OH + rb - 1) / rb) * ((OW + 3) / 4) * (C / 8) : (long)N * OH * OW * (C / 8);
     int grid = shg_cdiv(total, 256);
     if (grid > 256 * 32) grid = 256 * 32;
-#ifdef SHG_ABLATE
-    const bool march = !getenv("SHG_F16_FIR_OLD");                     // study switch: the 2 x 4-pixel kernel instead
-#else
-    const bool march = true;
-#endif
-    if (same && fh == 4 && fw == 4 && march) {
+    if (same && fh == 4 && fw == 4) {
         // marching strips: the longest of 32 / 16 / 8 / 4 rows that still leaves >= 8 workgroups per CU
         int rows = 32;
         auto lanes = [&](int r) { return (long)N * ((OH + r - 1) / r) * ((OW + 1) / 2) * (C / 8); };
         while (rows > 4 && lanes(rows) < 256L * 256 * 8) rows /= 2;
         SHG_CHECK_ARG(lanes(rows) < (1L << 31), "upfirdn2d_f16: tensor too large");
         hipLaunchKernelGGL(f16::fir4_march_f16_kernel, dim3((unsigned)shg_cdiv(lanes(rows), 256)), dim3(256), 0, (hipStream_t)stream, p, rows);
-    } else if (same && fh == 4 && fw == 4) hipLaunchKernelGGL((f16::fir_same_f16_kernel<4, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
-    else if (same) hipLaunchKernelGGL((f16::fir_same_f16_kernel<0, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+    } else if (same) hipLaunchKernelGGL(f16::fir_same_f16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     else if (fh == 4 && fw == 4 && upx == 1 && upy == 1 && downx == 2 && downy == 2 && total < (1L << 31))
         hipLaunchKernelGGL((f16::updn4_f16_kernel<1, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     else if (fh == 4 && fw == 4 && upx == 2 && upy == 2 && downx == 1 && downy == 1 && total < (1L << 31))

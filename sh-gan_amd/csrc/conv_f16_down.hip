@@ -224,9 +224,6 @@ __global__ __launch_bounds__(512) void conv_f16_down_kernel(const DownP P) {
 // Stride-2 3x3 launches with whole 16-channel k-steps and whole 8-channel output pieces; of the fused tail bias, out_scale and the activation
 // (noise / residual / input scale stay on the gather kernel).
 bool conv_down_eligible(const ConvP& p) {
-#ifdef SHG_F16_NO_DOWN
-    return false;
-#else
     if (!(conv_f16_routes() & 4)) return false;
     if (p.s_in != 2 || p.s_out != 1 || p.ntaps != 9 || (p.I & 15) || (p.O & 7) || p.in_scale || p.residual || p.noise_mode) return false;
     // thin layers only: a step is one 16-channel k-step (36 MFMAs per wave against ten DMA requests and a barrier), which pays while the layer is
@@ -235,7 +232,6 @@ bool conv_down_eligible(const ConvP& p) {
     if (p.I > 128) return false;
     if ((reinterpret_cast<uintptr_t>(p.bias) | reinterpret_cast<uintptr_t>(p.out_scale)) & 15) return false;
     return (long)p.H * p.W * p.I * 2 < (1L << 31) && (long)p.OHt * p.OWt * p.O * 2 < (1L << 31);
-#endif
 }
 
 int conv_down_launch(const ConvP& p0, int pad, hipStream_t st) {

@@ -37,16 +37,6 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-#ifdef SHG_RING_TRACE
-// timeline study (python sh-gan_amd/build.py --variant=ringtrace -DSHG_RING_TRACE=1, tools/ring_trace.py): workgroup 0 records s_memtime of waves 0 and 7 at
-// four points of its first 64 steps: step entry | past vmcnt(0) + barrier | requests of the next step issued (+ deferred stores) | multiplied (+ packed)
-__device__ long long shg_ring_trace_buf[2 * 64 * 4];
-extern "C" int shg_ring_trace_read(long long* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(shg_ring_trace_buf), sizeof(shg_ring_trace_buf)); }
-#define RING_TRACE(slot) do { if (blockIdx.x == 0 && s < 64 && (wave == 0 || wave == 7) && lane == 0) shg_ring_trace_buf[((wave ? 1 : 0) * 64 + s) * 4 + (slot)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define RING_TRACE(slot) do { } while (0)
-#endif
-
 namespace ring {
 
 constexpr int TH = 16, TW = 32;                 // output pixels of a tile: wave w owns rows 2w, 2w + 1 (two 32-pixel MFMA column blocks)
@@ -80,7 +70,7 @@ struct Coord { int n, ty, tx, ot; };
 struct RingDiv { unsigned n_ot, tiles_x, tiles_y, m_ot, m_tx, m_ty; };    // divisors of the tile decode and floor(2^32 / divisor)
 
 // n / d for wave-uniform values with a precomputed m = floor((2^32 - 1) / d): the estimate is at most one short (scalar unit: ~8 instructions
-// instead of the ~40 of a runtime division -- the decode of the next tile stood between two steps' multiplies: tools/ring_trace.py 'issue')
+// instead of the ~40 of a runtime division -- the decode of the next tile stood between two steps' multiplies in a clock trace)
 __device__ __forceinline__ unsigned fastdiv(unsigned n, unsigned d, unsigned m, unsigned& rem) {
     unsigned q = __umulhi(n, m), r = n - q * d;
     if (r >= d) { ++q; r -= d; }
@@ -131,7 +121,7 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
     // ---- this wave's requests of a step: five patch pieces and five weight pieces (piece 8 i + wave; i = 4 exists for waves 0-3 only: the others
     // send theirs -- every lane out of range, zeros -- to the dump slot, wave 7 uses that slot for the tile's bias when there is one).  The requests
     // are issued one at a time BETWEEN the MFMAs of the running step: a `buffer_load ... lds` costs its wave 100-200 cycles at issue, and with the
-    // 80 requests of a step issued together after the barrier the matrix pipe idled 1 700-3 500 cycles per step (tools/ring_trace.py).
+    // 80 requests of a step issued together after the barrier the matrix pipe idled 1 700-3 500 cycles per step (clock trace).
     unsigned wsoff[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
@@ -285,16 +275,12 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
         for (int i = 0; i < 5; ++i) dma_weight(i, 0, tile_off);
         if (prm_any) { dma_params(cur, 0); if (!prm_per_tile) dma_params(cur, 1); }
     }
-#ifndef SHG_RING_NO_PRIO
     // the second-dispatched half of the workgroup loses the issue arbitration of its SIMD to the older wave on every step (wave 7 multiplies
     // 5.5 k cycles beside wave 0's 3.6 k, and the step ends with the slowest wave): one static priority for that half, no per-phase flips
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
     while (true) {
         // step s is in LDS once every wave's requests have landed; the same barrier says every wave has finished reading stage (s+1) & 1
-        RING_TRACE(0);
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        RING_TRACE(1);
         int nchunk = chunk + 1, ntile = tile;
         if (nchunk == nchunks) { nchunk = 0; ntile = tile + gridDim.x; }
         const bool has_next = ntile < ntiles;
@@ -305,7 +291,6 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
         const bool with_w = !(resident && s + 1 >= 2);
         const bool prm_next = prm_per_tile && nchunk == 0 && has_next;
         const int b_tpar = tpar ^ 1;
-        RING_TRACE(2);
         if (with_w) {
             if (pend) body(T_{}, T_{}, s & 1, chunk_off, tile_off, prm_next, nc, b_tpar);
             else body(T_{}, F_{}, s & 1, chunk_off, tile_off, prm_next, nc, b_tpar);
@@ -365,7 +350,6 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
             pend_addresses(cur);
             pend = true;
         }
-        RING_TRACE(3);
         if (!has_next) break;
         if (nchunk == 0) { tile = ntile; cur = nc; tpar ^= 1; }
         chunk = nchunk;
@@ -386,16 +370,12 @@ static int g_f16_routes = 7;         // bit 0: stride-1 3x3 launches on the ring
 int conv_f16_routes() { return g_f16_routes; }
 
 bool conv_ring_eligible(const ConvP& p, int span_y, int span_x) {
-#ifdef SHG_F16_NO_RING
-    return false;
-#else
     if (!(g_f16_routes & 1)) return false;
     if (p.s_in != 1 || p.ntaps != 9 || (p.O & 7) || (p.I & 31) || p.in_scale || p.residual) return false;
     if (p.tail && (p.s_out != 1 || p.oy0 || p.ox0)) return false;
     if (p.noise_mode && ((p.OWt & 3) || (reinterpret_cast<uintptr_t>(p.noise) & 15))) return false;
     if ((reinterpret_cast<uintptr_t>(p.bias) | reinterpret_cast<uintptr_t>(p.out_scale)) & 15) return false;
     return span_y == 3 && span_x == 3;                             // (the kernel's 18 x 34 patch)
-#endif
 }
 
 int conv_ring_launch(const ConvP& p0, int span_y, int span_x, hipStream_t st) {

@@ -248,13 +248,9 @@ __global__ __launch_bounds__(512) void conv_f16_upring_kernel(const UpP P) {
 // The merged kernel serves the stride-2 transposed 3x3 form with whole 32-channel input chunks and whole 8-channel output pieces, no bias
 // (the layers that use it add theirs after the FIR), with or without the input scale.
 bool convt_upring_eligible(const ConvP& p) {
-#ifdef SHG_F16_NO_UPRING
-    return false;
-#else
     if (!(conv_f16_routes() & 2)) return false;
     return (p.I & 31) == 0 && (p.O & 7) == 0 && !p.bias && !p.tail && p.I <= 512 && ((reinterpret_cast<uintptr_t>(p.in_scale)) & 15) == 0 &&
            (long)p.H * p.W * p.I * 2 < (1L << 31) && (long)p.OHt * p.OWt * p.O * 2 < (1L << 31);
-#endif
 }
 
 int convt_upring_launch(const ConvP& p0, int crop, hipStream_t st) {

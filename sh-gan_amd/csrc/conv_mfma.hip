@@ -88,14 +88,6 @@ struct ConvParams {
     int tail_first, tail_ks, tail_ips, fix;
     float* tail_ws;
     int raw_reduce;          // split-K tail only sums the slices (transposed conv: its epilogue lives in the FIR kernel)
-    // Ablation bits for kernel timing studies -- only in the -DSHG_ABLATE build used by tools/ (env SHG_CONV_DBG: 1 skip W
-    // loads, 2 skip X loads, 4 skip LDS stores, 8 skip barriers, 16 skip epilogue, 32 no tail split).  The product build
-    // has no such switch: `dbg` is the constant 0 there and every `p.dbg & ...` branch folds away.
-#ifdef SHG_ABLATE
-    int dbg;
-#else
-    static constexpr int dbg = 0;
-#endif
 };
 
 // Compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N-1>{}).  Used for the MFMA
@@ -261,20 +253,17 @@ __global__ __launch_bounds__(WO * WP * 64, OCC) void conv_mfma_kernel(const Conv
 
     auto piece_load = [&](int j, int i0) __attribute__((always_inline)) {
         if (j < PW0) {
-            if (!(p.dbg & 1)) wv[j] = *reinterpret_cast<const f32x4*>(wbase + (size_t)i0 * NTAPS * 64 + wl[j]);
+            wv[j] = *reinterpret_cast<const f32x4*>(wbase + (size_t)i0 * NTAPS * 64 + wl[j]);
         } else {
             const int k = (j - PW0) / XG, g = (j - PW0) % XG;
-            if (!(p.dbg & 2)) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int ic = g * 4 + c;
-                    xv[k][ic] = p.x[xo[k] + (unsigned)(min(i0 + ic, p.I - 1) * HW)];
-                }
+            for (int c = 0; c < 4; ++c) {
+                const int ic = g * 4 + c;
+                xv[k][ic] = p.x[xo[k] + (unsigned)(min(i0 + ic, p.I - 1) * HW)];
             }
         }
     };
     auto piece_store = [&](int j, int i0, int buf) __attribute__((always_inline)) {
-        if (p.dbg & 4) return;
         if (j < PW0) {
             const int e = tid + j * NT;
             if (e < V4) *reinterpret_cast<f32x4*>(Wl + buf * WSZ + e * 4) = wv[j];
@@ -294,7 +283,6 @@ __global__ __launch_bounds__(WO * WP * 64, OCC) void conv_mfma_kernel(const Conv
 
     // weights of the chunk starting at channel i0 -> LDS buffer `buf` (whole waves: V4 is a multiple of 64)
     auto w_dma = [&](int i0, int buf) __attribute__((always_inline)) {
-        if (p.dbg & 1) return;
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
             if ((k + 1) * NT <= V4 || k * NT + wave * 64 < V4)
@@ -442,14 +430,13 @@ __global__ __launch_bounds__(WO * WP * 64, OCC) void conv_mfma_kernel(const Conv
                 }
             });
         }
-        if (!(p.dbg & 8)) __syncthreads();
+        __syncthreads();
         if (!DB && more) {                           // single buffer: everyone is done reading -> overwrite, publish
 #pragma unroll
             for (int j = 0; j < NPIECE; ++j) piece_store(j, i0 + KC, 0);
             __syncthreads();
         }
     }
-    if (p.dbg & 16) return;
 
     // tail split: slice blocks park their raw accumulators in tail_ws [tile][slice][reg][thread]; the fix launch reads
     // them back inside the epilogue loops below (same code path as an ordinary tile from there on)
@@ -634,15 +621,8 @@ static int conv_ksplit(int grid, int chunks, bool allow) {
     return ks;
 }
 
-// smallest phase-grid width (W+1) that goes to the 8-wave double-buffered transposed-conv tiles (SHG_UP_MIN)
-static int conv_up_min() {
-#ifdef SHG_ABLATE
-    static const int v = getenv("SHG_UP_MIN") ? atoi(getenv("SHG_UP_MIN")) : 16;
-    return v;
-#else
-    return 16;
-#endif
-}
+// smallest phase-grid width (W+1) that goes to the 8-wave double-buffered transposed-conv tiles
+static constexpr int CONV_UP_MIN = 16;
 
 static int conv_cu_count() { return shg_cu_count(); }
 
@@ -682,7 +662,7 @@ static int launch_conv(ConvParams& p, void* workspace, size_t ws_bytes, hipStrea
     const int nwork = p.n_ptiles * p.n_otiles;
     p.tail_first = nwork; p.tail_ks = 1; p.tail_ips = p.I; p.fix = 0; p.tail_ws = nullptr;
     int n_tail = 0;
-    if (DB && p.ksplit == 1 && workspace && !(p.dbg & 32)) {
+    if (DB && p.ksplit == 1 && workspace) {
         const int slots = conv_cu_count();
         const int tail = nwork % slots;
         if (nwork > slots && tail > 0 && tail * 10 < slots * 6) {
@@ -858,21 +838,13 @@ static int launch_conv1x1_gemm(ConvParams& p, int narrow, hipStream_t s) {
 
 static int conv_dispatch(ConvParams& p, int K, int S, bool up, void* workspace, size_t ws_bytes, hipStream_t s) {
     const bool narrow = p.O <= 64;    // 64 x 256 tile instead of 128 x 128
-    // SHG_CONV_VARIANT (tuning knob, bit flags): 1 = force the single-buffer 4-wave kernels; 2 / 4 / 8 = try the 8-wave
-    // double-buffered variants for 64-channel layers / stride-2 (128 px) / stride-2 (256 px); 16 = transposed conv back on 8 waves;
-    // 32 = stride-2 back on 8 waves
-#ifdef SHG_ABLATE
-    static const int variant = getenv("SHG_CONV_VARIANT") ? atoi(getenv("SHG_CONV_VARIANT")) : 0;
-#else
-    constexpr int variant = 0;
-#endif
     if (up) {
         // all-phase transposed conv: large grids use 8-wave double-buffered tiles (128 ch x 128 px, or 64 ch x 256 px),
         // small ones the 4-wave 64 ch x 128 px tile (+ split-K)
-        const bool big = !(variant & 1) && p.OWp >= conv_up_min() && p.OHp >= 16 && p.wgroups == 1;
+        const bool big = p.OWp >= CONV_UP_MIN && p.OHp >= 16 && p.wgroups == 1;
         const bool raw_out = p.out_mode == 1 && !p.out_scale && !p.bias && !p.noise && !p.residual && !p.act;
         // planar hand-over to the FIR kernel: 16 waves (four instruction streams per SIMD), 128 ch x 128 px or 64 ch x 256 px
-        if (big && raw_out && !(variant & 16))
+        if (big && raw_out)
             return narrow ? launch_conv<9, 8, 1, 1, 2, 8, 1, true, true, 4>(p, workspace, ws_bytes, s)
                           : launch_conv<9, 8, 1, 1, 4, 4, 1, true, true, 4>(p, workspace, ws_bytes, s);
         if (big) return narrow ? launch_conv<9, 8, 2, 1, 1, 8, 1, true, true, 2>(p, workspace, ws_bytes, s)
@@ -881,28 +853,22 @@ static int conv_dispatch(ConvParams& p, int K, int S, bool up, void* workspace, 
     }
     if (K == 9 && S == 1) {
         // large images, many channels: 8-wave 128 x 256 tile, double-buffered LDS, staggered hand-over
-        if (!narrow && !(variant & 1) && p.OWp >= 32 && p.OHp >= 8 && p.wgroups == 1)
+        if (!narrow && p.OWp >= 32 && p.OHp >= 8 && p.wgroups == 1)
             return launch_conv<9, 8, 2, 2, 2, 4, 1, false, true, 2>(p, workspace, ws_bytes, s);
-        if (narrow && (variant & 2) && p.OWp >= 32 && p.OHp >= 16 && p.wgroups == 1)
-            return launch_conv<9, 8, 2, 2, 1, 8, 2, false, true, 2>(p, workspace, ws_bytes, s);
-        if (narrow && (variant & 8) && p.OWp >= 32 && p.OHp >= 16 && p.wgroups == 1)
-            return launch_conv<9, 8, 2, 2, 1, 4, 2, false, true, 2>(p, workspace, ws_bytes, s);
         return narrow ? launch_conv<9, 8, 2, 2, 1, 4, 2, false, false, 3>(p, workspace, ws_bytes, s)
                       : launch_conv<9, 8, 2, 2, 2, 2, 2, false, false, 2>(p, workspace, ws_bytes, s);
     }
     if (K == 9 && S == 2) {
-        if (!narrow && (variant & 4) && p.OWp >= 32 && p.OHp >= 4 && p.wgroups == 1)
-            return launch_conv<9, 8, 2, 1, 2, 4, 2, false, true, 2>(p, workspace, ws_bytes, s);
         // 128 ch x 256 px tile, double-buffered: 16 waves (4 instruction streams per SIMD; measured 3 % faster than 8 waves)
-        if (!narrow && !(variant & 33) && p.OWp >= 32 && p.OHp >= 8 && p.wgroups == 1 && !p.in_scale)
+        if (!narrow && p.OWp >= 32 && p.OHp >= 8 && p.wgroups == 1 && !p.in_scale)
             return launch_conv<9, 8, 1, 2, 4, 4, 2, false, true, 4>(p, workspace, ws_bytes, s);
-        if (!narrow && !(variant & 1) && p.OWp >= 32 && p.OHp >= 8 && p.wgroups == 1 && !p.in_scale)
+        if (!narrow && p.OWp >= 32 && p.OHp >= 8 && p.wgroups == 1 && !p.in_scale)
             return launch_conv<9, 8, 2, 2, 2, 4, 3, false, true, 2>(p, workspace, ws_bytes, s);
         return narrow ? launch_conv<9, 8, 2, 2, 1, 4, 5, false, false, 2>(p, workspace, ws_bytes, s)
                       : launch_conv<9, 8, 2, 2, 2, 2, 3, false, false, 2>(p, workspace, ws_bytes, s);
     }
     int c1_narrow = 0;
-    if (K == 1 && S == 1 && !(variant & 64) && conv1x1_gemm_ok(p, &c1_narrow)) return launch_conv1x1_gemm(p, c1_narrow, s);
+    if (K == 1 && S == 1 && conv1x1_gemm_ok(p, &c1_narrow)) return launch_conv1x1_gemm(p, c1_narrow, s);
     if (K == 1 && S == 1) return narrow ? launch_conv<1, 32, 2, 2, 1, 4, 1, false, false, 3>(p, workspace, ws_bytes, s)
                                         : launch_conv<1, 32, 2, 2, 2, 2, 1, false, false, 3>(p, workspace, ws_bytes, s);
     shg_set_error("conv2d: 1x1 stride-2 convolution is not implemented (decimate with upfirdn2d first)");
@@ -929,9 +895,6 @@ static int conv_fill(ConvParams& p, const float* x, const float* wt, float* y, i
     p.wgroups = wgroups < 1 ? 1 : wgroups; p.wstride = wstride;
     p.noise_mode = noise ? noise_mode : 0; p.noise_strength = noise_strength;
     p.act = act; p.alpha = alpha; p.gain = gain; p.clamp = clamp; p.out_mode = out_mode; p.ksplit = 1;
-#ifdef SHG_ABLATE
-    { const char* d = getenv("SHG_CONV_DBG"); p.dbg = d ? atoi(d) : 0; }
-#endif
     if (mode == 2) {
         // transposed stride 2 (conv2d_resample.py:130-137): Y = 2u+a, X = 2v+b over u in [0,H], v in [0,W]
         p.OHt = 2 * H + 1; p.OWt = 2 * W + 1; p.OHp = H + 1; p.OWp = W + 1; p.S = 1;
@@ -974,7 +937,7 @@ extern "C" size_t shg_conv2d_workspace_bytes(int NB, int I, int O, int H, int W,
     p.NB = NB; p.I = I; p.O = O; p.H = H; p.W = W; p.wgroups = wgroups < 1 ? 1 : wgroups;
     if (mode == 2) {   // small transposed convs (the 4-wave 64 x 128 tile) may split; planar output of 4 phase planes
         p.S = 1; p.span_y = 2; p.span_x = 2;
-        const bool big = W + 1 >= conv_up_min() && H + 1 >= 16 && p.wgroups == 1;
+        const bool big = W + 1 >= CONV_UP_MIN && H + 1 >= 16 && p.wgroups == 1;
         if (big) conv_tiles(p, O <= 64 ? 64 : 128, O <= 64 ? 256 : 128, true, 512);
         else conv_tiles(p, 64, 128, true, 512);
         const int ks = conv_ksplit(p.n_ptiles * p.n_otiles, shg_cdiv(I, 8), true);

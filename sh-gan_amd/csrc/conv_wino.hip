@@ -51,22 +51,12 @@ struct WinoParams {
     float noise_strength;
     int act;
     float alpha, gain, clamp;
-    // timing studies, -DSHG_ABLATE build only (env SHG_WINO_DBG: 1 skip weight loads, 2 skip window DMA, 4 skip transform,
-    // 16 skip epilogue); the product build folds every `p.dbg & ...` branch away
-#ifdef SHG_ABLATE
-    int dbg;
-#else
-    static constexpr int dbg = 0;
-#endif
 };
 
 namespace wino {
 // K chunk (input channels per barrier).  The weights never touch LDS (each wave keeps its own position's slice in
 // registers), so LDS holds only V and the raw windows: 12 channels = 137 KB of the 160 KB.
-#ifndef SHG_WINO_KC
-#define SHG_WINO_KC 8
-#endif
-constexpr int KC = SHG_WINO_KC, BO = 64, BT = 64;
+constexpr int KC = 8, BO = 64, BT = 64;
 static_assert(KC % 4 == 0 && (KC / 2) % 2 == 0 && KC <= 12, "KC: multiple of 4 with an even number of k-steps");
 // A tile is TY x TX blocks (TY * TX = 64) = 2TY x 2TX pixels: 4 x 16 (8 x 32 px) for images at least 32 wide, 8 x 8
 // (16 x 16 px) below.  Raw window per channel: rows oy0-1 .. oy0+2TY, columns ox0-4 .. ox0+2TX+3 (16-byte aligned in global
@@ -136,7 +126,6 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(const WinoParams p) {
     }
     const bool ract1 = lane < PATCH4 - 64;
     auto dma_raw = [&](int c, int buf) __attribute__((always_inline)) {
-        if (p.dbg & 2) return;
 #pragma unroll
         for (int q = 0; q < CPL; ++q) {
             const int k = (wave - NXF) * CPL + q;
@@ -160,7 +149,6 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(const WinoParams p) {
     const f32x4* ubase = reinterpret_cast<const f32x4*>(p.wu + (((size_t)otile * p.nchunk * 16 + wave) * 64 + lane) * KC) + (size_t)c0 * ustride;
     f32x4 ua[NU], ub[NU];                                       // even / odd chunks
     auto load_u = [&](f32x4 (&dst)[NU], int c) __attribute__((always_inline)) {
-        if (p.dbg & 1) return;
 #pragma unroll
         for (int j = 0; j < NU; ++j) dst[j] = ubase[(size_t)c * ustride + j];
     };
@@ -177,7 +165,6 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(const WinoParams p) {
         scv[v] = (p.in_scale && xformer && ch < p.I) ? p.in_scale[(long)n * p.I + ch] : 1.f;
     }
     auto transform = [&](int c, int buf) __attribute__((always_inline)) {
-        if (p.dbg & 4) return;
         // style of this wave's channel in chunk c: lane c%64 of the preloaded vector c/64
         const int ca = c0 + c;
         const float sc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ca < 64 ? scv[0] : scv[1]), ca & 63));
@@ -273,7 +260,6 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(const WinoParams p) {
         if (c + 1 < nch) chunk(std::integral_constant<int, 1>{}, c + 1);
     }
     mma(apend[0], apend[1], 1);
-    if (p.dbg & 16) return;
 
     // ---- epilogue: the 16 M_xi of an (o, t) pair live in 16 waves -> exchanged through LDS (the V buffers), four passes
     // of 32 channels x 32 blocks; inverse transform and fused layer tail, one (channel, block) item per thread and pass.
@@ -488,9 +474,6 @@ extern "C" int shg_conv2d_wino_ws_f32(const float* x, const float* wu, float* y,
     wino_plan(p, NB, I, OP, H, W);
     p.noise_mode = noise ? noise_mode : 0; p.noise_strength = noise_strength;
     p.act = act; p.alpha = alpha; p.gain = gain; p.clamp = clamp;
-#ifdef SHG_ABLATE
-    { const char* d = getenv("SHG_WINO_DBG"); p.dbg = d ? atoi(d) : 0; }
-#endif
     // K split: only with scratch for it, 16-byte aligned operands of the reduction (its loads are float4)
     int ks = workspace ? shg_wino_ksplit((long)p.n_ttiles * p.n_otiles, p.nchunk) : 1;
     const size_t out_bytes = (size_t)NB * O * H * W * sizeof(float);

@@ -31,24 +31,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __attribute__((aligned(16))) float shg_wino4_zeros[64];
 
-#ifdef SHG_W4_TRACE
-#ifndef SHG_W4_TRACE_WG
-#define SHG_W4_TRACE_WG 0          // which workgroup records (a late one shows the steady state, 0 the synchronised first round)
-#endif
-// timeline study (tools/w4_variant.sh trace -DSHG_W4_TRACE=1): workgroup 0 records clock64() at six points of chunks 8..15
-__device__ long long shg_wino4_trace_buf[8 * 8 * 8];
-extern "C" int shg_wino4_trace_read(long long* host) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(shg_wino4_trace_buf), sizeof(shg_wino4_trace_buf));
-}
-#define W4_TRACE(slot) do { if (blockIdx.x == SHG_W4_TRACE_WG && c >= SHG_W4_TRACE - 1 && c < SHG_W4_TRACE + 6 && lane == 0) shg_wino4_trace_buf[(wave * 8 + (c - (SHG_W4_TRACE - 1))) * 8 + (slot)] = clock64(); } while (0)
-#define W4_TRACE_T(slot) do { if (blockIdx.x == SHG_W4_TRACE_WG && (threadIdx.x & 63) == 0) shg_wino4_trace_buf[((threadIdx.x >> 6) * 8 + 7) * 8 + (slot)] = clock64(); } while (0)
-#define W4_TRACE_E(slot) do { if (SHG_W4_TRACE == 100 && blockIdx.x == SHG_W4_TRACE_WG && (threadIdx.x & 63) == 0) shg_wino4_trace_buf[(threadIdx.x >> 6) * 64 + (slot)] = clock64(); } while (0)
-#else
-#define W4_TRACE(slot) do { } while (0)
-#define W4_TRACE_T(slot) do { } while (0)
-#define W4_TRACE_E(slot) do { } while (0)
-#endif
-
 struct Wino4Params {
     const float* x;          // [NB, I, H, W]
     const float* wu;         // transformed weights [OP/64][nchunk][4 k-steps][72 units][64 lanes]
@@ -67,13 +49,6 @@ struct Wino4Params {
     float noise_strength;
     int act;
     float alpha, gain, clamp;
-    // timing studies (tools/w4_variant.sh <tag> -DSHG_WINO4_DBG=<bits>: 1 skip weight loads, 2 skip window DMA, 4 skip transform,
-    // 8 skip MFMA, 16 skip epilogue); the product build folds every `p.dbg & ...` branch away
-#ifdef SHG_WINO4_DBG
-    static constexpr int dbg = SHG_WINO4_DBG;
-#else
-    static constexpr int dbg = 0;
-#endif
 };
 
 namespace wino4 {
@@ -127,7 +102,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, half = lane >> 5;
-    W4_TRACE_T(0);
 
     const int nwork = p.n_ttiles * p.n_otiles;
     const int work = wino4_xcd_remap(blockIdx.x, nwork);
@@ -153,7 +127,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
         roff[j] = ok ? n * p.I * HW + iy * p.W + ix : -1;
     }
     auto dma_piece = [&](int c, int buf, int q, int j) __attribute__((always_inline)) {
-        if (p.dbg & 2) return;
         const int k = (wave - 4) * 2 + q;
         const int ch = (c0 + c) * KC + k;
         const bool chok = ch < iend;                             // (also false for chunks past the end)
@@ -199,18 +172,15 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
         return half ? s1 : s0;
     };
     auto tr_read = [&](int r, f32x4 (&w)[3], int buf) __attribute__((always_inline)) {
-        if (p.dbg & 4) return;
         const f32x4* rb = reinterpret_cast<const f32x4*>(rbase + buf * R_SZ + r * PW);
 #pragma unroll
         for (int q = 0; q < 3; ++q) w[q] = rb[q];
     };
     auto tr_row = [&](int r, const f32x4 (&w)[3], float (&u)[6][6], float sc) __attribute__((always_inline)) {
-        if (p.dbg & 4) return;
         const float di[6] = {w[0][3] * sc, w[1][0] * sc, w[1][1] * sc, w[1][2] * sc, w[1][3] * sc, w[2][0] * sc};
         wino4_bt(di, u[r]);
     };
     auto tr_col = [&](int j, const float (&u)[6][6], int buf) __attribute__((always_inline)) {
-        if (p.dbg & 4) return;
         float* vb = vbase + buf * V_SZ + j * KC * BT;
         const float di[6] = {u[0][j], u[1][j], u[2][j], u[3][j], u[4][j], u[5][j]};
         float o[6];
@@ -285,24 +255,16 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
         // while the first B operands of the next chunk are on their way from LDS.
         // Every iteration issues the same loads (past the end: re-fetches / zeros) so the compiler's wait counts for the weight
         // ring stay exact.
-#ifdef SHG_W4_PRIO
-        if constexpr (XF == (SHG_W4_PRIO == 1)) __builtin_amdgcn_s_setprio(3);      // (arbitration study: 1 = transform waves first, 2 = fetch waves)
-#endif
-        W4_TRACE_T(1);
         const int last = nch - 1;
         auto fetch = [&](const float* bb, int ks, int pb) __attribute__((always_inline)) {
 #pragma unroll
             for (int q = 0; q < NP; ++q) b[pb][q] = bb[(q * KC + ks * 2) * BT];
         };
         auto mma = [&](int ks, int pb, int j) __attribute__((always_inline)) {
-            if (!(p.dbg & 8)) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ur[ks][j], b[pb][j >> 1], acc[j], 0, 0, 0);
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ur[ks][j], b[pb][j >> 1], acc[j], 0, 0, 0);
         };
         auto refill = [&](int c, int ks, int j) __attribute__((always_inline)) {
-#ifdef SHG_W4_SAMEADDR
-            if (!(p.dbg & 1)) ur[ks][j] = ubase[(SHG_W4_SAMEADDR == 2 ? (size_t)(ks * NUNIT + j) * 64 : 0)];   // (study: L1-resident weights)
-#else
-            if (!(p.dbg & 1)) ur[ks][j] = ubase[(size_t)c * ustride + (ks * NUNIT + j) * 64];
-#endif
+            ur[ks][j] = ubase[(size_t)c * ustride + (ks * NUNIT + j) * 64];
         };
         for (int c = 0; c < nch; ++c) {
             const int buf = c & 1;
@@ -312,7 +274,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
             float u[6][6];
             float sc = 1.f;
             if constexpr (XF) sc = style_of(cn);
-            W4_TRACE(0);
             fetch(bb, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             // MFMA m of the chunk: group m / NU (0 = k-step 3 of the previous chunk -- zeros the first time round --, 1..3 = k-steps
@@ -337,11 +298,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            W4_TRACE(1);
 #pragma unroll
             for (int ks = 0; ks < 3; ++ks) {
-                if (ks == 1) W4_TRACE(2);
-                if (ks == 2) W4_TRACE(3);
                 fetch(bb, ks + 1, (ks + 1) & 1);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -358,25 +316,17 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
             for (int m = 4 * NU - RFD; m < 4 * NU; ++m) refill_m(m);
             // the last window piece went out ahead of all but 2*NPIECE - 1 - RFD of the chunk's 4*NU weight loads: in-order retirement makes
             // "at most that many outstanding" mean "the window has landed" without waiting for the weights
-            W4_TRACE(4);
             if constexpr (!XF) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * NU - 2 * NPIECE + 1 + RFD) : "memory");
             // raw barrier: __syncthreads() carries a release fence that the compiler lowers to `s_waitcnt vmcnt(0)`, i.e. a wait for
             // the weight loads just issued.  LDS traffic is ordered by lgkmcnt(0), the DMA by the count above.
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            W4_TRACE(5);
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            W4_TRACE(6);
         }
 #pragma unroll
         for (int j = 0; j < NU; ++j) mma(3, 1, j);
 
-        W4_TRACE_T(2);
         // epilogue: four passes (channel block ob, row half h) of 16 channels x 32 blocks x 36 positions through LDS
-        if (p.dbg & 16) {
-            if (acc[0][0] == 12345.f) p.y[0] = acc[1][1];
-            return;
-        }
         // Operands of the fused tail.  Every load is unconditional (absent operands read a block of zeros) and the loads of pass
         // p+1 are issued BEFORE the stores of pass p: a conditional load makes the compiler wait with vmcnt(0), and on this chip
         // vmcnt also counts stores -- the tail then waited for its own previous row to reach memory (1200 cycles per row, 5000 of a
@@ -405,7 +355,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
         auto finish = [&](int pass, TailOps& t) __attribute__((always_inline)) {
             const int ob = pass >> 1, h = pass & 1;
             const int o = o0 + ob * 32 + 16 * h + o_l;
-            W4_TRACE_E(pass * 8 + 1);
             // A^T m A: rows of m first (over the position columns), then columns
             float tmp[6][4];
     #pragma unroll
@@ -417,7 +366,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
     #pragma unroll
                 for (int k = 0; k < 4; ++k) tmp[r][k] = a4[k];
             }
-            W4_TRACE_E(pass * 8 + 2);
             f32x4 out[4];
     #pragma unroll
             for (int k = 0; k < 4; ++k) {                             // output column k of the block needs tmp[.][k]
@@ -431,9 +379,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
                     out[i][k] = v + t.rs[i][k];
                 }
             }
-            W4_TRACE_E(pass * 8 + 4);
             if (pass < 3) tail_load(pass + 1, t);                     // ahead of this pass's stores
-            W4_TRACE_E(pass * 8 + 5);
             if (o < p.O && col_ok) {
                 float* yp = p.y + blockIdx.y * p.part_stride + ((long)n * p.O + o) * plane;
     #pragma unroll
@@ -447,7 +393,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
 #pragma unroll
         for (int pass = 0; pass < 4; ++pass) {
             const int ob = pass >> 1, h = pass & 1;
-            W4_TRACE_E(pass * 8 + 0);
 #pragma unroll
             for (int q = 0; q < NP; ++q) {
 #pragma unroll
@@ -459,8 +404,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
             }
             __syncthreads();
             finish(pass, tops);
-            W4_TRACE_E(pass * 8 + 3);
-            W4_TRACE_T(3 + pass);
             if (pass < 3) __syncthreads();
         }
     };

@@ -37,10 +37,7 @@ __global__ __launch_bounds__(256) void bias_act_kernel(const float* x, float* y,
 // The scalar kernel above (three 64-bit divisions per ELEMENT) ran at 3.2 TB/s of read + write traffic on the 512^2 tensors of the training
 // step and 2.1 with scale + noise; this one 5.6 / 4.9 (tools/pointwise_bench.py).  PU > 1 (several float4 requested before the first use)
 // measured SLOWER: 4.5 / 4.3 / 3.8 TB/s at 2 / 4 / 8 -- the pass is not short of loads in flight.
-#ifndef SHG_PW_PU
-#define SHG_PW_PU 1
-#endif
-constexpr int PU = SHG_PW_PU;
+constexpr int PU = 1;
 __global__ __launch_bounds__(256) void bias_act_v4_kernel(const float4* x, float4* y, const float* scale, const float* bias, const float4* noise,
                                                           int noise_mode, float noise_strength, const float4* residual, unsigned C, unsigned HW4,
                                                           unsigned total4, int act, float alpha, float gain, float clamp) {

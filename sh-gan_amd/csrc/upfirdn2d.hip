@@ -38,12 +38,6 @@ struct UfdParams {
     // fir_same only: polyphase-planar output for the stride-2 convolution (conv_wino_poly.hip): when pl_pp > 0 the result
     // element (oy, ox) goes to plane (oy&1)*2 + (ox&1), row oy>>1, column ox>>1 of y [4][NC][pl_ph2][pl_pp]
     int pl_ph2, pl_pp;
-    // timing studies, -DSHG_ABLATE build only (env SHG_FIR_DBG: 1 skip window loads, 2 skip FIR math, 4 skip stores)
-#ifdef SHG_ABLATE
-    int dbg;
-#else
-    static constexpr int dbg = 0;
-#endif
 };
 
 __device__ __forceinline__ float ufd_epilogue(const UfdParams& p, float v, int nc, int oy, int ox) {
@@ -296,7 +290,7 @@ __global__ __launch_bounds__(256, 4) void fir_up_planar_kernel(const UfdParams p
             // valid full-resolution rows: Y = 2u+a in [0, 2H]  <=>  u in [0, H-a]
             const bool ok = v >= 0 && v <= p.W - pb_ && u >= 0 && u <= p.H - pa;
             const unsigned boff = ok ? (unsigned)(u * PWg + v) * 4u : 0u;
-            const float val = (p.dbg & 1) ? 1.f : *reinterpret_cast<const float*>(pb + boff);
+            const float val = *reinterpret_cast<const float*>(pb + boff);
             tvr[k] = ok ? val : 0.f;
         }
 #pragma unroll
@@ -363,7 +357,7 @@ __global__ __launch_bounds__(256, 4) void fir_up_planar_kernel(const UfdParams p
                     for (int ky = 0; ky < 4; ++ky)
 #pragma unroll
                         for (int kx = 0; kx < 4; ++kx) acc += m[dy + ky][dx + kx] * fr[ky * 4 + kx];
-                    o4[dx] = (p.dbg & 2) ? m[dy][dx] : acc;
+                    o4[dx] = acc;
                 }
                 const int pix = (2 * u + dy) * p.OW + 2 * v;
                 float* yp = p.y + (long)nc * p.OH * p.OW + pix;
@@ -386,7 +380,7 @@ __global__ __launch_bounds__(256, 4) void fir_up_planar_kernel(const UfdParams p
                         o[dx] = t;
                     }
                     if (dy < 2) nzq[dy & 1] = nz_row(dy + 2);                    // ahead of this row's store
-                    if (!(p.dbg & 4) || o[0] == 12345.f) *reinterpret_cast<float4*>(yp) = make_float4(o[0], o[1], o[2], o[3]);
+                    *reinterpret_cast<float4*>(yp) = make_float4(o[0], o[1], o[2], o[3]);
                 } else {
 #pragma unroll
                     for (int dx = 0; dx < 4; ++dx)
@@ -640,9 +634,6 @@ extern "C" int shg_upfir_planar_f32(const float* mid, const float* f, float* y, 
     p.scale = scale; p.bias = bias; p.noise = noise; p.residual = residual;
     p.noise_mode = noise ? noise_mode : 0; p.noise_strength = noise_strength;
     p.act = act; p.alpha = alpha; p.act_gain = act_gain; p.clamp = clamp; p.has_epilogue = 1;
-#ifdef SHG_ABLATE
-    { const char* d = getenv("SHG_FIR_DBG"); p.dbg = d ? atoi(d) : 0; }
-#endif
     // each workgroup walks several (n,c) planes with the next window prefetched; ~8k workgroups keep 256 CUs busy
     const int TV = W >= 96 ? 128 : (W >= 48 ? 64 : 32), TU = 1024 / TV;
     const int tiles = shg_cdiv(W, TV) * shg_cdiv(H, TU);

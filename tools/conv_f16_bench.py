@@ -3,9 +3,6 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import shgan_amd
-from shgan_amd import _lib
-if os.environ.get('SHG_VARIANT'):        # A/B knobs: python sh-gan_amd/build.py --variant=<tag> -D...
-    _lib.use_library(os.path.join(os.path.dirname(os.path.abspath(__file__)), '_variants', 'libshgan_hip_%s.so' % os.environ['SHG_VARIANT']))
 from shgan_amd import kernels_f16 as kf
 
 dev = 'cuda:0'
@@ -26,7 +23,7 @@ def timeit(fn, reps=10):
 
 
 N = 8
-FWD_ONLY = bool(os.environ.get('SHG_F16_FWD_ONLY'))     # ablation runs (tools/f16_abl.sh): forward shapes only
+FWD_ONLY = bool(os.environ.get('SHG_F16_FWD_ONLY'))     # forward shapes only
 for (i, o, r, k, s) in [(64, 64, 512, 3, 1), (128, 128, 256, 3, 1), (256, 256, 128, 3, 1), (512, 512, 64, 3, 1), (64, 128, 513, 3, 2), (128, 256, 257, 3, 2),
                          (64, 64, 512, 1, 1), (512, 512, 64, 1, 1)]:
     x = torch.randn(N, i, r, r, device=dev).half().to(memory_format=CL)

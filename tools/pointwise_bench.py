@@ -1,12 +1,9 @@
 """Streaming passes of the float32 (NCHW) training / inference path: bias + activation forward / backward, the fused modulation tail, channel
-scaling.  GB/s = algorithmic read + write bytes / time.  usage: [SHG_VARIANT=<tag>] python tools/pointwise_bench.py"""
+scaling.  GB/s = algorithmic read + write bytes / time.  usage: python tools/pointwise_bench.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import shgan_amd
-from shgan_amd import _lib
-if os.environ.get('SHG_VARIANT'):
-    _lib.use_library(os.path.join(os.path.dirname(os.path.abspath(__file__)), '_variants', 'libshgan_hip_%s.so' % os.environ['SHG_VARIANT']))
 from shgan_amd import kernels as kk
 
 dev = 'cuda:0'

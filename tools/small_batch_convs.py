@@ -3,9 +3,6 @@ on batch / 2 = 4 images).  us per launch and direct-form TFLOP/s."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, shgan_amd
-from shgan_amd import _lib
-if os.environ.get('SHG_VARIANT'):
-    _lib.use_library(os.path.join(os.path.dirname(os.path.abspath(__file__)), '_variants', 'libshgan_hip_%s.so' % os.environ['SHG_VARIANT']))
 from shgan_amd import kernels
 from shgan_amd.model_zoo.stylegan_utils import upfirdn2d as ufd
 

@@ -5,9 +5,6 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import shgan_amd
-from shgan_amd import _lib
-if os.environ.get('SHG_VARIANT'):
-    _lib.use_library(os.path.join(os.path.dirname(os.path.abspath(__file__)), '_variants', 'libshgan_hip_%s.so' % os.environ['SHG_VARIANT']))
 from shgan_amd import kernels as kk
 N = int(sys.argv[sys.argv.index('--batch') + 1]) if '--batch' in sys.argv else 8
 if os.environ.get('SHG_WGRAD_DIRECT'):
