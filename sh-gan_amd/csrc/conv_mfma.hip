@@ -862,8 +862,6 @@ static int conv_dispatch(ConvParams& p, int K, int S, bool up, void* workspace, 
         // 128 ch x 256 px tile, double-buffered: 16 waves (4 instruction streams per SIMD; measured 3 % faster than 8 waves)
         if (!narrow && p.OWp >= 32 && p.OHp >= 8 && p.wgroups == 1 && !p.in_scale)
             return launch_conv<9, 8, 1, 2, 4, 4, 2, false, true, 4>(p, workspace, ws_bytes, s);
-        if (!narrow && p.OWp >= 32 && p.OHp >= 8 && p.wgroups == 1 && !p.in_scale)
-            return launch_conv<9, 8, 2, 2, 2, 4, 3, false, true, 2>(p, workspace, ws_bytes, s);
         return narrow ? launch_conv<9, 8, 2, 2, 1, 4, 5, false, false, 2>(p, workspace, ws_bytes, s)
                       : launch_conv<9, 8, 2, 2, 2, 2, 3, false, false, 2>(p, workspace, ws_bytes, s);
     }

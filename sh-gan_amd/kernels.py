@@ -693,10 +693,12 @@ def conv2d(x, pw, mode=MODE_SAME, pad=0, in_scale=None, out_scale=None, bias=Non
     in_scale, out_scale, bias = L.req(in_scale, 'in_scale'), L.req(out_scale, 'out_scale'), L.req(bias, 'bias')
     if residual is not None and tuple(residual.shape) != tuple(y.shape):
         raise _lib.ShgError('conv2d: residual shape mismatch')
+    # the Winograd kernels read noise / residual in pieces: F(2x2) wants them 8-byte aligned, F(4x4) 16-byte aligned (y is ours)
+    tail_al = (_addr(noise) or 0) | (_addr(residual) or 0)
     if (WINO and mode == MODE_SAME and pad == 1 and pw.kh == 3 and pw.kw == 3 and pw.groups == 1 and h >= WINO_MIN and w >= WINO_MIN
-            and w % 4 == 0 and x.data_ptr() % 16 == 0 and i <= 1024 and (pw.wu is not None or pw._w is not None)):
+            and w % 4 == 0 and x.data_ptr() % 16 == 0 and tail_al % 8 == 0 and i <= 1024 and (pw.wu is not None or pw._w is not None)):
         direct = 2.0 * nb * pw.o * i * 9 * oh * ow                                # direct-form (algorithmic) flops
-        if WINO4 and h >= WINO4_MIN and lib.shg_conv2d_wino4_supported(nb, i, pw.o, h, w):
+        if WINO4 and h >= WINO4_MIN and tail_al % 16 == 0 and lib.shg_conv2d_wino4_supported(nb, i, pw.o, h, w):
             wu = pw.wino4()
             executed = 2.0 * nb * pw.o * i * 36.0 * ((h + 3) // 4) * ((w + 3) // 4)
             ws_bytes = int(lib.shg_conv2d_wino4_workspace_bytes(nb, i, pw.o, pw.op, h, w)) if WINO_SPLIT else 0
