@@ -25,10 +25,6 @@
 #include "shg_common.h"
 #include "conv_f16_p.h"
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f16x __attribute__((ext_vector_type(16)));
-
 namespace f16 {
 
 constexpr int TH = 8, TW = 16;       // output-pixel tile of a workgroup (4 waves x 2 rows x 16 columns)
@@ -309,8 +305,6 @@ struct WgradP {
     int slices, OP, IP;
     int XR, XC;                      // staged input rows / columns per block
 };
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // LDS images are TRANSPOSED while staging ([channel][pixel], 2-byte scatter writes of the 16-byte NHWC loads), so that an MFMA operand --
 // 8 consecutive pixels of one channel -- is ONE aligned ds_read_b128 instead of eight 2-byte gathers:

@@ -20,14 +20,6 @@
 namespace f16 {
 namespace down {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f16x __attribute__((ext_vector_type(16)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int TH = 8, TW = 32;                    // output pixels of a tile: wave w owns row w
 constexpr int PR = 2 * TH + 1, PC = 2 * TW + 1;   // window: 17 rows x 65 columns
 constexpr int ROWS = PC + 1;                      // slots of a window row: 33 even columns, 33 slots for the 32 odd ones (66)
@@ -41,25 +33,6 @@ struct DownP {
     unsigned m_ot, m_tx, m_ty;
 };
 
-__device__ __forceinline__ i32x4 make_srd(const void* base, unsigned bytes) {
-    const unsigned long long b = (unsigned long long)base;
-    i32x4 s;
-    s[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    s[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
-    s[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    s[3] = 0x00020000;
-    return s;
-}
-__device__ __forceinline__ void dma16(unsigned lds_addr, unsigned voff, i32x4 srd, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(voff), "s"(srd), "s"(soff));
-}
-__device__ __forceinline__ unsigned fastdiv(unsigned n, unsigned d, unsigned m, unsigned& rem) {
-    unsigned q = __umulhi(n, m), r = n - q * d;
-    if (r >= d) { ++q; r -= d; }
-    rem = r;
-    return q;
-}
-
 struct Coord { int n, ty, tx, ot; };
 
 __global__ __launch_bounds__(512) void conv_f16_down_kernel(const DownP P) {
@@ -72,11 +45,11 @@ __global__ __launch_bounds__(512) void conv_f16_down_kernel(const DownP P) {
 
     auto decode = [&](int tile) __attribute__((always_inline)) -> Coord {
         Coord c;
-        unsigned r, t = fastdiv((unsigned)tile, (unsigned)P.n_ot, P.m_ot, r);
+        unsigned r, t = shg_fastdiv((unsigned)tile, (unsigned)P.n_ot, P.m_ot, r);
         c.ot = (int)r;
-        t = fastdiv(t, (unsigned)P.tiles_x, P.m_tx, r);
+        t = shg_fastdiv(t, (unsigned)P.tiles_x, P.m_tx, r);
         c.tx = (int)r;
-        c.n = (int)fastdiv(t, (unsigned)P.tiles_y, P.m_ty, r);
+        c.n = (int)shg_fastdiv(t, (unsigned)P.tiles_y, P.m_ty, r);
         c.ty = (int)r;
         return c;
     };
@@ -84,7 +57,7 @@ __global__ __launch_bounds__(512) void conv_f16_down_kernel(const DownP P) {
     // ---- window requests: wave w owns pieces 5 w .. 5 w + 4 of the 40; lane l of a piece = slot 32 piece + l / 2, 16-byte half (l & 1) ^ bit 3
     // of the slot index; slot = row * 66 + (column & 1) * 33 + (column >> 1): input pixel (16 ty - pad + row, 64 tx - pad + column)
     unsigned pvoff[5];
-    i32x4 srd_x = make_srd(p.x, 0);
+    i32x4 srd_x = shg_make_srd(p.x, 0);
     auto tile_addresses = [&](const Coord& c) __attribute__((always_inline)) {
         const int iy0 = c.ty * (2 * TH) - P.pad, ix0 = c.tx * (2 * TW) - P.pad;
 #pragma unroll
@@ -95,24 +68,24 @@ __global__ __launch_bounds__(512) void conv_f16_down_kernel(const DownP P) {
             const bool ok = (row < PR) & (col < PC) & ((unsigned)iy < (unsigned)p.H) & ((unsigned)ix < (unsigned)p.W);
             pvoff[i] = ok ? (unsigned)(((iy * p.W + ix) * p.I + ch) * 2) : OOB;
         }
-        srd_x = make_srd(p.x + (long)c.n * p.H * p.W * p.I, (unsigned)(p.H * p.W * p.I * 2));
+        srd_x = shg_make_srd(p.x + (long)c.n * p.H * p.W * p.I, (unsigned)(p.H * p.W * p.I * 2));
     };
-    const i32x4 srd_w = make_srd(p.w, (unsigned)((long)((p.OB + 3) / 4 * 4) * 9 * c16n * 1024));
+    const i32x4 srd_w = shg_make_srd(p.w, (unsigned)((long)((p.OB + 3) / 4 * 4) * 9 * c16n * 1024));
     auto dma_patch = [&](int i, int stage, unsigned step_off) __attribute__((always_inline)) {
-        dma16(lds0 + L_P + stage * PSTAGE + (wave * 5 + i) * 1024, pvoff[i], srd_x, step_off);
+        shg_dma16(lds0 + L_P + stage * PSTAGE + (wave * 5 + i) * 1024, pvoff[i], srd_x, step_off);
     };
     // weight pieces of a step: piece = tap * 4 + channel block (36); wave w issues pieces w, w + 8, w + 16, w + 24 and (waves 0-3) w + 32
     auto dma_weight = [&](int i, int stage, unsigned tile_off) __attribute__((always_inline)) {
         const int pi = i * 8 + wave;
-        if (pi < 36) dma16(lds0 + L_W + stage * WSTAGE + pi * 1024, (unsigned)(lane * 16), srd_w,
+        if (pi < 36) shg_dma16(lds0 + L_W + stage * WSTAGE + pi * 1024, (unsigned)(lane * 16), srd_w,
                            (unsigned)(((pi & 3) * 9 + (pi >> 2)) * c16n * 1024) + tile_off);
     };
     // a tile's parameters (waves 6 / 7): 128 bias values | 128 out_scale values of sample n (each its own KiB)
     auto dma_params = [&](const Coord& c, int tpar) __attribute__((always_inline)) {
         const unsigned dst = lds0 + L_PRM + tpar * 2048;
-        if (wave == 7) { if (p.bias) dma16(dst, lane < 32 ? (unsigned)(c.ot * 512 + lane * 16) : OOB, make_srd(p.bias, (unsigned)(p.O * 4)), 0u); }
+        if (wave == 7) { if (p.bias) shg_dma16(dst, lane < 32 ? (unsigned)(c.ot * 512 + lane * 16) : OOB, shg_make_srd(p.bias, (unsigned)(p.O * 4)), 0u); }
         else if (wave == 6) {
-            if (p.out_scale) dma16(dst + 1024, lane < 32 ? (unsigned)((c.n * p.O + c.ot * 128) * 4 + lane * 16) : OOB, make_srd(p.out_scale, (unsigned)((long)p.N * p.O * 4)), 0u);
+            if (p.out_scale) shg_dma16(dst + 1024, lane < 32 ? (unsigned)((c.n * p.O + c.ot * 128) * 4 + lane * 16) : OOB, shg_make_srd(p.out_scale, (unsigned)((long)p.N * p.O * 4)), 0u);
         }
     };
 
@@ -173,7 +146,7 @@ __global__ __launch_bounds__(512) void conv_f16_down_kernel(const DownP P) {
         if (step == nsteps - 1) {
             // C/D layout: column (pixel) = lane & 31, row (channel) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
             const unsigned char* prm = lds + L_PRM + tpar * 2048;
-            const i32x4 srd_y = make_srd(p.y + (long)cur.n * p.OHt * p.OWt * p.O, (unsigned)(p.OHt * p.OWt * p.O * 2));
+            const i32x4 srd_y = shg_make_srd(p.y + (long)cur.n * p.OHt * p.OWt * p.O, (unsigned)(p.OHt * p.OWt * p.O * 2));
             const int oy = cur.ty * TH + wave, ox = cur.tx * TW + j;
             const bool ok = (oy < p.OHt) & (ox < p.OWt);
             const unsigned pix = ok ? (unsigned)((oy * p.OWt + ox) * p.O * 2) : OOB;

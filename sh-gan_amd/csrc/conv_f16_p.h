@@ -1,9 +1,16 @@
 // Launch parameters of the fp16 gather convolutions (conv_f16.hip: conv_f16_kernel; conv_f16_ring.hip: the persistent LDS-DMA kernel for
 // the stride-1-read forms).  gfx950 only.
 #pragma once
-#include "shg_common.h"
+#include "shg_device.h"
 
 namespace f16 {
+
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+typedef float f16x __attribute__((ext_vector_type(16)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct ConvP {
     const _Float16* x;

@@ -29,14 +29,6 @@
 
 namespace f16 {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f16x __attribute__((ext_vector_type(16)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace ring {
 
 constexpr int TH = 16, TW = 32;                 // output pixels of a tile: wave w owns rows 2w, 2w + 1 (two 32-pixel MFMA column blocks)
@@ -50,33 +42,9 @@ constexpr int PRM = 4096, PRM_SCALE = 1024, PRM_NOISE = 2048;      // a tile's p
 constexpr int LDS_BYTES = L_PRM + 2 * PRM;      // 163 840: all of the CU's LDS
 constexpr unsigned OOB = 0x80000000u;           // a byte offset no descriptor range admits: the DMA writes zeros for that lane
 
-__device__ __forceinline__ i32x4 make_srd(const void* base, unsigned bytes) {
-    const unsigned long long b = (unsigned long long)base;
-    i32x4 s;
-    s[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    s[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
-    s[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    s[3] = 0x00020000;                          // raw buffer, dword data format (tools/micro/lds_dma_probe.hip pins the semantics used here)
-    return s;
-}
-
-// 64 lanes x 16 bytes global -> LDS [lds_addr + 16 lane]; lanes whose voff + soff fails the range check deliver zeros
-__device__ __forceinline__ void dma16(unsigned lds_addr, unsigned voff, i32x4 srd, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(voff), "s"(srd), "s"(soff));
-}
-
 struct Coord { int n, ty, tx, ot; };
 
 struct RingDiv { unsigned n_ot, tiles_x, tiles_y, m_ot, m_tx, m_ty; };    // divisors of the tile decode and floor(2^32 / divisor)
-
-// n / d for wave-uniform values with a precomputed m = floor((2^32 - 1) / d): the estimate is at most one short (scalar unit: ~8 instructions
-// instead of the ~40 of a runtime division -- the decode of the next tile stood between two steps' multiplies in a clock trace)
-__device__ __forceinline__ unsigned fastdiv(unsigned n, unsigned d, unsigned m, unsigned& rem) {
-    unsigned q = __umulhi(n, m), r = n - q * d;
-    if (r >= d) { ++q; r -= d; }
-    rem = r;
-    return q;
-}
 
 template <int NT>
 __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const int ntiles, const RingDiv dv) {
@@ -91,11 +59,11 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
 
     auto decode = [&](int tile) __attribute__((always_inline)) -> Coord {
         Coord c;
-        unsigned r, t = fastdiv((unsigned)tile, dv.n_ot, dv.m_ot, r);
+        unsigned r, t = shg_fastdiv((unsigned)tile, dv.n_ot, dv.m_ot, r);
         c.ot = (int)r;
-        t = fastdiv(t, dv.tiles_x, dv.m_tx, r);
+        t = shg_fastdiv(t, dv.tiles_x, dv.m_tx, r);
         c.tx = (int)r;
-        c.n = (int)fastdiv(t, dv.tiles_y, dv.m_ty, r);
+        c.n = (int)shg_fastdiv(t, dv.tiles_y, dv.m_ty, r);
         c.ty = (int)r;
         return c;
     };
@@ -104,7 +72,7 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
     // lane l of a piece = patch pixel 32 grp + l / 2, 16-byte half (l & 1) ^ bit 3 of the pixel index
     const int ks_dma = wave >> 2;
     unsigned pvoff[5];
-    i32x4 srd_x = make_srd(p.x, 0);
+    i32x4 srd_x = shg_make_srd(p.x, 0);
     auto tile_addresses = [&](const Coord& c) __attribute__((always_inline)) {
         const int iy0 = c.ty * TH + p.org_y, ix0 = c.tx * TW + p.org_x;
 #pragma unroll
@@ -115,9 +83,9 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
             const bool ok = (pp < npix) & ((unsigned)iy < (unsigned)p.H) & ((unsigned)ix < (unsigned)p.W);
             pvoff[i] = ok ? (unsigned)(((iy * p.W + ix) * p.I + ch) * 2) : OOB;
         }
-        srd_x = make_srd(p.x + (long)c.n * p.H * p.W * p.I, (unsigned)(p.H * p.W * p.I * 2));
+        srd_x = shg_make_srd(p.x + (long)c.n * p.H * p.W * p.I, (unsigned)(p.H * p.W * p.I * 2));
     };
-    const i32x4 srd_w = make_srd(p.w, (unsigned)((long)((p.OB + 3) / 4 * 4) * p.wslots * c16n * 1024));
+    const i32x4 srd_w = shg_make_srd(p.w, (unsigned)((long)((p.OB + 3) / 4 * 4) * p.wslots * c16n * 1024));
     // ---- this wave's requests of a step: five patch pieces and five weight pieces (piece 8 i + wave; i = 4 exists for waves 0-3 only: the others
     // send theirs -- every lane out of range, zeros -- to the dump slot, wave 7 uses that slot for the tile's bias when there is one).  The requests
     // are issued one at a time BETWEEN the MFMAs of the running step: a `buffer_load ... lds` costs its wave 100-200 cycles at issue, and with the
@@ -130,25 +98,25 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
     }
     const bool w4_ok = 32 + wave < NT * 4;
     auto dma_patch = [&](int i, int stage, unsigned chunk_off) __attribute__((always_inline)) {
-        dma16(lds0 + L_P + stage * PSTAGE + (ks_dma * 20 + (wave & 3) * 5 + i) * 1024, pvoff[i], srd_x, chunk_off);
+        shg_dma16(lds0 + L_P + stage * PSTAGE + (ks_dma * 20 + (wave & 3) * 5 + i) * 1024, pvoff[i], srd_x, chunk_off);
     };
     auto dma_weight = [&](int i, int stage, unsigned tile_off) __attribute__((always_inline)) {
-        if (i < 4) dma16(lds0 + L_W + stage * WSTAGE + (i * 8 + wave) * 1024, (unsigned)(lane * 16), srd_w, wsoff[i] + tile_off);
-        else if (w4_ok) dma16(lds0 + L_W + stage * WSTAGE + (32 + wave) * 1024, (unsigned)(lane * 16), srd_w, wsoff[4] + tile_off);
+        if (i < 4) shg_dma16(lds0 + L_W + stage * WSTAGE + (i * 8 + wave) * 1024, (unsigned)(lane * 16), srd_w, wsoff[i] + tile_off);
+        else if (w4_ok) shg_dma16(lds0 + L_W + stage * WSTAGE + (32 + wave) * 1024, (unsigned)(lane * 16), srd_w, wsoff[4] + tile_off);
     };
     // a tile's parameters, one request each from the waves without a fifth weight piece: wave 7 the 64 bias values of the channel tile, wave 6 its
     // 64 out_scale values of sample n (beyond the tensor: zeros; those channels are never stored), waves 4 / 5 noise rows 0-7 / 8-15 of the
     // tile (lane = row l / 8, columns 4 (l % 8) ..; OW % 4 == 0 keeps a piece inside or outside its row as a whole)
     auto dma_params = [&](const Coord& c, int tpar) __attribute__((always_inline)) {
         const unsigned dst = lds0 + L_PRM + tpar * PRM;       // (descriptors are built here, once per tile: held for the whole kernel they cost 12 scalar registers)
-        if (wave == 7) { if (p.bias) dma16(dst, lane < 16 ? (unsigned)(c.ot * 256 + lane * 16) : OOB, make_srd(p.bias, (unsigned)(p.O * 4)), 0u); }
+        if (wave == 7) { if (p.bias) shg_dma16(dst, lane < 16 ? (unsigned)(c.ot * 256 + lane * 16) : OOB, shg_make_srd(p.bias, (unsigned)(p.O * 4)), 0u); }
         else if (wave == 6) {
-            if (p.out_scale) dma16(dst + PRM_SCALE, lane < 16 ? (unsigned)((c.n * p.O + c.ot * 64) * 4 + lane * 16) : OOB, make_srd(p.out_scale, (unsigned)((long)p.N * p.O * 4)), 0u);
+            if (p.out_scale) shg_dma16(dst + PRM_SCALE, lane < 16 ? (unsigned)((c.n * p.O + c.ot * 64) * 4 + lane * 16) : OOB, shg_make_srd(p.out_scale, (unsigned)((long)p.N * p.O * 4)), 0u);
         } else if (wave >= 4 && p.noise_mode) {
             const int gy = c.ty * TH + (wave - 4) * 8 + (lane >> 3), gx = c.tx * TW + (lane & 7) * 4;
             const unsigned img = p.noise_mode == 2 ? (unsigned)c.n * (unsigned)(p.OHt * p.OWt) : 0u;
-            dma16(dst + PRM_NOISE + (wave - 4) * 1024, (gy < p.OHt && gx < p.OWt) ? (img + (unsigned)(gy * p.OWt + gx)) * 4u : OOB,
-                  make_srd(p.noise, (unsigned)((long)(p.noise_mode == 2 ? p.N : 1) * p.OHt * p.OWt * 4)), 0u);
+            shg_dma16(dst + PRM_NOISE + (wave - 4) * 1024, (gy < p.OHt && gx < p.OWt) ? (img + (unsigned)(gy * p.OWt + gx)) * 4u : OOB,
+                      shg_make_srd(p.noise, (unsigned)((long)(p.noise_mode == 2 ? p.N : 1) * p.OHt * p.OWt * 4)), 0u);
         }
     };
 
@@ -178,7 +146,7 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
     u32x2 pk[2][2][4];
     unsigned pyoff[2] = {OOB, OOB};
     int p_ot = 0;
-    i32x4 srd_y = make_srd(p.y, 0);
+    i32x4 srd_y = shg_make_srd(p.y, 0);
     bool pend = false;
     auto pend_addresses = [&](const Coord& c) __attribute__((always_inline)) {
 #pragma unroll
@@ -189,7 +157,7 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
             pyoff[q] = ok ? (unsigned)((oy * p.OWt + ox) * p.O * 2) : OOB;
         }
         p_ot = c.ot;
-        srd_y = make_srd(p.y + (long)c.n * p.OHt * p.OWt * p.O, (unsigned)(p.OHt * p.OWt * p.O * 2));
+        srd_y = shg_make_srd(p.y + (long)c.n * p.OHt * p.OWt * p.O, (unsigned)(p.OHt * p.OWt * p.O * 2));
     };
     auto store_piece = [&](int k) __attribute__((always_inline)) {          // k = (q, m, gp)
         const int q = k >> 2, m = (k >> 1) & 1, gp = k & 1;

@@ -21,14 +21,6 @@
 namespace f16 {
 namespace upring {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f16x __attribute__((ext_vector_type(16)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int TH = 16, TW = 32, PW = TW + 1;       // grid pixels of a tile; patch = (TH + 1) x (TW + 1) input pixels
 constexpr int PPX = 640, PLANE = PPX * 32, PSTAGE = 2 * PLANE, WSTAGE = 18 * 1024;
 constexpr int L_W = 0, L_P = 2 * WSTAGE, L_S = L_P + 2 * PSTAGE, LDS_BYTES = L_S + 2 * 2048;
@@ -39,25 +31,6 @@ struct UpP {
     int crop, tiles_x, tiles_y, n_ot, ntiles;
     unsigned m_ot, m_tx, m_ty;  // floor((2^32 - 1) / divisor) of the tile decode
 };
-
-__device__ __forceinline__ i32x4 make_srd(const void* base, unsigned bytes) {
-    const unsigned long long b = (unsigned long long)base;
-    i32x4 s;
-    s[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    s[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
-    s[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    s[3] = 0x00020000;
-    return s;
-}
-__device__ __forceinline__ void dma16(unsigned lds_addr, unsigned voff, i32x4 srd, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(voff), "s"(srd), "s"(soff));
-}
-__device__ __forceinline__ unsigned fastdiv(unsigned n, unsigned d, unsigned m, unsigned& rem) {
-    unsigned q = __umulhi(n, m), r = n - q * d;
-    if (r >= d) { ++q; r -= d; }
-    rem = r;
-    return q;
-}
 
 struct Coord { int n, ty, tx, ot; };
 
@@ -72,11 +45,11 @@ __global__ __launch_bounds__(512) void conv_f16_upring_kernel(const UpP P) {
 
     auto decode = [&](int tile) __attribute__((always_inline)) -> Coord {
         Coord c;
-        unsigned r, t = fastdiv((unsigned)tile, (unsigned)P.n_ot, P.m_ot, r);
+        unsigned r, t = shg_fastdiv((unsigned)tile, (unsigned)P.n_ot, P.m_ot, r);
         c.ot = (int)r;
-        t = fastdiv(t, (unsigned)P.tiles_x, P.m_tx, r);
+        t = shg_fastdiv(t, (unsigned)P.tiles_x, P.m_tx, r);
         c.tx = (int)r;
-        c.n = (int)fastdiv(t, (unsigned)P.tiles_y, P.m_ty, r);
+        c.n = (int)shg_fastdiv(t, (unsigned)P.tiles_y, P.m_ty, r);
         c.ty = (int)r;
         return c;
     };
@@ -85,7 +58,7 @@ __global__ __launch_bounds__(512) void conv_f16_upring_kernel(const UpP P) {
     // (l & 1) ^ bit 3 of the pixel index (the swizzle of conv_f16_ring.hip); patch pixel (r, c) = input pixel (16 ty - 1 + r, 32 tx - 1 + c)
     const int ks_dma = wave >> 2;
     unsigned pvoff[5];
-    i32x4 srd_x = make_srd(p.x, 0);
+    i32x4 srd_x = shg_make_srd(p.x, 0);
     auto tile_addresses = [&](const Coord& c) __attribute__((always_inline)) {
         const int iy0 = c.ty * TH - 1, ix0 = c.tx * TW - 1;
 #pragma unroll
@@ -95,23 +68,23 @@ __global__ __launch_bounds__(512) void conv_f16_upring_kernel(const UpP P) {
             const bool ok = (py <= TH) & ((unsigned)iy < (unsigned)p.H) & ((unsigned)ix < (unsigned)p.W);
             pvoff[i] = ok ? (unsigned)(((iy * p.W + ix) * p.I + ch) * 2) : OOB;
         }
-        srd_x = make_srd(p.x + (long)c.n * p.H * p.W * p.I, (unsigned)(p.H * p.W * p.I * 2));
+        srd_x = shg_make_srd(p.x + (long)c.n * p.H * p.W * p.I, (unsigned)(p.H * p.W * p.I * 2));
     };
-    const i32x4 srd_w = make_srd(p.w, (unsigned)((long)((p.OB + 3) / 4 * 4) * 9 * c16n * 1024));
+    const i32x4 srd_w = shg_make_srd(p.w, (unsigned)((long)((p.OB + 3) / 4 * 4) * 9 * c16n * 1024));
     auto dma_patch = [&](int i, int stage, unsigned chunk_off) __attribute__((always_inline)) {
-        dma16(lds0 + L_P + stage * PSTAGE + (ks_dma * 20 + (wave & 3) * 5 + i) * 1024, pvoff[i], srd_x, chunk_off);
+        shg_dma16(lds0 + L_P + stage * PSTAGE + (ks_dma * 20 + (wave & 3) * 5 + i) * 1024, pvoff[i], srd_x, chunk_off);
     };
     // weight pieces of a step: piece = tap * 2 + k-step (18); wave w issues pieces w, w + 8 and (waves 0, 1) w + 16
     auto dma_weight = [&](int i, int stage, unsigned tile_off) __attribute__((always_inline)) {
         const int pi = i * 8 + wave;
-        if (pi < 18) dma16(lds0 + L_W + stage * WSTAGE + pi * 1024, (unsigned)(lane * 16), srd_w, (unsigned)((((pi >> 1) * c16n) + (pi & 1)) * 1024) + tile_off);
+        if (pi < 18) shg_dma16(lds0 + L_W + stage * WSTAGE + pi * 1024, (unsigned)(lane * 16), srd_w, (unsigned)((((pi >> 1) * c16n) + (pi & 1)) * 1024) + tile_off);
     };
     // in_scale row of sample n (I floats, at most 2 KiB): waves 6 / 7 fetch its halves
     auto dma_scale = [&](const Coord& c, int tpar) __attribute__((always_inline)) {
         if (wave >= 6) {
             const int off = (wave - 6) * 1024 + lane * 16;
-            dma16(lds0 + L_S + tpar * 2048 + (wave - 6) * 1024, off < p.I * 4 ? (unsigned)(c.n * p.I * 4 + off) : OOB,
-                  make_srd(p.in_scale, (unsigned)((long)p.N * p.I * 4)), 0u);
+            shg_dma16(lds0 + L_S + tpar * 2048 + (wave - 6) * 1024, off < p.I * 4 ? (unsigned)(c.n * p.I * 4 + off) : OOB,
+                  shg_make_srd(p.in_scale, (unsigned)((long)p.N * p.I * 4)), 0u);
         }
     };
 
@@ -207,7 +180,7 @@ __global__ __launch_bounds__(512) void conv_f16_upring_kernel(const UpP P) {
             // C/D layout: column (pixel) = lane & 31, row (channel) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); lanes 0-31 hold channels 8g .. 8g+3 of
             // group g, lanes 32-63 channels 8g+4 .. 8g+7: after the half exchange the lower lanes own the 16 bytes of group 2 gp, the upper
             // lanes those of group 2 gp + 1
-            const i32x4 srd_y = make_srd(p.y + (long)cur.n * p.OHt * p.OWt * p.O, (unsigned)(p.OHt * p.OWt * p.O * 2));
+            const i32x4 srd_y = shg_make_srd(p.y + (long)cur.n * p.OHt * p.OWt * p.O, (unsigned)(p.OHt * p.OWt * p.O * 2));
 #pragma unroll
             for (int ph = 0; ph < 4; ++ph)
 #pragma unroll

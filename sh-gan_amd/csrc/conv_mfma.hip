@@ -35,12 +35,9 @@
 //     reduce/epilogue kernel) so that 4x4..16x16 layers still fill 256 CUs.
 // The stride-1 3x3 layers of images >= 16x16 normally run on the Winograd kernel (conv_wino.hip); this
 // file serves them when W % 4 != 0 and for everything else (stride 2, transposed, 1x1, tiny images).
-#include "shg_common.h"
+#include "shg_device.h"
 #include <stdlib.h>
 #include <utility>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));   // native vector: stays in registers (HIP's float4 struct copies may not)
 
 struct ConvParams {
     const float* x;          // [NB, I, H, W]
@@ -101,15 +98,6 @@ __device__ __forceinline__ void static_for(F&& f) {
     static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
 }
 
-// Bijective XCD-aware remap (blocks b, b+8, ... share an XCD and its L2): every XCD walks a
-// contiguous range of the o-tile-major work list, so its L2 holds one weight slice at a time.
-__device__ __forceinline__ int xcd_remap(int bid, int total) {
-    const int q = total >> 3, r = total & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + idx;
-}
-
 __device__ __forceinline__ float conv_epilogue(const ConvParams& p, float v, int n, int o, long idx, float nz) {
     if (p.out_scale) v *= p.out_scale[n * p.O + o];
     v += nz;
@@ -154,8 +142,8 @@ __global__ __launch_bounds__(WO * WP * 64, OCC) void conv_mfma_kernel(const Conv
     else if ((int)blockIdx.x >= p.tail_first && p.ksplit == 1) {
         const int tb = blockIdx.x - p.tail_first;
         kslice = 0; work = p.tail_first + tb / p.tail_ks; tslice = tb - (tb / p.tail_ks) * p.tail_ks;
-    } else if (p.ksplit == 1) { kslice = 0; work = xcd_remap(blockIdx.x, p.tail_first); }
-    else { kslice = blockIdx.x / nwork; work = xcd_remap(blockIdx.x - kslice * nwork, nwork); }
+    } else if (p.ksplit == 1) { kslice = 0; work = shg_xcd_remap(blockIdx.x, p.tail_first); }
+    else { kslice = blockIdx.x / nwork; work = shg_xcd_remap(blockIdx.x - kslice * nwork, nwork); }
     const int otile = work / p.n_ptiles;
     int ptile = work - otile * p.n_ptiles;
     int ci = 0;
@@ -713,7 +701,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_gemm_kernel(const ConvParams p
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wo = wave / WP, wp = wave % WP;
     const int P = p.H * p.W, ptiles = P / BP, otiles = p.O / BO;
-    int t = xcd_remap(blockIdx.x, gridDim.x);
+    int t = shg_xcd_remap(blockIdx.x, gridDim.x);
     const int ot = t % otiles; t /= otiles;
     const int pt = t % ptiles, n = t / ptiles;
     const int o0 = ot * BO, p0 = pt * BP;
@@ -801,8 +789,10 @@ __global__ __launch_bounds__(256, 2) void conv1x1_gemm_kernel(const ConvParams p
                 f32x4 out;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
+                    // (an expression of its own -- one contracted v4 * osc + bs -- not conv_epilogue's conditional multiply / adds and not shg_conv_tail's
+                    // sum with a noise term: equal to either within rounding, bit identity is not claimed)
                     float v = v4[q] * osc + bs;
-                    v = p.act ? shg_lrelu_agc(v, p.alpha, p.gain, p.clamp) : v * p.gain;   // (same expression as conv_epilogue: identical bits)
+                    v = p.act ? shg_lrelu_agc(v, p.alpha, p.gain, p.clamp) : v * p.gain;
                     out[q] = v + rs[q];
                 }
                 *reinterpret_cast<f32x4*>(p.y + idx) = out;

@@ -15,7 +15,7 @@
 // registers (one workgroup per CU, 68 KB of LDS, the staged values live in the 512-register budget beside the 144
 // accumulators).  K slices are summed by a second tiny kernel in slice order, so the result is
 // deterministic (no atomics).
-#include "shg_common.h"
+#include "conv_wgrad_p.h"
 
 typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -479,7 +479,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* part, fl
 }
 
 static void launch_wgrad_reduce(const float* part, float* dw, long n, int nslice, hipStream_t s);
-void shg_launch_wgrad_reduce(const float* part, float* dw, long n, int nslice, hipStream_t s) { launch_wgrad_reduce(part, dw, n, nslice, s); }    // conv_wgrad_wino.hip
+void shg_launch_wgrad_reduce(const float* part, float* dw, long n, int nslice, hipStream_t s) { launch_wgrad_reduce(part, dw, n, nslice, s); }    // (conv_wgrad_p.h: for conv_wgrad_wino.hip)
 static void launch_wgrad_reduce(const float* part, float* dw, long n, int nslice, hipStream_t s) {
     int G = 1;
     while (G < 16 && (n + 256 / G - 1) / (256 / G) < 2048 && nslice >= 8 * G) G *= 2;

@@ -17,12 +17,9 @@
 // buffered, 16 channels interleaved per piece so that the 16 channels of a ds_read_b128 group hit 16 consecutive 16-byte slots (the
 // interleave is done on the GLOBAL side of the DMA: lane = (piece, channel)).  The epilogue applies G^T . G per accumulator element (all 36 positions of an (o, i) pair live in one lane) and writes
 // 9 partial sums; tile slices are added by conv_wgrad.hip's fixed-order reduction (deterministic).
-#include "shg_common.h"
+#include "conv_wgrad_p.h"
 
 typedef float ww_f4 __attribute__((ext_vector_type(4)));
-typedef int ww_i4 __attribute__((ext_vector_type(4)));
-
-void shg_launch_wgrad_reduce(const float* part, float* dw, long n, int nslice, hipStream_t s);      // conv_wgrad.hip
 
 struct WgWinoP {
     const float* x;      // [NB, I, H, W]
@@ -39,16 +36,9 @@ constexpr int BO = 64, BI = 32;
 constexpr int G_BYTES = BO * 32 * 16, X_BYTES = BI * 64 * 16, STAGE = G_BYTES + X_BYTES;     // 32 KiB + 32 KiB
 constexpr unsigned OOB = 0x80000000u;
 
-__device__ __forceinline__ ww_i4 make_srd(const void* base, unsigned bytes) {
-    const unsigned long long b = (unsigned long long)base;
-    ww_i4 s;
-    s[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    s[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
-    s[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    s[3] = 0x00020000;
-    return s;
-}
-__device__ __forceinline__ void dma16(unsigned lds_addr, unsigned voff, ww_i4 srd) {
+// Not shg_dma16: no scalar offset operand, and a "memory" clobber that shg_dma16 deliberately lacks -- it keeps the compiler's own loads and
+// LDS reads on their side of the request (the stages here are ordered by vmcnt(0) + barrier once per chunk, not by counted waits).
+__device__ __forceinline__ void dma16_ordered(unsigned lds_addr, unsigned voff, i32x4 srd) {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lds_addr), "v"(voff), "s"(srd) : "memory");
 }
 
@@ -96,21 +86,21 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_wino_kernel(const WgWinoP p
     auto issue = [&](int c, int buf) __attribute__((always_inline)) {
         const int cx = c % p.ctx, t = c / p.ctx, cy = t % p.cty, n = t / p.cty;
         const int gy0 = cy * 4 * TY, gx0 = cx * 4 * TX;        // window origin in the gradient; the input window starts at (gy0 - 1, gx0 - 4)
-        const ww_i4 srd_g = make_srd(p.g + (long)n * p.O * HW, (unsigned)((long)p.O * HW * 4));
-        const ww_i4 srd_x = make_srd(p.x + (long)n * p.I * HW, (unsigned)((long)p.I * HW * 4));
+        const i32x4 srd_g = shg_make_srd(p.g + (long)n * p.O * HW, (unsigned)((long)p.O * HW * 4));
+        const i32x4 srd_x = shg_make_srd(p.x + (long)n * p.I * HW, (unsigned)((long)p.I * HW * 4));
         const unsigned base = lds0 + buf * STAGE;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {                           // request k = wave + 8 j: channel group j, pieces 4 wave ..
             const int q = 4 * wave + tq, o = o0 + 16 * j + cc, gy = gy0 + (q >> LX), gx = gx0 + (q & (TX - 1)) * 4;
             const bool ok = (q >> LX) < 4 * TY && o < p.O && gy < p.H && gx < p.W;
-            dma16(base + (wave + 8 * j) * 1024, ok ? (unsigned)((o * HW + gy * p.W + gx) * 4) : OOB, srd_g);
+            dma16_ordered(base + (wave + 8 * j) * 1024, ok ? (unsigned)((o * HW + gy * p.W + gx) * 4) : OOB, srd_g);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {                           // request k = wave + 8 j: channel group j / 2, pieces 4 (wave + 8 (j & 1)) ..
             const int q = 4 * (wave + 8 * (j & 1)) + tq, row = q / XP, px = q - row * XP, i = i0 + 16 * (j >> 1) + cc;
             const int iy = gy0 - 1 + row, ix = gx0 - 4 + px * 4;
             const bool ok = row < 4 * TY + 2 && i < p.I && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-            dma16(base + G_BYTES + (wave + 8 * j) * 1024, ok ? (unsigned)((i * HW + iy * p.W + ix) * 4) : OOB, srd_x);
+            dma16_ordered(base + G_BYTES + (wave + 8 * j) * 1024, ok ? (unsigned)((i * HW + iy * p.W + ix) * 4) : OOB, srd_x);
         }
     };
 

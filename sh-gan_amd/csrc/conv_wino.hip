@@ -23,35 +23,11 @@
 // Epilogue: the 16 M_xi of an (o, t) pair live in 16 different waves -> they are exchanged through LDS in four passes
 // of 32 channels x 32 blocks; each thread then applies A^T . A, the fused layer tail (demodulation coefficient, noise,
 // bias, lrelu_agc, skip) and stores two pixels at a time (128-byte row segments per 16 lanes).
-#include "shg_common.h"
+#include "wino_common.h"
 #include <stdlib.h>
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __attribute__((aligned(16))) float shg_wino_zeros[64];   // zero source for LDS-DMA lanes that fall into padding
-
-struct WinoParams {
-    const float* x;          // [NB, I, H, W]
-    const float* wu;         // transformed weights [OP/64][nchunk][16][64 lanes][KC]
-    float* y;                // [NB, O, H, W]
-    const float* in_scale;   // [NB, I] or null
-    const float* out_scale;  // [NB, O] or null
-    const float* bias;       // [O] or null
-    const float* noise;      // see noise_mode
-    const float* residual;   // like y, added after the activation
-    int NB, I, O, OP, H, W;
-    int tiles_x, tiles_y;    // tiles per image (8 x 32 or 16 x 16 pixels)
-    int n_ttiles, n_otiles, nchunk;
-    int cps;                 // chunks per K slice (= nchunk when the launch is not split); slice = blockIdx.y
-    long part_stride;        // floats between the slices' partial outputs (0: y itself)
-    int noise_mode;          // 0 none, 1 [H,W], 2 [NB,H,W]
-    float noise_strength;
-    int act;
-    float alpha, gain, clamp;
-};
+__device__ __attribute__((aligned(16))) float shg_wino_zeros[64];   // zero source for LDS-DMA lanes that fall into padding (wino_common.h: why one per file)
 
 namespace wino {
 // K chunk (input channels per barrier).  The weights never touch LDS (each wave keeps its own position's slice in
@@ -75,13 +51,6 @@ constexpr int NXF = KC;                  // waves 0..KC-1 transform one channel 
 static_assert(2 * V_SZ >= 16 * 32 * 32, "epilogue exchange buffer lives in the V region");
 }   // namespace wino
 
-__device__ __forceinline__ int wino_xcd_remap(int bid, int total) {
-    const int q = total >> 3, r = total & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + idx;
-}
-
 template <int TY, int TX>
 __global__ __launch_bounds__(1024) void conv_wino_kernel(const WinoParams p) {
     using namespace wino;
@@ -98,7 +67,7 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(const WinoParams p) {
     const int l31 = lane & 31, half = lane >> 5;
 
     const int nwork = p.n_ttiles * p.n_otiles;
-    const int work = wino_xcd_remap(blockIdx.x, nwork);
+    const int work = shg_xcd_remap(blockIdx.x, nwork);
     const int otile = work / p.n_ttiles;
     const int ttile = work - otile * p.n_ttiles;
     const int txb = ttile % p.tiles_x;
@@ -324,9 +293,7 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(const WinoParams p) {
                 f32x2 out;
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) {
-                    float v = yv[i][jj] * osc[ob] + nzv[tb][i][jj] * p.noise_strength + bsv[ob];
-                    v = p.act ? shg_lrelu_agc(v, p.alpha, p.gain, p.clamp) : v * p.gain;
-                    out[jj] = v + rs[jj];
+                    out[jj] = shg_conv_tail(yv[i][jj], osc[ob], nzv[tb][i][jj] * p.noise_strength, bsv[ob], p.act, p.alpha, p.gain, p.clamp) + rs[jj];
                 }
                 *reinterpret_cast<f32x2*>(p.y + blockIdx.y * p.part_stride + base + pix) = out;      // W % 4 == 0, ox even: aligned, both pixels inside
             }
@@ -394,7 +361,7 @@ extern "C" int shg_conv_weight_prep_wino_f32(const float* w, const float* wscale
 // input channels; 512-channel layers at 16^2 / 32^2 are 64-128 such pairs at batch 8 (32-64 at the path-length pass's batch 4): half
 // of the chip or less, and a launch takes the same 150 / 200 us at batch 2 and at batch 16.  With a workspace the channel chunks are cut
 // into `ks` slices (blockIdx.y), every slice writes its raw partial output, and this kernel sums them and applies the layer tail the
-// unsplit kernel applies in its store pass (same expression).
+// unsplit kernels apply in their store passes (the same function, shg_conv_tail: identical bits).
 __global__ __launch_bounds__(256) void wino_split_reduce_kernel(const float* part, float* y, int ks, long total, long plane, int O, const float* out_scale,
                                                                 const float* bias, const float* noise, int noise_mode, float noise_strength, int act,
                                                                 float alpha, float gain, float clamp, const float* residual) {
@@ -415,9 +382,7 @@ __global__ __launch_bounds__(256) void wino_split_reduce_kernel(const float* par
         f32x4 out;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float t = v[j] * osc + nz[j] * noise_strength + bs;
-            t = act ? shg_lrelu_agc(t, alpha, gain, clamp) : t * gain;
-            out[j] = t + rs[j];
+            out[j] = shg_conv_tail(v[j], osc, nz[j] * noise_strength, bs, act, alpha, gain, clamp) + rs[j];
         }
         *reinterpret_cast<f32x4*>(y + e) = out;
     }
@@ -451,8 +416,7 @@ extern "C" size_t shg_conv2d_wino_workspace_bytes(int NB, int I, int O, int OP, 
     if (NB < 1 || I < 1 || O < 1 || OP < 64 || H < 1 || W < 1) return 0;
     WinoParams p{};
     wino_plan(p, NB, I, OP, H, W);
-    const int ks = shg_wino_ksplit((long)p.n_ttiles * p.n_otiles, p.nchunk);
-    return ks > 1 ? (size_t)ks * NB * O * H * W * sizeof(float) : 0;
+    return shg_wino_split_bytes((long)p.n_ttiles * p.n_otiles, p.nchunk, (size_t)NB * O * H * W * sizeof(float));
 }
 
 extern "C" int shg_conv2d_wino_ws_f32(const float* x, const float* wu, float* y, int NB, int I, int O, int OP, int H, int W,
@@ -465,27 +429,11 @@ extern "C" int shg_conv2d_wino_ws_f32(const float* x, const float* wu, float* y,
     SHG_CHECK_ARG((long)NB * I * H * W < 2147483647L && (long)NB * O * H * W < 2147483647L, "conv2d_wino: tensor too large");
     SHG_CHECK_ARG(I <= 128 * wino::KC, "conv2d_wino: too many input channels");
     SHG_CHECK_ARG(W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0, "conv2d_wino: needs W %% 4 == 0 and a 16-byte aligned x (use shg_conv2d_f32 otherwise)");
-    SHG_CHECK_ARG(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(residual)) & 7) == 0,
-                  "conv2d_wino: y / noise / residual must be 8-byte aligned");
-    WinoParams p{};
-    p.x = x; p.wu = wu; p.y = y; p.in_scale = in_scale; p.out_scale = out_scale; p.bias = bias;
-    p.noise = noise_mode ? noise : nullptr; p.residual = residual;
-    p.NB = NB; p.I = I; p.O = O; p.OP = OP; p.H = H; p.W = W;
+    SHG_CHECK_ARG(((shg_addr(y) | shg_addr(noise) | shg_addr(residual)) & 7) == 0, "conv2d_wino: y / noise / residual must be 8-byte aligned");
+    WinoParams p = shg_wino_params(x, wu, y, NB, I, O, OP, H, W, in_scale, out_scale, bias, noise, noise_mode, noise_strength, act, alpha, gain, clamp, residual);
     wino_plan(p, NB, I, OP, H, W);
-    p.noise_mode = noise ? noise_mode : 0; p.noise_strength = noise_strength;
-    p.act = act; p.alpha = alpha; p.gain = gain; p.clamp = clamp;
-    // K split: only with scratch for it, 16-byte aligned operands of the reduction (its loads are float4)
-    int ks = workspace ? shg_wino_ksplit((long)p.n_ttiles * p.n_otiles, p.nchunk) : 1;
-    const size_t out_bytes = (size_t)NB * O * H * W * sizeof(float);
-    while (ks > 1 && (size_t)ks * out_bytes > ws_bytes) ks /= 2;
-    if (((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(residual) | reinterpret_cast<uintptr_t>(workspace)) & 15) != 0) ks = 1;
-    p.cps = shg_cdiv(p.nchunk, ks);
-    ks = shg_cdiv(p.nchunk, p.cps);
-    p.part_stride = 0;
-    if (ks > 1) {                             // slices write raw sums; the tail moves to the reduction
-        p.y = (float*)workspace; p.part_stride = (long)NB * O * H * W;
-        p.out_scale = nullptr; p.bias = nullptr; p.noise = nullptr; p.noise_mode = 0; p.residual = nullptr; p.act = 0; p.gain = 1.f;
-    }
+    // K split: the kernel takes 8-byte aligned operands, the reduction's loads are float4 -- split only when all of them are 16-byte aligned
+    const int ks = shg_wino_split(p, workspace, ws_bytes, shg_addr(y) | shg_addr(noise) | shg_addr(residual) | shg_addr(workspace));
     const bool wide = W >= 32;
     const dim3 grid(p.n_ttiles * p.n_otiles, ks);
     if (wide) hipLaunchKernelGGL((conv_wino_kernel<4, 16>), grid, dim3(wino::NT), 0, (hipStream_t)stream, p);

@@ -22,34 +22,11 @@
 // Epilogue: the 36 M_xi of an (o, t) pair live in different waves -> exchanged through LDS in four passes of 16 channels x
 // 32 blocks; each thread applies A^T . A, the fused layer tail (demodulation coefficient, noise, bias, lrelu_agc, skip) and
 // stores its 4x4 pixels as four 16-byte rows.
-#include "shg_common.h"
+#include "wino_common.h"
 #include <stdlib.h>
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __attribute__((aligned(16))) float shg_wino4_zeros[64];
-
-struct Wino4Params {
-    const float* x;          // [NB, I, H, W]
-    const float* wu;         // transformed weights [OP/64][nchunk][4 k-steps][72 units][64 lanes]
-    float* y;                // [NB, O, H, W]
-    const float* in_scale;   // [NB, I] or null
-    const float* out_scale;  // [NB, O] or null
-    const float* bias;       // [O] or null
-    const float* noise;      // see noise_mode
-    const float* residual;   // like y, added after the activation
-    int NB, I, O, OP, H, W;
-    int tiles_x, tiles_y;    // tiles per image
-    int n_ttiles, n_otiles, nchunk;
-    int cps;                 // chunks per K slice (= nchunk when the launch is not split: conv_wino.hip, K-split); slice = blockIdx.y
-    long part_stride;        // floats between the slices' partial outputs (0: y itself)
-    int noise_mode;          // 0 none, 1 [H,W], 2 [NB,H,W]
-    float noise_strength;
-    int act;
-    float alpha, gain, clamp;
-};
+__device__ __attribute__((aligned(16))) float shg_wino4_zeros[64];   // zero source for padded DMA lanes and absent tail operands (wino_common.h: why one per file)
 
 namespace wino4 {
 constexpr int KC = 8, BO = 64, BT = 32, NPOS = 36, NW = 8, NT = NW * 64, NUNIT = 2 * NPOS;    // unit = (position, 32-channel block)
@@ -65,13 +42,6 @@ struct Tile {
 };
 static_assert(2 * V_SZ >= NPOS * 16 * 32, "epilogue exchange buffer lives in the V region");
 }   // namespace wino4
-
-__device__ __forceinline__ int wino4_xcd_remap(int bid, int total) {
-    const int q = total >> 3, r = total & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + idx;
-}
 
 // 1-D input transform of F(4,3): B^T d, B^T = [[4,0,-5,0,1,0],[0,-4,-4,1,1,0],[0,4,-4,-1,1,0],[0,-2,-1,2,1,0],[0,2,-1,-2,1,0],[0,4,0,-5,0,1]]
 template <class T>
@@ -92,7 +62,7 @@ __device__ __forceinline__ void wino4_at(const float (&m)[6], float (&o)[4]) {
 }
 
 template <int TY, int TX>
-__global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p) {
+__global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) {
     using namespace wino4;
     using T = Tile<TY, TX>;
     constexpr int PW = T::PW, PW4 = T::PW4, PATCH4 = T::PATCH4, RP = T::RP, R_SZ = T::R_SZ, NPIECE = T::NPIECE;
@@ -104,7 +74,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
     const int l31 = lane & 31, half = lane >> 5;
 
     const int nwork = p.n_ttiles * p.n_otiles;
-    const int work = wino4_xcd_remap(blockIdx.x, nwork);
+    const int work = shg_xcd_remap(blockIdx.x, nwork);
     const int otile = work / p.n_ttiles;
     const int ttile = work - otile * p.n_ttiles;
     const int txb = ttile % p.tiles_x;
@@ -374,9 +344,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4Params p)
                 wino4_at(col, a4);
     #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    float v = a4[i] * t.osc + nz[i][k] * p.noise_strength + t.bs;
-                    v = p.act ? shg_lrelu_agc(v, p.alpha, p.gain, p.clamp) : v * p.gain;
-                    out[i][k] = v + t.rs[i][k];
+                    out[i][k] = shg_conv_tail(a4[i], t.osc, nz[i][k] * p.noise_strength, t.bs, p.act, p.alpha, p.gain, p.clamp) + t.rs[i][k];
                 }
             }
             if (pass < 3) tail_load(pass + 1, t);                     // ahead of this pass's stores
@@ -478,12 +446,7 @@ extern "C" int shg_conv2d_wino4_supported(int NB, int I, int O, int H, int W) {
 }
 
 // y = act(out_scale[n,o] * conv3x3_same(x * in_scale[n,i], w) + noise*noise_strength + bias[o]) + residual, stride 1, pad 1.
-int shg_wino_ksplit(long tiles, int nchunk);                   // conv_wino.hip
-void shg_launch_wino_split_reduce(const float* part, float* y, int ks, int NB, int O, int H, int W, const float* out_scale, const float* bias,
-                                  const float* noise, int noise_mode, float noise_strength, int act, float alpha, float gain, float clamp,
-                                  const float* residual, hipStream_t s);
-
-static int wino4_plan(Wino4Params& p, int NB, int I, int OP, int H, int W) {
+static int wino4_plan(WinoParams& p, int NB, int I, int OP, int H, int W) {
     // tile shape: the same 32 blocks as 16 x 32 pixels, 8 x 64 for W >= 128 or 4 x 128 for W >= 256.  The 8 x 64 window has the
     // same area as the 16 x 32 one (10 x 72 against 18 x 40 floats per channel), the 4 x 128 one a fourth piece per channel
     // (6 x 136), but every output row piece is 256 / 512 contiguous bytes instead of 128, which is what the store path wants
@@ -497,10 +460,9 @@ static int wino4_plan(Wino4Params& p, int NB, int I, int OP, int H, int W) {
 // bytes of scratch with which shg_conv2d_wino4_ws_f32 splits this problem along its input channels (0: it will not; see conv_wino.hip)
 extern "C" size_t shg_conv2d_wino4_workspace_bytes(int NB, int I, int O, int OP, int H, int W) {
     if (NB < 1 || I < 1 || O < 1 || OP < 64 || H < 1 || W < 1) return 0;
-    Wino4Params p{};
+    WinoParams p{};
     wino4_plan(p, NB, I, OP, H, W);
-    const int ks = shg_wino_ksplit((long)p.n_ttiles * p.n_otiles, p.nchunk);
-    return ks > 1 ? (size_t)ks * NB * O * H * W * sizeof(float) : 0;
+    return shg_wino_split_bytes((long)p.n_ttiles * p.n_otiles, p.nchunk, (size_t)NB * O * H * W * sizeof(float));
 }
 
 extern "C" int shg_conv2d_wino4_ws_f32(const float* x, const float* wu, float* y, int NB, int I, int O, int OP, int H, int W,
@@ -511,25 +473,11 @@ extern "C" int shg_conv2d_wino4_ws_f32(const float* x, const float* wu, float* y
     SHG_CHECK_ARG(shg_conv2d_wino4_supported(NB, I, O, H, W), "conv2d_wino4: unsupported geometry (use shg_conv2d_wino_f32)");
     SHG_CHECK_ARG(OP % 64 == 0 && OP >= O, "conv2d_wino4: OP must be a multiple of 64 and >= O");
     SHG_CHECK_ARG((long)NB * I * H * W < 2147483647L && (long)NB * O * H * W < 2147483647L, "conv2d_wino4: tensor too large");
-    SHG_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(noise) |
-                    reinterpret_cast<uintptr_t>(residual)) & 15) == 0, "conv2d_wino4: x / y / noise / residual must be 16-byte aligned");
-    Wino4Params p{};
-    p.x = x; p.wu = wu; p.y = y; p.in_scale = in_scale; p.out_scale = out_scale; p.bias = bias;
-    p.noise = noise_mode ? noise : nullptr; p.residual = residual;
-    p.NB = NB; p.I = I; p.O = O; p.OP = OP; p.H = H; p.W = W;
+    SHG_CHECK_ARG(((shg_addr(x) | shg_addr(y) | shg_addr(noise) | shg_addr(residual)) & 15) == 0, "conv2d_wino4: x / y / noise / residual must be 16-byte aligned");
+    WinoParams p = shg_wino_params(x, wu, y, NB, I, O, OP, H, W, in_scale, out_scale, bias, noise, noise_mode, noise_strength, act, alpha, gain, clamp, residual);
     const int shape = wino4_plan(p, NB, I, OP, H, W);
-    p.noise_mode = noise ? noise_mode : 0; p.noise_strength = noise_strength;
-    p.act = act; p.alpha = alpha; p.gain = gain; p.clamp = clamp;
-    int ks = (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0) ? shg_wino_ksplit((long)p.n_ttiles * p.n_otiles, p.nchunk) : 1;
-    const size_t out_bytes = (size_t)NB * O * H * W * sizeof(float);
-    while (ks > 1 && (size_t)ks * out_bytes > ws_bytes) ks /= 2;
-    p.cps = shg_cdiv(p.nchunk, ks);
-    ks = shg_cdiv(p.nchunk, p.cps);
-    p.part_stride = 0;
-    if (ks > 1) {                             // slices write raw sums; the tail moves to the reduction
-        p.y = (float*)workspace; p.part_stride = (long)NB * O * H * W;
-        p.out_scale = nullptr; p.bias = nullptr; p.noise = nullptr; p.noise_mode = 0; p.residual = nullptr; p.act = 0; p.gain = 1.f;
-    }
+    // K split: the tail operands are 16-byte aligned already (checked above), which leaves the workspace
+    const int ks = shg_wino_split(p, workspace, ws_bytes, shg_addr(workspace));
     const dim3 grid(p.n_ttiles * p.n_otiles, ks);
     if (shape == 2) hipLaunchKernelGGL((conv_wino4_kernel<1, 32>), grid, dim3(wino4::NT), 0, (hipStream_t)stream, p);
     else if (shape == 1) hipLaunchKernelGGL((conv_wino4_kernel<2, 16>), grid, dim3(wino4::NT), 0, (hipStream_t)stream, p);

@@ -34,15 +34,11 @@
 //   scheme DA: the P_ee term as F(3x3,2x2) -> raw partial sums in y;
 //   scheme DB: the other three terms of a 2x2 output block with 16 multiplies, added to the partial sums, then the
 //              fused layer tail (bias, lrelu_agc, gain, skip).  Two launches (DB consumes DA's output).
-#include "shg_common.h"
+#include "wino_common.h"
 #include <stdlib.h>
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __attribute__((aligned(16))) float shg_poly_zeros[64];   // zero source for LDS-DMA lanes that fall into padding
+__device__ __attribute__((aligned(16))) float shg_poly_zeros[64];   // zero source for LDS-DMA lanes that fall into padding (wino_common.h: why one per file)
 
 struct PolySub {            // one scheme's share of a launch
     const float* wu;         // transformed weights [OP/64][nchunk][16][64 lanes][KC]
@@ -105,13 +101,6 @@ struct Geo {
 };
 }   // namespace poly
 
-__device__ __forceinline__ int poly_xcd_remap(int bid, int total) {
-    const int q = total >> 3, r = total & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + idx;
-}
-
 template <int SCHEME, int TY, int TX, int NBX>
 __device__ __forceinline__ void poly_body(const PolyParams& p, const PolySub& q, const int bid, float* __restrict__ Vl,
                                           float* __restrict__ Rl) {
@@ -127,7 +116,7 @@ __device__ __forceinline__ void poly_body(const PolyParams& p, const PolySub& q,
     const int l31 = lane & 31, half = lane >> 5;
 
     const int nwork = q.n_ttiles * p.n_otiles;
-    const int work = poly_xcd_remap(bid, nwork);
+    const int work = shg_xcd_remap(bid, nwork);
     const int otile = work / q.n_ttiles;
     const int ttile = work - otile * q.n_ttiles;
     const int txb = ttile % q.tiles_x;
@@ -656,11 +645,6 @@ extern "C" int shg_conv2d_up_poly_supported(int NB, int I, int O, int H, int W) 
 // Phase planes of the stride-2 transposed 3x3 convolution of x * in_scale[n,i]: y [4][NB,O,H+1,W+1] (same contract as
 // shg_conv2d_f32 mode 2 / out_mode 1 without epilogue operands).  wt = GEMM-layout weights of shg_conv_weight_prep_f32
 // (for the strips), wu_a / wu_b from shg_conv_weight_prep_up_poly_f32.
-int shg_wino_ksplit(long tiles, int nchunk);                   // conv_wino.hip
-void shg_launch_wino_split_reduce(const float* part, float* y, int ks, int NB, int O, int H, int W, const float* out_scale, const float* bias,
-                                  const float* noise, int noise_mode, float noise_strength, int act, float alpha, float gain, float clamp,
-                                  const float* residual, hipStream_t s);
-
 // tiling of an up launch; returns the kernel variant: 0 narrow, 1 / 2 / 3 flat with 11 / 22 / 43 block columns, 4 wide, 5 rectangular 8 x 8
 static int up_poly_plan(PolyParams& p, int NB, int I, int OP, int H, int W) {
     p.n_otiles = OP / 64; p.nchunk = shg_cdiv(I, poly::KC);
@@ -691,8 +675,7 @@ extern "C" size_t shg_conv2d_up_poly_workspace_bytes(int NB, int I, int O, int O
     if (!shg_conv2d_up_poly_supported(NB, I, O, H, W) || OP < 64) return 0;
     PolyParams p{};
     up_poly_plan(p, NB, I, OP, H, W);
-    const int ks = shg_wino_ksplit((long)(p.a.n_ttiles + p.b.n_ttiles) * p.n_otiles, p.nchunk);
-    return ks > 1 ? (size_t)ks * 4 * NB * O * (H + 1) * (W + 1) * sizeof(float) : 0;
+    return shg_wino_split_bytes((long)(p.a.n_ttiles + p.b.n_ttiles) * p.n_otiles, p.nchunk, (size_t)4 * NB * O * (H + 1) * (W + 1) * sizeof(float));
 }
 
 extern "C" int shg_conv2d_up_poly_ws_f32(const float* x, const float* wt, const float* wu_a, const float* wu_b, float* y, int NB, int I,
@@ -708,15 +691,9 @@ extern "C" int shg_conv2d_up_poly_ws_f32(const float* x, const float* wt, const 
     p.NB = NB; p.I = I; p.O = O; p.OP = OP; p.H = H; p.W = W;
     p.a.wu = wu_a; p.b.wu = wu_b; p.wt = wt;
     const int variant = up_poly_plan(p, NB, I, OP, H, W);
-    // K split (small grids): slices write partial planes, one small launch adds them
-    const size_t out_bytes = (size_t)4 * NB * O * (H + 1) * (W + 1) * sizeof(float);
-    int ks = (workspace && ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(y)) & 15) == 0)
-                 ? shg_wino_ksplit((long)(p.a.n_ttiles + p.b.n_ttiles) * p.n_otiles, p.nchunk) : 1;
-    while (ks > 1 && (size_t)ks * out_bytes > ws_bytes) ks /= 2;
-    p.cps = shg_cdiv(p.nchunk, ks);
-    ks = shg_cdiv(p.nchunk, p.cps);
-    p.part_stride = 0;
-    if (ks > 1) { p.y = (float*)workspace; p.part_stride = (long)(out_bytes / sizeof(float)); }
+    // K split (small grids): slices write partial planes, one small launch adds them (no tail operands: workspace and y are its float4 accesses)
+    const int ks = shg_wino_split((long)(p.a.n_ttiles + p.b.n_ttiles) * p.n_otiles, p.nchunk, (size_t)4 * NB * O * (H + 1) * (W + 1) * sizeof(float),
+                                  workspace, ws_bytes, shg_addr(workspace) | shg_addr(y), &p.y, &p.cps, &p.part_stride);
     const dim3 grid((p.a.n_ttiles + p.b.n_ttiles) * p.n_otiles + shg_cdiv(p.n_strip_tiles, 4), ks);
     if (variant == 0) hipLaunchKernelGGL((conv_poly_up_kernel<8, 8, 0, 8, 8>), grid, dim3(poly::NT), 0, s, p);
     else if (variant == 1) hipLaunchKernelGGL((conv_poly_up_kernel<1, 64, 11, 4, 16>), grid, dim3(poly::NT), 0, s, p);

@@ -10,15 +10,13 @@
 // The epilogue writes at a channel offset of the Mixed block's concat buffer (no concat pass).  Several independent convolutions
 // (the branches of a Mixed block at one depth) are one grouped launch; a group may split K over `splitk` workgroups, whose fp32
 // partial sums go to the workspace and are added in a fixed order (split index ascending) by a second, grouped launch.
-#include "shg_common.h"
+#include "shg_device.h"
 #include "../../include/shgan_hip.h"
 
 #define INC_BM 64        // output channels per workgroup
 #define INC_BN 64        // output pixels per workgroup
 #define INC_BK 16        // K per stage
 #define INC_OUT 299      // the detector's input resolution
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct IncConvArgs {
     shg_inc_conv_desc g[SHG_INC_MAX_GROUPS];

@@ -666,6 +666,12 @@ MODE_SAME, MODE_DOWN2, MODE_UP2T = 0, 1, 2
 _CONV_CLASS = {MODE_SAME: 'conv_mfma_s1', MODE_DOWN2: 'conv_mfma_s2', MODE_UP2T: 'conv_mfma_up'}
 
 
+def _wino_workspace(L, bytes_fn, *shape):
+    """(scratch, bytes) with which a Winograd launch of `shape` splits along its input channels (small grids); (None, 0): it does not."""
+    ws_bytes = int(bytes_fn(*shape)) if WINO_SPLIT else 0
+    return (L.new((ws_bytes // 4,)) if ws_bytes else None), ws_bytes
+
+
 def conv2d(x, pw, mode=MODE_SAME, pad=0, in_scale=None, out_scale=None, bias=None, noise=None, noise_strength=1.0,
            act=False, gain=1.0, alpha=0.2, act_gain=SQRT2, clamp=256.0, residual=None, planar=False):
     """x [NB, I, H, W] (for grouped weights NB = N*groups slots) -> y [NB, O, OH, OW].
@@ -701,16 +707,14 @@ def conv2d(x, pw, mode=MODE_SAME, pad=0, in_scale=None, out_scale=None, bias=Non
         if WINO4 and h >= WINO4_MIN and tail_al % 16 == 0 and lib.shg_conv2d_wino4_supported(nb, i, pw.o, h, w):
             wu = pw.wino4()
             executed = 2.0 * nb * pw.o * i * 36.0 * ((h + 3) // 4) * ((w + 3) // 4)
-            ws_bytes = int(lib.shg_conv2d_wino4_workspace_bytes(nb, i, pw.o, pw.op, h, w)) if WINO_SPLIT else 0
-            ws = L.new((ws_bytes // 4,)) if ws_bytes else None
+            ws, ws_bytes = _wino_workspace(L, lib.shg_conv2d_wino4_workspace_bytes, nb, i, pw.o, pw.op, h, w)
             with _timed(L, 'conv_wino4', direct, executed):
                 check(lib.shg_conv2d_wino4_ws_f32(
                     _ptr(x), _ptr(wu), _ptr(y), nb, i, pw.o, pw.op, h, w, _ptr(in_scale), _ptr(out_scale), _ptr(bias), _ptr(noise),
                     nmode, float(noise_strength), a, al, g, cl, _ptr(residual), _ptr(ws), ws_bytes, L.stream()), 'conv2d_wino4')
             return y
         wu = pw.wino()
-        ws_bytes = int(lib.shg_conv2d_wino_workspace_bytes(nb, i, pw.o, pw.op, h, w)) if WINO_SPLIT else 0       # (small grids: split along the input channels)
-        ws = L.new((ws_bytes // 4,)) if ws_bytes else None
+        ws, ws_bytes = _wino_workspace(L, lib.shg_conv2d_wino_workspace_bytes, nb, i, pw.o, pw.op, h, w)
         with _timed(L, 'conv_wino', direct, direct * 16.0 / 36.0):
             check(lib.shg_conv2d_wino_ws_f32(
                 _ptr(x), _ptr(wu), _ptr(y), nb, i, pw.o, pw.op, h, w, _ptr(in_scale), _ptr(out_scale), _ptr(bias), _ptr(noise), nmode,
@@ -722,8 +726,7 @@ def conv2d(x, pw, mode=MODE_SAME, pad=0, in_scale=None, out_scale=None, bias=Non
         wa, wb = pw.up_poly()
         nba, nbb = ((h + 1 + 2) // 3) * ((w + 1 + 2) // 3), (h // 2) * (w // 2)
         executed = 2.0 * nb * pw.o * i * (16.0 * (nba + nbb) + h + w)
-        ws_bytes = int(lib.shg_conv2d_up_poly_workspace_bytes(nb, i, pw.o, pw.op, h, w)) if WINO_SPLIT else 0
-        ws = L.new((ws_bytes // 4,)) if ws_bytes else None
+        ws, ws_bytes = _wino_workspace(L, lib.shg_conv2d_up_poly_workspace_bytes, nb, i, pw.o, pw.op, h, w)
         with _timed(L, 'conv_poly_up', 2.0 * nb * pw.o * i * 9 * h * w, executed):
             check(lib.shg_conv2d_up_poly_ws_f32(_ptr(x), _ptr(pw.wt), _ptr(wa), _ptr(wb), _ptr(y), nb, i, pw.o, pw.op, h, w,
                                                 _ptr(in_scale), _ptr(ws), ws_bytes, L.stream()), 'conv2d_up_poly')
