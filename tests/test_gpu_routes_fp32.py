@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
 SQRT2 = 2 ** 0.5
-TOL_CONV = 2e-5          # convolutions and their weight gradients (tests/test_gpu_wgrad_wino.py, tools/fuzz_ops.py)
+TOL_CONV = 2e-5          # convolutions and their weight gradients (tests/test_gpu_wgrad_wino.py, the ops family of tests/fuzz_cases.py)
 TOL_PW = 1e-5            # elementwise / FIR passes
 
 
@@ -179,7 +179,7 @@ def fir_strided(dtype, n=2, c=3, h=9, w=11):
     xin = x64.to(dtype)
     ref = _orc().upfirdn2d(xin.double().transpose(2, 3), f.double(), up=2, down=1, padding=[1, 2, 0, 1], gain=4.0)
     xd, fd = xin.to(DEV).transpose(2, 3), dev(f)                     # H and W strides exchanged: read in place
-    tol = {torch.float64: 1e-12, torch.float32: 3e-6, torch.float16: 2e-3}[dtype]       # (tools/fuzz_round5b.py)
+    tol = {torch.float64: 1e-12, torch.float32: 3e-6, torch.float16: 2e-3}[dtype]       # (the round5b family of tests/fuzz_cases.py)
     return (lambda: kk.upfirdn2d_strided(xd, fd, 2, 2, 1, 1, 1, 2, 0, 1, False, 4.0)), ref, tol
 
 
