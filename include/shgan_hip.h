@@ -335,6 +335,27 @@ int shg_inception_conv_f32(const shg_inc_conv_desc* groups, int G, int B, void* 
 int shg_inception_pool_f32(const float* x, float* y, int B, int C, int H, int W, int mode, int stride, int pad, int y_ctot, int y_coff, void* stream);
 int shg_inception_mean_f32(const float* x, float* y, int B, int C, int HW, void* stream);
 
+/* ---- LPIPS, AlexNet backbone: `lpips.LPIPS(net='alex')` as lib/evaluator/eva_lpips.py:39-52 calls it (sh-gan_amd/lpips.py drives it;
+ * csrc/lpips.hip).  conv2..conv5 and the max pools run on the detector's convolution and pool entry points above.
+ * Conv1 weight prep: w [64,3,11,11], bias [64] -> wp [SHG_LPIPS_CONV1_WP_ELEMS] floats ([368][64], k = (ky*11 + kx)*3 + c, zero
+ *   rows beyond K = 363), bp [64]; once per network.
+ * Conv1: x [B,3,H,W] -> y [B,64,OH,OW] = relu(conv2d(s(v), w, stride 4, pad 2) + bias), OH = (H + 4 - 11) / 4 + 1, H and W >= 7, on
+ *   exact-fp32 MFMA.  v = lut[x] when lut [256] is given (x uint8), else ((x*scale + bias) - 0.5) * 2 with every step rounded to float32
+ *   (x float32; x*scale + bias is the evaluator batch's [0, 1] form, the rest eva_lpips.py:39-40); s(v) = (v - shift[c]) * float32(1 /
+ *   scaling[c]), the LPIPS scaling layer, on in-bounds taps only (the zero padding is of the scaled image).  shift, scaling: HOST
+ *   arrays of 3 floats; wp 16-byte aligned.
+ * Head, for one tap: fp, fg [B,C,h,w] (features of the B preds and the B gts), w [C] -> out[b] += mean over pixels of
+ *   sum_c w[c] (fp/(sqrt(sum_c fp^2) + 1e-10) - fg/(sqrt(sum_c fg^2) + 1e-10))^2, out float64 [B].  scratch: the number of bytes the
+ *   scratch query returns (0 for invalid arguments): per-tile float64 partial sums, added per image in a fixed order -- no atomics,
+ *   the same bits run to run and in any batch. */
+#define SHG_LPIPS_CONV1_WP_ELEMS (368 * 64)
+int shg_lpips_conv1_weight_prep_f32(const float* w, const float* bias, float* wp, float* bp, void* stream);
+int shg_lpips_conv1_f32(const void* x, const float* lut, float scale, float bias, const float* shift, const float* scaling, const float* wp,
+                        const float* bp, float* y, int B, int H, int W, void* stream);
+size_t shg_lpips_head_scratch_bytes(int B, int h, int w);
+int shg_lpips_head_f32(const float* fp, const float* fg, const float* w, int B, int C, int h, int wd, void* scratch, size_t scratch_bytes,
+                       double* out, void* stream);
+
 /* ---- evaluation image metrics (lib/evaluator/eva_psnr.py, for_dataset=None, rgb_range=1; eva_ssim._ssim, size_average=False).
  * pred, gt [B,C,H,W] contiguous; each operand is uint8 when its lut [256] (value of every code: float64 for pred, float32 for gt) is
  * given, float32 otherwise; the element value is then v*scale + bias (the evaluator's fake/255 and (real+1)/2).  As in the reference's

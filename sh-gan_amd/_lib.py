@@ -120,6 +120,10 @@ _SIGS = {
     'shg_inception_conv_f32': [ctypes.POINTER(IncConv), c_i, c_i, c_fp, ctypes.c_size_t, c_fp],
     'shg_inception_pool_f32': [c_fp, c_fp] + [c_i] * 9 + [c_fp],
     'shg_inception_mean_f32': [c_fp, c_fp, c_i, c_i, c_i, c_fp],
+    'shg_lpips_conv1_weight_prep_f32': [c_fp, c_fp, c_fp, c_fp, c_fp],
+    'shg_lpips_conv1_f32': [c_fp, c_fp, c_f, c_f, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
+    'shg_lpips_head_scratch_bytes': [c_i] * 3,
+    'shg_lpips_head_f32': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, ctypes.c_size_t, c_fp, c_fp],
     'shg_image_metrics_scratch_bytes': [c_i] * 4,
     'shg_image_metrics': [c_fp, c_fp, c_f, c_f, c_fp, c_fp, c_f, c_f] + [c_i] * 6 + [c_fp, ctypes.c_size_t, c_fp, c_fp, c_fp],
     'shg_resize_bicubic_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
@@ -177,6 +181,7 @@ def get_lib():
     lib.shg_conv2d_wgrad_wino_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_conv2d_wgrad_f16_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_image_metrics_scratch_bytes.restype = ctypes.c_size_t
+    lib.shg_lpips_head_scratch_bytes.restype = ctypes.c_size_t
     lib.shg_inception_conv_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_inception_packed_weight_elems.restype = c_l
     lib.shg_conv2d_f16_packed_weight_elems.restype = c_l

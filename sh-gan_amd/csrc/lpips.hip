@@ -1,0 +1,246 @@
+// LPIPS with the AlexNet backbone (`lpips.LPIPS(net='alex')`, version 0.1, as the reference's lib/evaluator/eva_lpips.py:39-52 calls it):
+// the two pieces the FID detector's kernels (inception.hip) do not cover.  conv2..conv5 and the two max pools of AlexNet run on
+// shg_inception_conv_f32 / shg_inception_pool_f32; sh-gan_amd/lpips.py drives the whole network.
+//
+// shg_lpips_conv1_f32: operand load + eva_lpips.py's `(x - 0.5) * 2` + the scaling layer + conv 3 -> 64, 11 x 11, stride 4, pad 2 + bias +
+//   ReLU in one launch.  Implicit GEMM on the exact-fp32 matrix cores (v_mfma_f32_32x32x2_f32), in the detector's layout: rows = the 64
+//   output channels (A = packed weight [368][64], K = 363 in tap-major order k = (ky*11 + kx)*3 + c, zero rows up to 368), columns =
+//   output pixels m = (b, oy, ox) gathered on the fly; one workgroup = 64 channels x 64 pixels, four waves of 32 x 32, K in 23 steps of
+//   16 through two LDS stages.  The scaling layer `(v - shift_c) / scale_c` is applied to the in-bounds taps only -- the convolution's
+//   zero padding is of the SCALED image, so the shift cannot move into the bias.  The division is a multiplication by float32(1 /
+//   scale_c): at most one ulp of the operand away from the published float32 division.  uint8 operands take the whole per-channel map
+//   from a 3 x 256 table a workgroup builds in LDS.
+// shg_lpips_head_f32: for one tap, per pixel f^ = f / (sqrt(sum_c f^2) + 1e-10) of both images and d = sum_c w_c (f^_pred - f^_gt)^2;
+//   one lane per pixel, both channel sums float32 FMA chains in channel order (the second loop re-reads the wave's 64-pixel columns from
+//   cache: each map comes from memory once); a wave's 64 values are added in float64 by a fixed butterfly -> scratch[b][tile]; a second
+//   launch adds an image's tiles in a fixed order (float64) and adds the spatial mean to out[b].  No atomics: the same bits run to run
+//   and in any batch.  A pixel whose features are all zero gives 0 / (0 + 1e-10) = 0.
+#include "shg_device.h"
+#include "../../include/shgan_hip.h"
+
+#define LP_BM 64                        // output channels (all of conv1's)
+#define LP_BN 64                        // output pixels per workgroup
+#define LP_BK 16                        // K per stage
+#define LP_K 363                        // 3 * 11 * 11
+#define LP_KT ((LP_K + LP_BK - 1) / LP_BK)
+#define LP_KP (LP_KT * LP_BK)
+#define LP_HEAD_THREADS 256
+
+namespace {
+
+struct LpConv1Args {
+    const void* x;
+    const float* lut;                   // uint8 operands: value of every code after `(x - 0.5) * 2`; NULL: float32 elements
+    float scale, bias;                  // float32 operands: u = x*scale + bias (the evaluator batch's [0, 1] form), v = (u - 0.5) * 2
+    float shift[3], inv[3];             // scaling layer: (v - shift) * inv
+    const float* wp;
+    const float* bp;
+    float* y;
+    int B, H, W, OH, OW;
+};
+
+__device__ __forceinline__ float lp_scaled(float v, float shift, float inv) { return __fmul_rn(__fsub_rn(v, shift), inv); }
+
+template <bool U8>
+__global__ __launch_bounds__(256) void lp_conv1_kernel(const LpConv1Args a) {
+    __shared__ float Ws[2][LP_BK][LP_BM];
+    __shared__ float Xs[2][LP_BK][LP_BN];
+    __shared__ float lut3[U8 ? 3 * 256 : 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (U8) {
+        const float v = a.lut[tid];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) lut3[c * 256 + tid] = lp_scaled(v, a.shift[c], a.inv[c]);
+        __syncthreads();
+    }
+    const int OHW = a.OH * a.OW, M = a.B * OHW;
+    // staging roles: X rows kr0 + 4i (i < 4) of pixel px; W row wr, columns wc..wc+3
+    const int px = tid & 63, kr0 = tid >> 6;
+    const int wr = tid >> 4, wc = (tid & 15) * 4;
+    const int m = (int)blockIdx.x * LP_BN + px;
+    const bool mvalid = m < M;
+    int b = 0, oy = 0, ox = 0;
+    if (mvalid) {
+        b = m / OHW;
+        const int r = m - b * OHW;
+        oy = r / a.OW;
+        ox = r - oy * a.OW;
+    }
+    const int iy0 = oy * 4 - 2, ix0 = ox * 4 - 2;
+    const long HW = (long)a.H * a.W;
+    const long xb = (long)b * 3 * HW;
+    const float* wp = a.wp + wc;
+    const uint8_t* x8 = reinterpret_cast<const uint8_t*>(a.x);
+    const float* xf = reinterpret_cast<const float*>(a.x);
+
+    float xr[4];
+    float4 wreg;
+    auto load = [&](int kt) {
+        wreg = *reinterpret_cast<const float4*>(wp + (long)(kt * LP_BK + wr) * LP_BM);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = kt * LP_BK + kr0 + 4 * i;
+            xr[i] = 0.f;
+            if (mvalid && k < LP_K) {
+                const int tap = k / 3, c = k - tap * 3;
+                const int ky = tap / 11, kx = tap - ky * 11;
+                const int iy = iy0 + ky, ix = ix0 + kx;
+                if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) {
+                    const long idx = xb + (long)c * HW + (long)iy * a.W + ix;
+                    if (U8) {
+                        xr[i] = lut3[c * 256 + x8[idx]];
+                    } else {
+                        const float u = __fadd_rn(__fmul_rn(xf[idx], a.scale), a.bias);
+                        const float v = __fmul_rn(__fsub_rn(u, 0.5f), 2.f);
+                        const float sh = c == 0 ? a.shift[0] : (c == 1 ? a.shift[1] : a.shift[2]);
+                        const float iv = c == 0 ? a.inv[0] : (c == 1 ? a.inv[1] : a.inv[2]);
+                        xr[i] = lp_scaled(v, sh, iv);
+                    }
+                }
+            }
+        }
+    };
+
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;     // the wave's channel / pixel sub-tile
+    const int lk = lane >> 5, lj = lane & 31;
+    load(0);
+    int buf = 0;
+    for (int kt = 0; kt < LP_KT; ++kt) {
+        *reinterpret_cast<float4*>(&Ws[buf][wr][wc]) = wreg;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Xs[buf][kr0 + 4 * i][px] = xr[i];
+        __syncthreads();
+        if (kt + 1 < LP_KT) load(kt + 1);                      // next step's loads in flight under this step's MFMAs
+#pragma unroll
+        for (int kk = 0; kk < LP_BK; kk += 2) {
+            const float av = Ws[buf][kk + lk][wm + lj];
+            const float bv = Xs[buf][kk + lk][wn + lj];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+        }
+        buf ^= 1;
+    }
+
+    // D[i][j]: channel i = (r&3) + 8(r>>2) + 4(lane>>5), pixel j = lane&31
+    const int mo = (int)blockIdx.x * LP_BN + wn + lj;
+    if (mo >= M) return;
+    const int ob = wm + 4 * lk;
+    const int bo = mo / OHW, pix = mo - bo * OHW;
+    float* yb = a.y + (long)bo * LP_BM * OHW + pix;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int o = ob + (r & 3) + 8 * (r >> 2);
+        yb[(long)o * OHW] = fmaxf(acc[r] + a.bp[o], 0.f);
+    }
+}
+
+// w [64][3][11][11], b [64] -> wp [LP_KP][64] (k = (ky*11 + kx)*3 + c; zero rows beyond K), bp [64]
+__global__ __launch_bounds__(256) void lp_conv1_prep_kernel(const float* w, const float* bias, float* wp, float* bp) {
+    const int e = (int)blockIdx.x * 256 + threadIdx.x;
+    if (e < LP_BM) bp[e] = bias[e];
+    if (e >= LP_KP * LP_BM) return;
+    const int k = e / LP_BM, o = e - k * LP_BM;
+    float v = 0.f;
+    if (k < LP_K) {
+        const int tap = k / 3, c = k - tap * 3;
+        v = w[(o * 3 + c) * 121 + tap];
+    }
+    wp[e] = v;
+}
+
+__global__ __launch_bounds__(64) void lp_head_tile_kernel(const float* fp, const float* fg, const float* w, int C, int HW, double* part) {
+    const int lane = threadIdx.x, tile = blockIdx.x, b = blockIdx.y;
+    const int pix = tile * 64 + lane;
+    float d = 0.f;
+    if (pix < HW) {
+        const float* p = fp + (long)b * C * HW + pix;
+        const float* g = fg + (long)b * C * HW + pix;
+        float sp = 0.f, sg = 0.f;
+        for (int c = 0; c < C; ++c) {
+            const float u = p[(long)c * HW], v = g[(long)c * HW];
+            sp = fmaf(u, u, sp);
+            sg = fmaf(v, v, sg);
+        }
+        const float np = sqrtf(sp) + 1e-10f, ng = sqrtf(sg) + 1e-10f;
+        for (int c = 0; c < C; ++c) {
+            const float diff = __fsub_rn(p[(long)c * HW] / np, g[(long)c * HW] / ng);
+            d = fmaf(w[c], __fmul_rn(diff, diff), d);
+        }
+    }
+    double s = (double)d;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) part[(long)b * gridDim.x + tile] = s;
+}
+
+__global__ __launch_bounds__(LP_HEAD_THREADS) void lp_head_finish_kernel(const double* part, int tiles, double inv_hw, double* out) {
+    __shared__ double red[LP_HEAD_THREADS];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const double* p = part + (long)b * tiles;
+    double s = 0.0;
+    for (int i = t; i < tiles; i += LP_HEAD_THREADS) s += p[i];
+    red[t] = s;
+    __syncthreads();
+#pragma unroll
+    for (int k = LP_HEAD_THREADS / 2; k > 0; k >>= 1) {
+        if (t < k) red[t] += red[t + k];
+        __syncthreads();
+    }
+    if (t == 0) out[b] += red[0] * inv_hw;
+}
+
+}  // namespace
+
+extern "C" int shg_lpips_conv1_weight_prep_f32(const float* w, const float* bias, float* wp, float* bp, void* stream) {
+    SHG_CHECK_ARG(w && bias && wp && bp, "lpips_conv1_weight_prep: null pointer");
+    hipLaunchKernelGGL(lp_conv1_prep_kernel, dim3(shg_cdiv(LP_KP * LP_BM, 256)), dim3(256), 0, (hipStream_t)stream, w, bias, wp, bp);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}
+
+extern "C" int shg_lpips_conv1_f32(const void* x, const float* lut, float scale, float bias, const float* shift, const float* scaling,
+                                   const float* wp, const float* bp, float* y, int B, int H, int W, void* stream) {
+    SHG_CHECK_ARG(x && shift && scaling && wp && bp && y, "lpips_conv1: null pointer");
+    SHG_CHECK_ARG(((uintptr_t)wp & 15) == 0, "lpips_conv1: packed weight not 16-byte aligned");
+    SHG_CHECK_ARG(B >= 1 && H >= 7 && W >= 7 && H <= 65536 && W <= 65536, "lpips_conv1: bad geometry B %d %dx%d (B >= 1, H and W >= 7)", B, H, W);
+    SHG_CHECK_ARG(scaling[0] != 0.f && scaling[1] != 0.f && scaling[2] != 0.f, "lpips_conv1: a scaling-layer scale of 0");
+    LpConv1Args a;
+    a.x = x; a.lut = lut; a.scale = scale; a.bias = bias; a.wp = wp; a.bp = bp; a.y = y;
+    for (int c = 0; c < 3; ++c) {
+        a.shift[c] = shift[c];
+        a.inv[c] = (float)(1.0 / (double)scaling[c]);
+    }
+    a.B = B; a.H = H; a.W = W;
+    a.OH = (H + 4 - 11) / 4 + 1;
+    a.OW = (W + 4 - 11) / 4 + 1;
+    const long M = (long)B * a.OH * a.OW;
+    SHG_CHECK_ARG(M * LP_BM < (1L << 31), "lpips_conv1: tensor too large for 32-bit pixel indices");
+    const dim3 grid((unsigned)((M + LP_BN - 1) / LP_BN));
+    if (lut) hipLaunchKernelGGL((lp_conv1_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((lp_conv1_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}
+
+extern "C" size_t shg_lpips_head_scratch_bytes(int B, int h, int w) {
+    if (B < 1 || h < 1 || w < 1) return 0;
+    return (size_t)B * (size_t)(((long)h * w + 63) / 64) * sizeof(double);
+}
+
+extern "C" int shg_lpips_head_f32(const float* fp, const float* fg, const float* w, int B, int C, int h, int wd, void* scratch, size_t scratch_bytes,
+                                  double* out, void* stream) {
+    SHG_CHECK_ARG(fp && fg && w && scratch && out, "lpips_head: null pointer");
+    SHG_CHECK_ARG(B >= 1 && C >= 1 && h >= 1 && wd >= 1, "lpips_head: B, C, h, w must be >= 1");
+    const long HW = (long)h * wd, tiles = (HW + 63) / 64;
+    SHG_CHECK_ARG(HW < (1L << 31) && B <= 65535, "lpips_head: feature map or batch too large");
+    SHG_CHECK_ARG(scratch_bytes >= shg_lpips_head_scratch_bytes(B, h, wd), "lpips_head: scratch of %zu bytes is too small (%zu needed)", scratch_bytes,
+                  shg_lpips_head_scratch_bytes(B, h, wd));
+    double* part = reinterpret_cast<double*>(scratch);
+    hipLaunchKernelGGL(lp_head_tile_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(64), 0, (hipStream_t)stream, fp, fg, w, C, (int)HW, part);
+    SHG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(lp_head_finish_kernel, dim3(B), dim3(LP_HEAD_THREADS), 0, (hipStream_t)stream, part, (int)tiles, 1.0 / (double)HW, out);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}

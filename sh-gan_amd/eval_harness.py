@@ -371,11 +371,18 @@ class EvalLoop:
     ``fid_real=True`` adds the real side of the FID (eva_fid.py's ``compute_fid`` without its cache file): per batch, on the batch's own
     stream, ``feature_fn(real, input_range='pm1')`` (the detector maps [-1, 1] floats, or a loader's decoded uint8 pixels, as the
     reference's ``real*127.5 + 127.5``) into per-stream partial moments, padded duplicates weighing 0; ``gather`` all-reduces both sides
-    once each (``self.fid`` fake, ``self.fid_real`` real) and ``fid_value()`` gives the FID."""
+    once each (``self.fid`` fake, ``self.fid_real`` real) and ``fid_value()`` gives the FID.
+
+    ``lpips=net`` adds the fourth evaluator (eva_lpips.py): any callable ``lpips(pred_u8, real, out=slice)`` -- ``lpips.Lpips`` on the
+    device, a torch stand-in in the CPU tests -- that writes the batch's float64 values into ``out``.  Per batch, on the batch's own stream
+    after the composite, it fills this rank's NaN-initialised ``[n_local]`` buffer at the batch's shard position; ``gather`` carries the
+    column in the same all-gather as PSNR / SSIM and sets ``image_metrics['lpips']`` (mean over exactly ``n_items`` in dataset order) and
+    ``['lpips_per_image']`` -- with ``metrics=None`` and with ``keep_images=False`` too."""
 
     def __init__(self, G, device, resolution, n_items, rank=0, world=1, noise_mode='random', seed=0, depth=None, feature_fn=None,
                  fid_dim=2048, latent_fn=None, device_masks=True, hole_range=(0, 1), keep_images=True, on_batch=None, step_fn=None,
-                 fid_accumulate_fn=None, feeder_stream=False, timing=False, metrics=None, ssim_window=11, metrics_fn=None, fid_real=False):
+                 fid_accumulate_fn=None, feeder_stream=False, timing=False, metrics=None, ssim_window=11, metrics_fn=None, fid_real=False,
+                 lpips=None):
         from .datasets import DeviceFeeder
         self.timing, self.batch_done_events = timing, []      # timing: one timing event per finished batch (bench: steady-state rate)
         self.G, self.device, self.res = G, torch.device(device), int(resolution)
@@ -401,6 +408,10 @@ class EvalLoop:
             from .image_metrics import MetricsAccumulator
             self.metrics = MetricsAccumulator(len(self.ids), self.device, metrics=tuple(metrics), window_size=ssim_window,
                                               metrics_fn=metrics_fn)
+        if lpips is not None and not callable(lpips):
+            raise ValueError('EvalLoop: lpips must be a callable lpips(pred_u8, real, out=slice)')
+        self.lpips_fn = lpips
+        self.lpips_values = (torch.full((len(self.ids),), float('nan'), dtype=torch.float64, device=self.device) if lpips is not None else None)
 
     def _fid_part(self, key, real=False):
         from .fid_stats import FidStats
@@ -440,8 +451,11 @@ class EvalLoop:
                         part.add_shard(self.feature_fn(real_, input_range='pm1'), k0, self.rank, self.world, self.n_items)
                 if real_ is not None and self.metrics is not None:
                     self.metrics.add(out, real_, k0)
+                if self.lpips_fn is not None:
+                    self.lpips_fn(out, real_, out=self.lpips_values[k0:k0 + out.shape[0]])
                 return out
-            out = pipe.run(step, x4, z, real) if (self.metrics is not None or self.fid_real_on) else pipe.run(step, x4, z)
+            need_real = self.metrics is not None or self.fid_real_on or self.lpips_fn is not None
+            out = pipe.run(step, x4, z, real) if need_real else pipe.run(step, x4, z)
             if self.timing and self.device.type == 'cuda':
                 tev = torch.cuda.Event(enable_timing=True)
                 tev.record(pipe.last_stream or torch.cuda.current_stream(self.device))
@@ -481,15 +495,18 @@ class EvalLoop:
             self.fid.all_reduce()
         if self.fid_real_on and self.local_fid_real() is not None:
             self.fid_real.all_reduce()
-        if self.metrics is not None:
+        if self.metrics is not None or self.lpips_fn is not None:
             self.image_metrics = self._gather_metrics(use)
         return images, self.fid
 
     def _gather_metrics(self, use):
         import torch.distributed as dist
         from .image_metrics import finish_metrics
-        names = list(self.metrics.values)
-        local = torch.stack([self.metrics.values[m] for m in names], dim=1)         # [n_local, M] float64
+        values = dict(self.metrics.values) if self.metrics is not None else {}
+        if self.lpips_fn is not None:
+            values['lpips'] = self.lpips_values
+        names = list(values)
+        local = torch.stack([values[m] for m in names], dim=1)                      # [n_local, M] float64
         if use:
             via_host = dist.get_backend() == 'gloo' and local.is_cuda
             src = local.cpu() if via_host else local

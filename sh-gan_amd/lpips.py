@@ -1,0 +1,291 @@
+"""LPIPS with the AlexNet backbone -- ``lpips.LPIPS(net='alex')`` (version 0.1, ``spatial=False``, ``lpips=True``) as the reference's
+lib/evaluator/eva_lpips.py:39-52 calls it -- on the HIP kernels of csrc/lpips.hip (first convolution, distance head) and
+csrc/inception.hip (conv2..conv5, the max pools).
+
+    net = Lpips.from_state_dict(torch.load('lpips_alex_full.pth'), device='cuda')     # or from_state_dicts(alexnet_sd, lin_sd)
+    v = net(pred_u8, real)                                                              # float64 [B], on the current stream
+
+The ``lpips`` package cannot be imported where this was written; what follows restates its PUBLISHED source and was not run against it:
+
+1. operands ``pred``, ``gt`` in [-1, 1], float32, at the images' own size (no resize);
+2. scaling layer ``(x - shift) / scale``, shift (-.030, -.088, -.188), scale (.458, .448, .450) per channel;
+3. AlexNet ``features``: conv 3->64 k11 s4 p2 + ReLU (tap 0), maxpool 3 s2, conv 64->192 k5 p2 + ReLU (tap 1), maxpool 3 s2, conv
+   192->384 k3 p1 + ReLU (tap 2), conv 384->256 k3 p1 + ReLU (tap 3), conv 256->256 k3 p1 + ReLU (tap 4); all with bias, floor pools;
+4. per tap and pixel ``f^ = f / (sqrt(sum_c f^2) + 1e-10)`` for both images and ``d = sum_c w_c (f^_pred - f^_gt)^2`` with the tap's
+   ``lin`` weight (a 1 x 1 convolution to one channel without bias; the dropout in front of it is off in eval);
+5. value = sum over the five taps of the spatial mean of ``d``: one number per image pair.
+
+Operand values follow the evaluator batch (shgan_default.py:283-286, eva_lpips.py:39-45): ``pred = float32(((u8 / 255) - 0.5) * 2)`` with
+the inner arithmetic in float64 (numpy), ``gt = ((real + 1) / 2 - 0.5) * 2`` in float32 throughout.  uint8 operands take these from
+256-entry tables, float32 operands from the same float32 steps inside the kernel's load.  The one departure from the published arithmetic:
+the scaling layer multiplies by ``float32(1 / scale)`` instead of dividing (at most one ulp of the operand).
+
+Weights (``from_state_dict``): the package's own layout -- ``net.slice1.0.{weight,bias}``, ``net.slice2.3.*``, ``net.slice3.6.*``,
+``net.slice4.8.*``, ``net.slice5.10.*``, ``lin{0..4}.model.1.weight`` [1,C,1,1], optionally the duplicates ``lins.{k}.model.1.weight`` and
+``scaling_layer.{shift,scale}`` (else the constants above) -- or (``from_state_dicts``) torchvision's ``alexnet`` state_dict
+(``features.{0,3,6,8,10}.{weight,bias}``; ``classifier.*`` ignored) plus the package's ``alex.pth`` (``lin{k}.model.1.weight``).  Both
+layouts were written from the published sources and NOT checked against the files, which are downloads and are not shipped.
+
+Pred and gt go through the network as one batch of 2B.  No launch plan depends on the batch size (``split_k=False``), the head adds in a
+fixed order without atomics: a pair's value is the same bits alone and inside any batch."""
+import collections
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib, inception, kernels
+from ._lib import ShgError, check
+
+SHIFT = (-.030, -.088, -.188)
+SCALE = (.458, .448, .450)
+# (I, O, kernel, stride, pad) of AlexNet's five convolutions; every one is a tap
+CONVS = ((3, 64, 11, 4, 2), (64, 192, 5, 1, 2), (192, 384, 3, 1, 1), (384, 256, 3, 1, 1), (256, 256, 3, 1, 1))
+TAP_CHANNELS = tuple(c[1] for c in CONVS)
+PACKAGE_CONV_KEYS = ('net.slice1.0', 'net.slice2.3', 'net.slice3.6', 'net.slice4.8', 'net.slice5.10')
+ALEXNET_CONV_KEYS = ('features.0', 'features.3', 'features.6', 'features.8', 'features.10')
+MIN_SIZE = 31             # the second max pool must see 3 x 3
+
+
+def out_sizes(h):
+    """Side of the five taps for an input side h."""
+    t0 = inception.out_size(h, 11, 4, 2)
+    t1 = inception.out_size(t0, 3, 2, 0)
+    t2 = inception.out_size(t1, 3, 2, 0)
+    return (t0, t1, t2, t2, t2)
+
+
+def macs_per_pair(H, W):
+    """Multiply-adds of the ten convolutions of one (pred, gt) pair at H x W (pools and the head are not counted)."""
+    hs, ws = out_sizes(H), out_sizes(W)
+    return 2 * sum(hs[k] * ws[k] * o * i * ks * ks for k, (i, o, ks, _, _) in enumerate(CONVS))
+
+
+def _conv_shapes(prefixes):
+    want = collections.OrderedDict()
+    for key, (i, o, k, _, _) in zip(prefixes, CONVS):
+        want[f'{key}.weight'] = (o, i, k, k)
+        want[f'{key}.bias'] = (o,)
+    return want
+
+
+def _lin_shapes():
+    return collections.OrderedDict((f'lin{k}.model.1.weight', (1, c, 1, 1)) for k, c in enumerate(TAP_CHANNELS))
+
+
+def _validate(sd, want, optional, ignored_prefixes, what):
+    for key in want:
+        if key not in sd:
+            raise ShgError(f'lpips: {what} lacks {key!r}')
+    for key, t in sd.items():
+        if key.startswith(ignored_prefixes):
+            continue
+        shape = want.get(key, optional.get(key))
+        if shape is None:
+            raise ShgError(f'lpips: unexpected {what} key {key!r}')
+        if tuple(t.shape) != shape:
+            raise ShgError(f'lpips: {key!r} has shape {tuple(t.shape)}, expected {shape}')
+
+
+def validate_state_dict(sd):
+    """The package's layout.  Raises ShgError naming the first missing key, unexpected key or wrong shape."""
+    want = _conv_shapes(PACKAGE_CONV_KEYS)
+    want.update(_lin_shapes())
+    optional = {f'lins.{k}.model.1.weight': (1, c, 1, 1) for k, c in enumerate(TAP_CHANNELS)}
+    optional.update({'scaling_layer.shift': (1, 3, 1, 1), 'scaling_layer.scale': (1, 3, 1, 1)})
+    _validate(sd, want, optional, (), 'state_dict')
+
+
+def validate_state_dicts(alexnet_sd, lin_sd):
+    """The two-file layout: torchvision ``alexnet`` (``classifier.*`` ignored) and the package's ``alex.pth``."""
+    _validate(alexnet_sd, _conv_shapes(ALEXNET_CONV_KEYS), {}, ('classifier.',), 'alexnet state_dict')
+    _validate(lin_sd, _lin_shapes(), {}, (), 'lin state_dict')
+
+
+def _f32(t):
+    return torch.as_tensor(t).detach().cpu().to(torch.float32).contiguous()
+
+
+def canonical_weights(sd, lin_sd=None):
+    """Either layout (validated) -> {'conv{k}.weight', 'conv{k}.bias', 'lin{k}' [C], 'shift' [3], 'scale' [3]} float32 on the CPU."""
+    if lin_sd is None:
+        validate_state_dict(sd)
+        prefixes, lins = PACKAGE_CONV_KEYS, sd
+    else:
+        validate_state_dicts(sd, lin_sd)
+        prefixes, lins = ALEXNET_CONV_KEYS, lin_sd
+    out = collections.OrderedDict()
+    for k, key in enumerate(prefixes):
+        out[f'conv{k}.weight'] = _f32(sd[f'{key}.weight'])
+        out[f'conv{k}.bias'] = _f32(sd[f'{key}.bias'])
+        out[f'lin{k}'] = _f32(lins[f'lin{k}.model.1.weight']).reshape(-1)
+        dup = f'lins.{k}.model.1.weight'
+        if lin_sd is None and dup in sd and not torch.equal(_f32(sd[dup]).reshape(-1), out[f'lin{k}']):
+            raise ShgError(f'lpips: {dup!r} differs from its duplicate \'lin{k}.model.1.weight\'')
+    out['shift'] = _f32(sd['scaling_layer.shift']).reshape(-1) if lin_sd is None and 'scaling_layer.shift' in sd else torch.tensor(SHIFT)
+    out['scale'] = _f32(sd['scaling_layer.scale']).reshape(-1) if lin_sd is None and 'scaling_layer.scale' in sd else torch.tensor(SCALE)
+    return out
+
+
+def value_table_cpu(operand, gt_range='pm1'):
+    """float32 [256]: the value of every uint8 code as the network receives it.  'pred': the composite, ``float32(((u8 / 255) - 0.5) * 2)``
+    with numpy float64 inside (shgan_default.py:283, eva_lpips.py:39,43).  'gt': a loader's decoded pixel -- its ``u8_value_table``
+    value as ``real`` ('pm1') then ``((real + 1) / 2 - 0.5) * 2``, or ``float32(u8 / 255)`` ('unit') then ``(u - 0.5) * 2``, in float32."""
+    if operand == 'pred':
+        return torch.from_numpy((((np.arange(256, dtype=np.float64) / 255) - 0.5) * 2).astype(np.float32))
+    if gt_range == 'pm1':
+        u = (kernels.u8_value_table('cpu') + 1) / 2
+    else:
+        u = torch.from_numpy((np.arange(256, dtype=np.float64) / 255).astype(np.float32))
+    return (u - 0.5) * 2
+
+
+_LUTS = {}
+
+
+def value_table(device, operand, gt_range='pm1'):
+    key = (str(device), operand, gt_range if operand == 'gt' else None)
+    if key not in _LUTS:
+        _LUTS[key] = value_table_cpu(operand, gt_range).to(device)
+    return _LUTS[key]
+
+
+def _c3(v):
+    return (ctypes.c_float * 3)(*[float(x) for x in v])
+
+
+def pack_conv1(w, b):
+    """float32 w [64,3,11,11], b [64] on the device -> (wp [368*64], bp [64]) in shg_lpips_conv1_f32's operand layout."""
+    L = kernels._Launch()
+    w, b = L.req(w, 'w'), L.req(b, 'bias')
+    if tuple(w.shape) != (64, 3, 11, 11) or tuple(b.shape) != (64,):
+        raise ShgError(f'lpips: conv1 weight {tuple(w.shape)} / bias {tuple(b.shape)}, expected (64, 3, 11, 11) / (64,)')
+    wp, bp = L.new((368 * 64,)), L.new((64,))
+    with L:
+        check(_lib.get_lib().shg_lpips_conv1_weight_prep_f32(kernels._ptr(w), kernels._ptr(b), kernels._ptr(wp), kernels._ptr(bp), L.stream()),
+              'lpips_conv1_weight_prep')
+    return wp, bp
+
+
+def conv1(images, wp, bp, operand='pred', gt_range='pm1', shift=SHIFT, scale=SCALE, y=None):
+    """images [B,3,H,W] (uint8 or float32, forms of ``Lpips.__call__``) -> relu(conv1(scaling_layer(value))) [B,64,OH,OW] (one launch);
+    ``y``: a contiguous float32 [B,64,OH,OW] view to write into."""
+    if operand not in ('pred', 'gt') or gt_range not in ('pm1', 'unit'):
+        raise ShgError(f"lpips: operand must be 'pred' or 'gt' and gt_range 'pm1' or 'unit' (got {operand!r}, {gt_range!r})")
+    if not isinstance(images, torch.Tensor) or images.ndim != 4 or images.shape[1] != 3:
+        raise ShgError('lpips: images must be a [B,3,H,W] tensor')
+    L = kernels._Launch()
+    if images.dtype == torch.uint8:
+        x = L.req(images, operand, dtype=torch.uint8)
+        lut = L.req(value_table(x.device, operand, gt_range), 'lut')
+        s, b = 1.0, 0.0
+    elif images.dtype == torch.float32:
+        x, lut = L.req(images, operand), None
+        s, b = (0.5, 0.5) if (operand == 'gt' and gt_range == 'pm1') else (1.0, 0.0)
+    else:
+        raise ShgError(f'lpips: {operand} must be uint8 or float32 (got {images.dtype})')
+    wp, bp = L.req(wp, 'wp'), L.req(bp, 'bp')
+    B, _, H, W = x.shape
+    if H < 7 or W < 7:
+        raise ShgError(f'lpips: conv1 needs H, W >= 7 (got {H} x {W})')
+    OH, OW = inception.out_size(H, 11, 4, 2), inception.out_size(W, 11, 4, 2)
+    if y is None:
+        y = L.new((B, 64, OH, OW))
+    L.view(y, 'y')
+    if tuple(y.shape) != (B, 64, OH, OW) or not y.is_contiguous() or y.dtype != torch.float32 or not y.is_cuda:
+        raise ShgError(f'lpips: conv1 output {tuple(y.shape)} does not fit input {tuple(x.shape)}')
+    with L:
+        check(_lib.get_lib().shg_lpips_conv1_f32(kernels._ptr(x), kernels._ptr(lut), s, b, _c3(shift), _c3(scale), kernels._ptr(wp), kernels._ptr(bp),
+                                                 kernels._ptr(y), B, H, W, L.stream()), 'lpips_conv1')
+    return y
+
+
+def head(fp, fg, w, out):
+    """One tap: fp, fg [B,C,h,w] float32 (features of the preds / the gts), w [C] -> out [B] float64 += spatial mean of d."""
+    L = kernels._Launch()
+    fp, fg, w = L.req(fp, 'fp'), L.req(fg, 'fg'), L.req(w, 'w')
+    L.req(out, 'out', dtype=torch.float64)
+    if fp.ndim != 4 or tuple(fp.shape) != tuple(fg.shape) or w.numel() != fp.shape[1]:
+        raise ShgError(f'lpips: head operands {tuple(fp.shape)}, {tuple(fg.shape)}, w {tuple(w.shape)} do not fit')
+    B, C, h, wd = fp.shape
+    if out.numel() != B or not out.is_contiguous():
+        raise ShgError(f'lpips: out must be a contiguous float64 [{B}] tensor')
+    lib = _lib.get_lib()
+    nbytes = int(lib.shg_lpips_head_scratch_bytes(B, h, wd))
+    scratch = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=L.dev)
+    with L:
+        check(lib.shg_lpips_head_f32(kernels._ptr(fp), kernels._ptr(fg), kernels._ptr(w), B, C, h, wd, kernels._ptr(scratch), nbytes,
+                                     kernels._ptr(out), L.stream()), 'lpips_head')
+    return out
+
+
+class Lpips:
+    """``net(pred, gt, gt_range='pm1', out=None) -> float64 [B]``.  pred: uint8 composite or float32 in [0, 1]; gt: float32 in [-1, 1] or
+    decoded uint8 pixels ('pm1'), or float32 in [0, 1] / uint8 with ``gt_range='unit'`` -- the operand forms of
+    ``image_metrics.image_metrics``.  Every launch goes to the current stream and every buffer comes from torch's caching allocator on it,
+    so the network runs on any stream (EvalLoop's side streams) concurrently with itself.  ``net(pred_u8, real, out=slice)`` is the
+    callable ``EvalLoop(lpips=...)`` takes."""
+
+    def __init__(self, conv1_wb, ops, lins, shift, scale, device, split_k=False):
+        self.conv1_wb, self.ops, self.lins = conv1_wb, ops, lins
+        self.shift, self.scale = tuple(float(v) for v in shift), tuple(float(v) for v in scale)
+        self.device, self.split_k = torch.device(device), split_k
+
+    @classmethod
+    def _from_canonical(cls, cw, device, split_k):
+        dev = torch.device(device)
+        conv1_wb = pack_conv1(cw['conv0.weight'].to(dev), cw['conv0.bias'].to(dev))
+        ops = []
+        for k, (i, o, ks, s, p) in enumerate(CONVS[1:], start=1):
+            wp, bp = inception.pack_weight(cw[f'conv{k}.weight'].to(dev), cw[f'conv{k}.bias'].to(dev))
+            ops.append(inception.ConvOp(f'conv{k + 1}', wp, bp, i, o, (ks, ks), (s, s), (p, p)))
+        lins = [cw[f'lin{k}'].to(dev) for k in range(5)]
+        return cls(conv1_wb, ops, lins, cw['shift'].tolist(), cw['scale'].tolist(), dev, split_k)
+
+    @classmethod
+    def from_state_dict(cls, sd, device='cuda', split_k=False):
+        """The package's full ``state_dict`` (``lpips.LPIPS(net='alex').state_dict()``)."""
+        return cls._from_canonical(canonical_weights(sd), device, split_k)
+
+    @classmethod
+    def from_state_dicts(cls, alexnet_sd, lin_sd, device='cuda', split_k=False):
+        """torchvision's ``alexnet`` state_dict + the package's ``weights/v0.1/alex.pth``."""
+        return cls._from_canonical(canonical_weights(alexnet_sd, lin_sd), device, split_k)
+
+    def features(self, pred, gt, gt_range='pm1'):
+        """-> the five taps, each [2B,C,h,w] float32: the preds' features in [:B], the gts' in [B:]."""
+        B, _, H, W = pred.shape
+        oh, ow = out_sizes(H), out_sizes(W)
+        new = lambda k: torch.empty((2 * B, TAP_CHANNELS[k], oh[k], ow[k]), dtype=torch.float32, device=self.device)    # noqa: E731
+        t0 = new(0)
+        conv1(pred, *self.conv1_wb, 'pred', gt_range, self.shift, self.scale, y=t0[:B])
+        conv1(gt, *self.conv1_wb, 'gt', gt_range, self.shift, self.scale, y=t0[B:])
+        taps, x = [t0], inception.pool(t0, 'max', 2, 0)
+        for k, op in enumerate(self.ops, start=1):
+            y = new(k)
+            inception.conv_group([(op, x, 0, y, 0)], split_k=self.split_k)
+            taps.append(y)
+            x = inception.pool(y, 'max', 2, 0) if k == 1 else y
+        return taps
+
+    def __call__(self, pred, gt, gt_range='pm1', out=None):
+        if gt_range not in ('pm1', 'unit'):
+            raise ShgError(f"lpips: gt_range must be 'pm1' or 'unit' (got {gt_range!r})")
+        if not (isinstance(pred, torch.Tensor) and isinstance(gt, torch.Tensor)) or pred.ndim != 4 or tuple(pred.shape) != tuple(gt.shape) \
+                or pred.shape[1] != 3:
+            raise ShgError('lpips: pred and gt must be [B,3,H,W] tensors of one shape')
+        if not (pred.is_cuda and gt.is_cuda):
+            raise ShgError('lpips: pred and gt must reside on a HIP (cuda) device: there is no CPU path')
+        B, _, H, W = pred.shape
+        if H < MIN_SIZE or W < MIN_SIZE:
+            raise ShgError(f'lpips: images of {H} x {W} are too small: the AlexNet taps need H, W >= {MIN_SIZE} (the second max pool must see 3 x 3)')
+        with torch.no_grad():
+            if out is None:
+                out = torch.zeros(B, dtype=torch.float64, device=self.device)
+            else:
+                if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != (B,) or not out.is_contiguous():
+                    raise ShgError(f'lpips: out must be a contiguous float64 [{B}] tensor')
+                out.zero_()
+            for t, w in zip(self.features(pred, gt, gt_range), self.lins):
+                head(t[:B], t[B:], w, out)
+        return out
