@@ -356,6 +356,31 @@ size_t shg_lpips_head_scratch_bytes(int B, int h, int w);
 int shg_lpips_head_f32(const float* fp, const float* fg, const float* w, int B, int C, int h, int wd, void* scratch, size_t scratch_bytes,
                        double* out, void* stream);
 
+/* ---- training tail on the gradient buckets (sh-gan_amd/optim.py drives it; csrc/optim.hip): gradient average + sanitisation + Adam
+ * (lib/experiments/stylegan_default.py:159-166 with torch.optim.Adam, weight_decay 0, amsgrad off) and the G_ema update (:383-390).
+ * Tables are int64 arrays ON THE DEVICE, one row per segment (= one parameter) plus a sentinel row; the last column of a row is the
+ * segment's first chunk (a chunk = SHG_OPT_CHUNK consecutive elements of one segment, a segment of n elements has ceil(n / chunk)),
+ * the sentinel's is the total, which is also passed as `chunks`.  The tables hold raw device addresses: the caller guarantees that
+ * every range lies inside its allocation (optim.py checks that on the host before a launch).
+ * Adam row, SHG_ADAM_ROW int64: {param, grad, exp_avg, exp_avg_sq addresses (4-byte aligned; grad, exp_avg and exp_avg_sq congruent
+ *   mod 16), numel, touched flag, scalar slot, hyper-parameter group, 0, first chunk}.
+ * Tick: for every touched row steps[slot] += 1 (float32 counter, as torch's capturable Adam keeps it) and scalars[slot *
+ *   SHG_ADAM_SCALARS ..] = {lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t), 1 - beta1, beta2, 1 - beta2, eps} computed in float64 from
+ *   hyper [ngroups][4] = {lr, beta1, beta2, eps} (float64) and rounded to float32.  One small workgroup, no host read.
+ * Stream: per element g = grad averaged over `world` ranks (div_mode 0: left as it is, 1: times float32(1 / world) -- what torch's
+ *   div_ by a host scalar computes on the device --, 2: divided by world), then if `sanitize` NaN -> 0, +inf -> 1e5, -inf -> -1e5, written
+ *   back to grad; for touched rows m = lerp(m, g, 1 - beta1) (torch's two-form lerp), v = beta2 v + (1 - beta2) g^2,
+ *   p -= step_size * m / (sqrt(v) * bc2 + eps).  Rows that are not touched keep param, exp_avg, exp_avg_sq and their step bit for bit.
+ * EMA row, SHG_EMA_ROW int64: {dst, src addresses (4-byte aligned), 32-bit words, kind (0: dst = lerp(src, dst, beta[0]) in float32,
+ *   1: dst = src, words copied as they are), 0, first chunk}; beta: one float32 on the device. */
+#define SHG_OPT_CHUNK 4096
+#define SHG_ADAM_ROW 10
+#define SHG_ADAM_SCALARS 8
+#define SHG_EMA_ROW 6
+int shg_adam_tick(const long* table, int nseg, const double* hyper, int ngroups, float* steps, float* scalars, void* stream);
+int shg_adam_buckets_f32(const long* table, int nseg, long chunks, const float* scalars, float world, int div_mode, int sanitize, void* stream);
+int shg_ema_lerp_f32(const long* table, int nseg, long chunks, const float* beta, void* stream);
+
 /* ---- evaluation image metrics (lib/evaluator/eva_psnr.py, for_dataset=None, rgb_range=1; eva_ssim._ssim, size_average=False).
  * pred, gt [B,C,H,W] contiguous; each operand is uint8 when its lut [256] (value of every code: float64 for pred, float32 for gt) is
  * given, float32 otherwise; the element value is then v*scale + bias (the evaluator's fake/255 and (real+1)/2).  As in the reference's

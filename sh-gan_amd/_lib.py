@@ -124,6 +124,9 @@ _SIGS = {
     'shg_lpips_conv1_f32': [c_fp, c_fp, c_f, c_f, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_lpips_head_scratch_bytes': [c_i] * 3,
     'shg_lpips_head_f32': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, ctypes.c_size_t, c_fp, c_fp],
+    'shg_adam_tick': [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp],
+    'shg_adam_buckets_f32': [c_fp, c_i, c_l, c_fp, c_f, c_i, c_i, c_fp],
+    'shg_ema_lerp_f32': [c_fp, c_i, c_l, c_fp, c_fp],
     'shg_image_metrics_scratch_bytes': [c_i] * 4,
     'shg_image_metrics': [c_fp, c_fp, c_f, c_f, c_fp, c_fp, c_f, c_f] + [c_i] * 6 + [c_fp, ctypes.c_size_t, c_fp, c_fp, c_fp],
     'shg_resize_bicubic_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],

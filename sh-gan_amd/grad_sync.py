@@ -130,19 +130,37 @@ class BucketedAllReduce:
         """Wait for the reductions launched by the armed backward pass; average, sanitise.  Buckets that were not launched (a
         parameter the armed pass did not reach, or no armed pass at all) are reduced here, synchronously.  ``reduced=True``: the caller
         has run ``reduce_all()`` -- only the averaging and the sanitisation are left (this part can be captured in a graph)."""
+        self.complete(reduced=reduced)
+        for flat in self.buckets:
+            if self.world > 1:
+                flat.div_(self.world)
+            if self.sanitize:
+                torch.nan_to_num(flat, nan=0.0, posinf=1e5, neginf=-1e5, out=flat)
+        self.rearm()
+
+    def complete(self, reduced=False):
+        """The collective half of ``finish()``: wait for the launched reductions, reduce the buckets that were not launched.  After it the
+        buckets hold the SUM over the ranks (``optim.ShgAdam.step_from_buckets`` averages and sanitises inside its own kernel)."""
         launched = {bi for bi, _ in self._handles}
         for bi, h in self._handles:
             h.wait()
         for bi, flat in enumerate(self.buckets):
             if self.reduce and not reduced and bi not in launched:
                 dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group)
-            if self.world > 1:
-                flat.div_(self.world)
-            if self.sanitize:
-                torch.nan_to_num(flat, nan=0.0, posinf=1e5, neginf=-1e5, out=flat)
+
+    def rearm(self):
+        """The bookkeeping half of ``finish()``: no handle outstanding, every bucket waits for all its gradients again."""
         self._handles = []
         self._pending = list(self._sizes)
         self._armed = False
+
+    def touched_ids(self):
+        """``id(p)`` of the parameters that received a gradient since ``zero_grad()``."""
+        return frozenset(self._touched)
+
+    def slot(self, p):
+        """(bucket index, offset, numel) of a parameter's gradient."""
+        return self._slot[id(p)]
 
     def remove(self):
         for h in self._hooks:

@@ -39,14 +39,18 @@ def make_phases(G, D, g_opt_kwargs, d_opt_kwargs, g_reg_interval=4, d_reg_interv
         kw = dict(opt_kwargs)
         sync = BucketedAllReduce(params, bucket_bytes=bucket_bytes, process_group=process_group) if any(p.is_cuda for p in params) or \
             torch.distributed.is_available() and torch.distributed.is_initialized() else None
+        if hasattr(opt_class, 'step_from_buckets'):          # optim.ShgAdam: the step reads the gradients in the phase's buckets
+            kw['sync'] = sync
         if reg_interval is None:
             opt = opt_class(params, **kw)
+            sync = getattr(opt, 'sync', sync)
             phases.append(Phase(name + 'both', module, opt, 1, sync))
         else:                                   # lazy regularisation
             mb_ratio = reg_interval / (reg_interval + 1)
             kw['lr'] = kw['lr'] * mb_ratio
             kw['betas'] = tuple(float(beta) ** mb_ratio for beta in kw['betas'])
             opt = opt_class(params, **kw)
+            sync = getattr(opt, 'sync', sync)              # (ShgAdam without buckets to share lays out its own)
             phases.append(Phase(name + 'main', module, opt, 1, sync))
             phases.append(Phase(name + 'reg', module, opt, reg_interval, sync))
     if timing and torch.cuda.is_available():
@@ -135,6 +139,9 @@ def _phase_step(phase, loss=None, reduced=False):
     if phase.sync is not None:
         if phase.sync.reduce and not reduced and not phase.sync.was_armed():
             _warn_unarmed(loss, phase)               # correct, but every bucket is reduced synchronously in finish(): no overlap
+        if hasattr(phase.opt, 'step_from_buckets'):  # optim.ShgAdam: average, sanitise and step in one pass over the buckets
+            phase.opt.step_from_buckets(reduced=reduced)
+            return
         phase.sync.finish(reduced=reduced)           # waits for the bucket all-reduces, averages, nan_to_num
         for p in phase.sync.untouched():             # as after zero_grad(set_to_none=True): the optimiser skips them
             p.grad = None
@@ -185,6 +192,8 @@ class PhaseGraphs:
             raise ValueError('PhaseGraphs: warmup >= 1 (lazily built constants, Adam state and allocator pools must exist before the capture)')
         self.split = any(ph.sync is not None and ph.sync.reduce for ph in phases)      # more than one rank: two graphs per phase
         for ph in phases:
+            if hasattr(ph.opt, 'step_from_buckets'):       # optim.ShgAdam keeps its step counters on the device by construction
+                continue
             for g in ph.opt.param_groups:
                 if not g.get('capturable', False):
                     raise ValueError('PhaseGraphs: build the optimisers with capturable=True (the step counter must live on the device)')
@@ -267,13 +276,17 @@ def update_ema(G_ema, G, batch_size, cur_nimg, ema_kimg=10.0, ema_rampup=None):
 
 
 def train(G, D, G_ema, loss, batches, phases, z_dim, batch_size, batch_gpu, total_kimg, effective_batch_gpu=None, ema_kimg=10.0,
-          ema_rampup=None, kimg_per_tick=4, on_tick=None, device=None):
+          ema_rampup=None, kimg_per_tick=4, on_tick=None, device=None, ema=None):
     """The iteration loop of stylegan_default.py:370-396: ``batches`` yields real images [batch_gpu, C, H, W] for this rank,
-    ``batch_size`` is the GLOBAL batch (= batch_gpu * world).  Returns (cur_nimg, batch_idx)."""
+    ``batch_size`` is the GLOBAL batch (= batch_gpu * world).  ``ema``: an ``optim.EmaUpdater(G_ema, G)`` (one launch per iteration)
+    in place of ``update_ema``.  Returns (cur_nimg, batch_idx)."""
     cur_nimg, batch_idx, cur_tick, tick_start = 0, 0, 0, 0
     for real_img in batches:
         run_phases(real_img, z_dim, phases, batch_idx, loss, batch_gpu, effective_batch_gpu, device)
-        update_ema(G_ema, G, batch_size, cur_nimg, ema_kimg, ema_rampup)
+        if ema is not None:
+            ema.update(batch_size, cur_nimg, ema_kimg, ema_rampup)
+        else:
+            update_ema(G_ema, G, batch_size, cur_nimg, ema_kimg, ema_rampup)
         cur_nimg += batch_size
         batch_idx += 1
         done = cur_nimg >= total_kimg * 1000
