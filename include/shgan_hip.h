@@ -278,6 +278,20 @@ int shg_shu_split_irfft2_f32(const float* Y, const float* cw, const float* const
  * shg_shu_split_irfft2_f32 itself, restricted to the 64 x 64 level with the table (1/c_k)/4096 (c_0 = c_32 = 1, else 2). */
 int shg_shu_split_adjoint_f32(const float* const* g, const long* g_batch_stride, const float* const* gauss, float* GS, int N, int C,
                               void* stream);
+/* Size-general forms of the four SHU entry points above (which stay fixed at 64 x 64 with 5 levels): `size` = the transform size
+ * (shu_input_res) = 16, 32, 64 or 128 -- from 256 a plane and its half spectrum no longer fit the LDS of one workgroup -- and
+ * `res` = the `levels` (1..6) level sizes, consecutive powers of two from shu_lowest_res >= 4 up to `size`; gauss / out / g and the
+ * stride arrays have `levels` entries in that order.  Spectra are [N,2C,size,size/2+1], DC on row size/2 - 1, scale 1/size^2.
+ * shg_shu_spectral_n_f32 takes any P % 4 == 0 (a last partial tile of 64 positions is guarded).  The transpose of
+ * shg_shu_rfft2_shift_n_f32 is shg_shu_split_irfft2_n_f32 with one level and the table (1/c_k)/size^2 (c_0 = c_{size/2} = 1, else 2). */
+int shg_shu_rfft2_shift_n_f32(const float* x, long x_batch_stride, float* T, int N, int C, int size, void* stream);
+int shg_shu_spectral_n_f32(const float* T, const float* w0p, const float* b0, const float* w1p, const float* cw, float* S,
+                           int N, int C2, int P, int bands, void* stream);
+int shg_shu_split_irfft2_n_f32(const float* Y, const float* cw, const float* const* gauss, float* const* out,
+                               const long* out_batch_stride, int N, int C, int bands, int accumulate, int size, const int* res,
+                               int levels, void* stream);
+int shg_shu_split_adjoint_n_f32(const float* const* g, const long* g_batch_stride, const float* const* gauss, float* GS, int N, int C,
+                                int size, const int* res, int levels, void* stream);
 
 /* ---- A24: eval composite (lib/experiments/shgan_default.py:257-262): x4 [N,4,H,W], img [N,3,H,W] -> u8 [N,3,H,W]. */
 int shg_composite_u8(const float* x4, const float* img, uint8_t* out, int N, int H, int W, void* stream);

@@ -94,6 +94,10 @@ _SIGS = {
     'shg_shu_spectral_f32': [c_fp] * 6 + [c_i] * 4 + [c_fp],
     'shg_shu_split_irfft2_f32': [c_fp, c_fp, c_pp, c_pp, ctypes.POINTER(c_l), c_i, c_i, c_i, c_i, c_fp],
     'shg_shu_split_adjoint_f32': [c_pp, ctypes.POINTER(c_l), c_pp, c_fp, c_i, c_i, c_fp],
+    'shg_shu_rfft2_shift_n_f32': [c_fp, c_l, c_fp, c_i, c_i, c_i, c_fp],
+    'shg_shu_spectral_n_f32': [c_fp] * 6 + [c_i] * 4 + [c_fp],
+    'shg_shu_split_irfft2_n_f32': [c_fp, c_fp, c_pp, c_pp, ctypes.POINTER(c_l), c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_i), c_i, c_fp],
+    'shg_shu_split_adjoint_n_f32': [c_pp, ctypes.POINTER(c_l), c_pp, c_fp, c_i, c_i, c_i, ctypes.POINTER(c_i), c_i, c_fp],
     'shg_composite_u8': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_assemble_input_f32': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_assemble_input_u8': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],

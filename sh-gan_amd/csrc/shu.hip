@@ -126,7 +126,9 @@ struct ShuSpectralParams {
     int P, B;       // positions per plane (64*33), bands
 };
 
-__global__ __launch_bounds__(256) void shu_spectral_kernel(const ShuSpectralParams p) {
+// TAIL: the last tile may run past P (P % 4 == 0 still holds: float4 granules are whole) -- positions >= P load zeros and are not stored.
+template <bool TAIL>
+__device__ __forceinline__ void shu_spectral_tile(const ShuSpectralParams& p) {
     __shared__ __attribute__((aligned(16))) float Tl[64][64];       // [channel][position]
     __shared__ __attribute__((aligned(16))) float tl[64][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
@@ -137,11 +139,15 @@ __global__ __launch_bounds__(256) void shu_spectral_kernel(const ShuSpectralPara
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int e = q * 256 + tid, ch = e >> 4, c4 = e & 15;
-        *reinterpret_cast<float4*>(&Tl[ch][4 * c4]) = *reinterpret_cast<const float4*>(Tn + (long)ch * p.P + 4 * c4);
+        if (!TAIL || p0 + 4 * c4 < p.P)
+            *reinterpret_cast<float4*>(&Tl[ch][4 * c4]) = *reinterpret_cast<const float4*>(Tn + (long)ch * p.P + 4 * c4);
+        else
+            *reinterpret_cast<float4*>(&Tl[ch][4 * c4]) = make_float4(0.f, 0.f, 0.f, 0.f);
     }
+    const bool live = !TAIL || p0 + nt * 32 + l31 < p.P;
     float cwv[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) cwv[k] = k < p.B ? p.cw[(long)k * p.P + p0 + nt * 32 + l31] : 0.f;
+    for (int k = 0; k < 8; ++k) cwv[k] = (k < p.B && live) ? p.cw[(long)k * p.P + p0 + nt * 32 + l31] : 0.f;
     __syncthreads();
     shu_f32x16 acc;
 #pragma unroll
@@ -174,9 +180,12 @@ __global__ __launch_bounds__(256) void shu_spectral_kernel(const ShuSpectralPara
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int row = mo * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        Sn[(long)row * p.P] = acc[r];
+        if (live) Sn[(long)row * p.P] = acc[r];
     }
 }
+
+__global__ __launch_bounds__(256) void shu_spectral_kernel(const ShuSpectralParams p) { shu_spectral_tile<false>(p); }
+__global__ __launch_bounds__(256) void shu_spectral_tail_kernel(const ShuSpectralParams p) { shu_spectral_tile<true>(p); }
 
 // T [N,64,P] (P = 64*33 positions, a multiple of 64), w0p / w1p: MFMA-ordered weights (see above), b0 [64], cw [B,P], B <= 8
 // -> S [N,64,P].  The shipped SHU geometry only (2C = 64 spectral channels); other shapes: shg_conv2d_f32 twice.
@@ -444,6 +453,386 @@ extern "C" int shg_shu_split_adjoint_f32(const float* const* g, const long* g_ba
         SHG_CHECK_ARG(!g[l] || gauss[l], "shu_split_adjoint: missing gaussian table for level %d", l);
     }
     hipLaunchKernelGGL(shu_split_adjoint_kernel, dim3(C, N), dim3(256), 0, (hipStream_t)stream, p);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}
+
+// ================================================================================================
+// Size-general forms: transform size N = 16, 32, 64 or 128 (shu_input_res) and a pyramid of 1..6 levels r = lowest, 2*lowest, .. N
+// (shu_lowest_res >= 4).  Same design as above -- one workgroup per (sample, channel) plane, everything between the passes in LDS --
+// with the size as a template parameter.  The kernels above stay the code of the shipped geometry (64 x 64, levels 4..64).
+// ================================================================================================
+#define SHU_MAX_LEVELS 6
+
+template <int N>
+__device__ __forceinline__ void shu_build_twiddles_n(float2* tw) {
+    for (int m = threadIdx.x; m < N; m += 256) {
+        float s, c;
+        sincospif((float)m * (2.0f / N), &s, &c);   // angle = 2*pi*m/N
+        tw[m] = make_float2(c, s);
+    }
+}
+
+// D[m][n] = sum_k a(m, k) * b(k, n) in tiles of 32 x 32 on v_mfma_f32_32x32x2_f32 (K even): the mtiles x ntiles tiles are dealt
+// round-robin to the 4 waves; store(m, n, value) receives every element once.  Operand layout as in shu_rfft2_shift_kernel.
+template <class AF, class BF, class SF>
+__device__ __forceinline__ void shu_mfma_tiles(int mtiles, int ntiles, int K, AF a, BF b, SF store) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, half = lane >> 5;
+    for (int t = wave; t < mtiles * ntiles; t += 4) {
+        const int m0 = (t / ntiles) * 32, n0 = (t % ntiles) * 32;
+        shu_f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int k = half; k < K; k += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a(m0 + l31, k), b(k, n0 + l31), acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) store(m0 + (r & 3) + 8 * (r >> 2) + 4 * half, n0 + l31, acc[r]);
+    }
+}
+
+// x: channel planes [C][N][N] per sample at x + n*xbs -> T [batch, 2C, N, N/2+1], DC on row N/2 - 1, scaled by 1/N^2.
+// N >= 64: both passes on the matrix cores with the operand scheme of shu_rfft2_shift_kernel (the last column k = N/2 on the VALU);
+// N < 64: scalar DFTs from the LDS twiddle table (< 0.1 MFLOP per plane).
+template <int N>
+__global__ __launch_bounds__(256) void shu_rfft2_shift_n_kernel(const float* x, long xbs, float* T, int C) {
+    constexpr int NH = N / 2 + 1, M = N - 1;
+    __shared__ float xs[N][N + 1];
+    __shared__ float Rr[N][NH], Ri[N][NH];
+    __shared__ float2 tw[N];
+    const int c = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+    shu_build_twiddles_n<N>(tw);
+    const float* xp = x + (long)n * xbs + (long)c * N * N;
+    for (int e = tid; e < N * N; e += 256) xs[e / N][e % N] = xp[e];
+    const float sc = 1.0f / (N * N);
+    float* Tre = T + ((long)n * 2 * C + c) * N * NH;
+    float* Tim = T + ((long)n * 2 * C + C + c) * N * NH;
+    if constexpr (N >= 64) {
+        for (int h = tid; h < N; h += 256) { Ri[h][0] = 0.f; Ri[h][N / 2] = 0.f; }
+        __syncthreads();
+        // pass 1 (along w, real input): rows m = 0..N/2 -> cos rows (Re R[h][m]), m = N/2+1..N-1 -> -sin rows of k = m - N/2
+        shu_mfma_tiles(N / 32, N / 32, N,
+            [&](int m, int w) { const int km = m < NH ? m : m - N / 2; const float2 t = tw[(km * w) & M]; return m < NH ? t.x : -t.y; },
+            [&](int w, int h) { return xs[h][w]; },
+            [&](int m, int h, float v) { if (m < NH) Rr[h][m] = v; else Ri[h][m - N / 2] = v; });
+        __syncthreads();
+        // pass 2 (along h, complex), columns k < N/2: rows m < N: Re T[u=m] = [cos | sin], m >= N: Im T[u=m-N] = [-sin | cos]
+        shu_mfma_tiles(2 * N / 32, N / 64, 2 * N,
+            [&](int m, int kk) {
+                const float2 t = tw[((m & M) * (kk & M)) & M];
+                return m >= N ? (kk >= N ? t.x : -t.y) : (kk >= N ? t.y : t.x);
+            },
+            [&](int kk, int k) { return kk >= N ? Ri[kk - N][k] : Rr[kk][k]; },
+            [&](int m, int k, float v) { (m >= N ? Tim : Tre)[(((m & M) + N / 2 - 1) & M) * NH + k] = v * sc; });
+        for (int e = tid; e < 2 * N; e += 256) {   // column k = N/2 (Im R = 0 there)
+            const int u = e & M;
+            const bool imrow = e >= N;
+            float v = 0.f;
+            for (int h = 0; h < N; ++h) {
+                const float2 t = tw[(u * h) & M];
+                v += (imrow ? -t.y : t.x) * Rr[h][N / 2];
+            }
+            (imrow ? Tim : Tre)[((u + N / 2 - 1) & M) * NH + N / 2] = v * sc;
+        }
+    } else {
+        __syncthreads();
+        for (int e = tid; e < N * NH; e += 256) {               // along w: real -> half complex, e^{-i theta}
+            const int h = e / NH, k = e - h * NH;
+            float re = 0.f, im = 0.f;
+            for (int w = 0; w < N; ++w) {
+                const float2 t = tw[(k * w) & M];
+                re += xs[h][w] * t.x; im -= xs[h][w] * t.y;
+            }
+            Rr[h][k] = re; Ri[h][k] = im;
+        }
+        __syncthreads();
+        for (int e = tid; e < N * NH; e += 256) {               // along h: complex, e^{-i theta}; row shift
+            const int u = e / NH, k = e - u * NH;
+            float re = 0.f, im = 0.f;
+            for (int h = 0; h < N; ++h) {
+                const float2 t = tw[(u * h) & M];
+                re += Rr[h][k] * t.x + Ri[h][k] * t.y;
+                im += Ri[h][k] * t.x - Rr[h][k] * t.y;
+            }
+            const int row = (u + N / 2 - 1) & M;
+            Tre[row * NH + k] = re * sc; Tim[row * NH + k] = im * sc;
+        }
+    }
+}
+
+static bool shu_size_ok(int size) { return size == 16 || size == 32 || size == 64 || size == 128; }
+
+// res[0..levels): consecutive powers of two, res[0] >= 4, res[levels-1] == size
+static bool shu_levels_ok(int size, const int* res, int levels) {
+    if (!res || levels < 1 || levels > SHU_MAX_LEVELS || res[levels - 1] != size) return false;
+    for (int l = 0; l < levels; ++l)
+        if (res[l] < 4 || res[l] != size >> (levels - 1 - l)) return false;
+    return true;
+}
+
+#define SHU_SIZE_MSG "transform size must be 16, 32, 64 or 128 (from 256 a plane and its half spectrum exceed the LDS of one workgroup)"
+#define SHU_DISPATCH_SIZE(size, LAUNCH) \
+    switch (size) { case 16: LAUNCH(16); break; case 32: LAUNCH(32); break; case 64: LAUNCH(64); break; default: LAUNCH(128); break; }
+
+extern "C" int shg_shu_rfft2_shift_n_f32(const float* x, long x_batch_stride, float* T, int N, int C, int size, void* stream) {
+    SHG_CHECK_ARG(x && T, "shu_rfft2_n: null pointer");
+    SHG_CHECK_ARG(shu_size_ok(size), "shu_rfft2_n: " SHU_SIZE_MSG ", got %d", size);
+    SHG_CHECK_ARG(N >= 1 && N <= 65535 && C >= 1, "shu_rfft2_n: bad shape");
+#define SHU_LAUNCH(S) hipLaunchKernelGGL(shu_rfft2_shift_n_kernel<S>, dim3(C, N), dim3(256), 0, (hipStream_t)stream, x, x_batch_stride, T, C)
+    SHU_DISPATCH_SIZE(size, SHU_LAUNCH)
+#undef SHU_LAUNCH
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}
+
+// shg_shu_spectral_f32 for any P % 4 == 0: whole tiles on the same kernel, a last partial tile on its guarded twin.
+extern "C" int shg_shu_spectral_n_f32(const float* T, const float* w0p, const float* b0, const float* w1p, const float* cw, float* S,
+                                      int N, int C2, int P, int bands, void* stream) {
+    SHG_CHECK_ARG(T && w0p && b0 && w1p && cw && S, "shu_spectral_n: null pointer");
+    SHG_CHECK_ARG(C2 == 64 && P >= 4 && P % 4 == 0 && bands >= 1 && bands <= 8 && N >= 1 && N <= 65535,
+                  "shu_spectral_n: built for 64 spectral channels, P %% 4 == 0, at most 8 bands");
+    SHG_CHECK_ARG(((reinterpret_cast<uintptr_t>(T) | reinterpret_cast<uintptr_t>(S)) & 15) == 0, "shu_spectral_n: T / S must be 16-byte aligned");
+    ShuSpectralParams p{T, w0p, b0, w1p, cw, S, P, bands};
+    if (P % 64 == 0) hipLaunchKernelGGL(shu_spectral_kernel, dim3(P / 64, N), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(shu_spectral_tail_kernel, dim3(shg_cdiv(P, 64), N), dim3(256), 0, (hipStream_t)stream, p);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}
+
+struct ShuSplitNParams {
+    const float* Y;        // [batch, 2C*B, N, N/2+1] when B > 1 (bands to reduce with cw) or [batch, 2C, N, N/2+1] when B == 1
+    const float* cw;       // [B, N, N/2+1]
+    const float* gauss[SHU_MAX_LEVELS]; // level l: [r, r/2+1], r = lowest << l
+    float* out[SHU_MAX_LEVELS];         // level l: planes [C][r][r] per sample at out[l] + n*obs[l]
+    long obs[SHU_MAX_LEVELS];
+    int C, B, accumulate, levels, lowest;
+};
+
+// Levels r < 64: scalar DFTs as in shu_split_irfft2_kernel (their Gaussian tables staged in LDS); levels r >= 64 (64, and 128 at N = 128):
+// matrix cores with the scheme of the r = 64 level there.  V and the pass-A result of a level below the top live in Z together (4 r (r/2+1)
+// floats <= 2 N (N/2+1)); the top level is the last reader of S and puts its pass-A result there.  N = 128: S + Z + tables = 137 KB of LDS.
+template <int N>
+__global__ __launch_bounds__(256) void shu_split_irfft2_n_kernel(const ShuSplitNParams p) {
+    constexpr int NH = N / 2 + 1, M = N - 1;
+    __shared__ float2 S[N][NH];
+    __shared__ float2 Z[N][NH];
+    __shared__ float2 tw[N];
+    __shared__ float gl[12 + 40 + 144 + 544];   // Gaussian-split tables of the scalar levels (r = 4 .. 32: r * (r/2 + 1) floats each)
+    const int c = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+    const int C = p.C, B = p.B;
+    shu_build_twiddles_n<N>(tw);
+    for (int l = 0, off = 0; l < p.levels && (p.lowest << l) < 64; ++l) {
+        const int r = p.lowest << l, cnt = r * (r / 2 + 1);
+        if (p.out[l]) for (int e = tid; e < cnt; e += 256) gl[off + e] = p.gauss[l][e];
+        off += cnt;
+    }
+    // heterogeneous band sum: flat conv-output channel = o*B + k  (shgan.py:157-160)
+    const long plane = N * NH;
+    const float* yre = p.Y + ((long)n * 2 * C + c) * B * plane;
+    const float* yim = p.Y + ((long)n * 2 * C + C + c) * B * plane;
+    for (int e = tid; e < plane; e += 256) {
+        float re = 0.f, im = 0.f;
+        for (int k = 0; k < B; ++k) {
+            const float wgt = B > 1 ? p.cw[k * plane + e] : 1.f;
+            re += yre[k * plane + e] * wgt;
+            im += yim[k * plane + e] * wgt;
+        }
+        S[e / NH][e % NH] = make_float2(re, im);
+    }
+    __syncthreads();
+    for (int l = 0, off = 0; l < p.levels; ++l) {
+        const int r = p.lowest << l, rh = r / 2 + 1, rm = r - 1, tstep = N / r, crop = N / 2 - r / 2;
+        const float* g = gl + off;
+        if (r < 64) off += r * rh;
+        if (!p.out[l]) continue;
+        float* op = p.out[l] + (long)n * p.obs[l] + (long)c * r * r;
+        if (r < 64) {
+            // complex inverse DFT over rows of the cropped, weighted, un-shifted block (shgan.py:328-334)
+            for (int e = tid; e < r * rh; e += 256) {
+                const int y = e / rh, w = e - y * rh;
+                float re = 0.f, im = 0.f;
+                for (int j = 0; j < r; ++j) {
+                    const int a = (j + r / 2 - 1) & rm;               // row inside the crop
+                    const float2 v = S[crop + a][w];
+                    const float gw = g[a * rh + w];
+                    const float2 t = tw[(j * y * tstep) & M];
+                    re += gw * (v.x * t.x - v.y * t.y);               // (a+bi)(c + si)
+                    im += gw * (v.x * t.y + v.y * t.x);
+                }
+                Z[y][w] = make_float2(re, im);
+            }
+            __syncthreads();
+            // half-complex -> real along x (imaginary parts of the DC and Nyquist bins are ignored, as in c2r)
+            for (int e = tid; e < r * r; e += 256) {
+                const int y = e / r, x = e - y * r;
+                float v = Z[y][0].x + ((x & 1) ? -Z[y][r / 2].x : Z[y][r / 2].x);
+                for (int w = 1; w < r / 2; ++w) {
+                    const float2 t = tw[(w * x * tstep) & M];
+                    v += 2.f * (Z[y][w].x * t.x - Z[y][w].y * t.y);
+                }
+                op[e] = p.accumulate ? op[e] + v : v;
+            }
+            __syncthreads();
+            continue;
+        }
+        if constexpr (N >= 64) {
+        // ---- r >= 64 on the matrix cores:
+        //   V[j][w] = g[a][w] * S[crop + a][w], a = (j + r/2 - 1) mod r              (weight + row un-shift, shgan.py:328-334)
+        //   pass A: [Re Z ; Im Z][m][w] = sum_kk A[m][kk] [Re V ; Im V][kk][w]       A = [[cos, -sin], [sin, cos]](theta j y)
+        //   pass B: out[y][x] = sum_kk Zc[y][kk] Bm[kk][x],  kk <= r/2: Re Z[y][w=kk] * c_w cos(theta w x) (c_0 = c_{r/2} = 1, else 2),
+        //           kk > r/2: Im Z[y][w=kk-r/2] * (-2 sin(theta w x))                (c2r ignores Im of the DC / Nyquist bins)
+        float* Vr = reinterpret_cast<float*>(&Z[0][0]);          // [r][rh]
+        float* Vi = Vr + r * rh;
+        float* Zr = r == N ? reinterpret_cast<float*>(&S[0][0]) : Vi + r * rh;
+        float* Zi = Zr + r * rh;
+        const float* gt = p.gauss[l];
+        for (int e = tid; e < r * rh; e += 256) {
+            const int j = e / rh, w = e - j * rh;
+            const int a = (j + r / 2 - 1) & rm;
+            const float2 v = S[crop + a][w];
+            const float gw = gt[a * rh + w];
+            Vr[e] = gw * v.x; Vi[e] = gw * v.y;
+        }
+        __syncthreads();
+        shu_mfma_tiles(2 * r / 32, r / 64, 2 * r,
+            [&](int m, int kk) {
+                const float2 t = tw[(((m & rm) * (kk & rm)) & rm) * tstep];
+                // Re Z = cos*Vr - sin*Vi ;  Im Z = sin*Vr + cos*Vi      (e^{+i theta})
+                return m >= r ? (kk >= r ? t.x : t.y) : (kk >= r ? -t.y : t.x);
+            },
+            [&](int kk, int w) { return (kk >= r ? Vi : Vr)[(kk & rm) * rh + w]; },
+            [&](int m, int w, float v) { (m >= r ? Zi : Zr)[(m & rm) * rh + w] = v; });
+        for (int e = tid; e < 2 * r; e += 256) {                 // column w = r/2 on the VALU
+            const int yy = e & rm;
+            const bool im2 = e >= r;
+            float v = 0.f;
+            for (int j = 0; j < r; ++j) {
+                const float2 t = tw[((yy * j) & rm) * tstep];
+                const float vr = Vr[j * rh + r / 2], vi = Vi[j * rh + r / 2];
+                v += im2 ? (t.y * vr + t.x * vi) : (t.x * vr - t.y * vi);
+            }
+            (im2 ? Zi : Zr)[yy * rh + r / 2] = v;
+        }
+        __syncthreads();
+        const int accumulate = p.accumulate;
+        shu_mfma_tiles(r / 32, r / 32, r,
+            [&](int y, int kk) { return kk >= rh ? Zi[y * rh + kk - r / 2] : Zr[y * rh + kk]; },
+            [&](int kk, int x) {
+                const int w = kk >= rh ? kk - r / 2 : kk;
+                const float2 t = tw[((w * x) & rm) * tstep];
+                return kk >= rh ? -2.f * t.y : ((w == 0 || w == r / 2) ? t.x : 2.f * t.x);
+            },
+            [&](int y, int x, float v) { float* dst = op + y * r + x; *dst = accumulate ? *dst + v : v; });
+        __syncthreads();
+        }
+    }
+}
+
+// res / gauss / out / out_batch_stride: arrays of `levels` entries, res = lowest .. size in consecutive powers of two (out[l] may be
+// null to skip a level).
+extern "C" int shg_shu_split_irfft2_n_f32(const float* Y, const float* cw, const float* const* gauss, float* const* out,
+                                          const long* out_batch_stride, int N, int C, int bands, int accumulate, int size, const int* res,
+                                          int levels, void* stream) {
+    SHG_CHECK_ARG(Y && gauss && out && out_batch_stride && res, "shu_split_n: null pointer");
+    SHG_CHECK_ARG(shu_size_ok(size), "shu_split_n: " SHU_SIZE_MSG ", got %d", size);
+    SHG_CHECK_ARG(shu_levels_ok(size, res, levels), "shu_split_n: the levels must be 1 to %d consecutive powers of two from >= 4 up to the size %d",
+                  SHU_MAX_LEVELS, size);
+    SHG_CHECK_ARG(bands >= 1 && (bands == 1 || cw), "shu_split_n: cw required when bands > 1");
+    SHG_CHECK_ARG(N >= 1 && N <= 65535 && C >= 1, "shu_split_n: bad shape");
+    ShuSplitNParams p{};
+    p.Y = Y; p.cw = cw; p.C = C; p.B = bands; p.accumulate = accumulate; p.levels = levels; p.lowest = res[0];
+    for (int l = 0; l < levels; ++l) {
+        p.gauss[l] = gauss[l]; p.out[l] = out[l]; p.obs[l] = out_batch_stride[l];
+        SHG_CHECK_ARG(!out[l] || gauss[l], "shu_split_n: missing gaussian table for level %d", l);
+    }
+#define SHU_LAUNCH(S) hipLaunchKernelGGL(shu_split_irfft2_n_kernel<S>, dim3(C, N), dim3(256), 0, (hipStream_t)stream, p)
+    SHU_DISPATCH_SIZE(size, SHU_LAUNCH)
+#undef SHU_LAUNCH
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}
+
+struct ShuSplitAdjNParams {
+    const float* g[SHU_MAX_LEVELS];     // level l: planes [C][r][r] per sample at g[l] + n*gbs[l]; null = no gradient for that level
+    long gbs[SHU_MAX_LEVELS];
+    const float* gauss[SHU_MAX_LEVELS];
+    float* GS;                          // [batch, 2C, N, N/2+1]: Re planes, then Im planes
+    int C, levels, lowest;
+};
+
+// shu_split_adjoint_kernel for any size / level list.  The gradient plane of a level passes through LDS in blocks of at most 32 rows (the
+// pass along x is row by row), so that N = 128 needs acc + T1 + 16 KB = 147 KB of LDS and not a whole 64 KB plane on top of the two spectra.
+template <int N>
+__global__ __launch_bounds__(256) void shu_split_adjoint_n_kernel(const ShuSplitAdjNParams p) {
+    constexpr int NH = N / 2 + 1, M = N - 1;
+    __shared__ float2 acc[N][NH];
+    __shared__ float2 T1[N][NH];
+    __shared__ float gl[32 * N];
+    __shared__ float2 tw[N];
+    const int c = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
+    shu_build_twiddles_n<N>(tw);
+    for (int e = tid; e < N * NH; e += 256) acc[e / NH][e % NH] = make_float2(0.f, 0.f);
+    __syncthreads();
+    for (int l = 0; l < p.levels; ++l) {
+        if (!p.g[l]) continue;
+        const int r = p.lowest << l, rh = r / 2 + 1, tstep = N / r, rb = r < 32 ? r : 32;
+        const float* gp = p.g[l] + (long)n * p.gbs[l] + (long)c * r * r;
+        for (int y0 = 0; y0 < r; y0 += rb) {
+            for (int e = tid; e < rb * r; e += 256) gl[e] = gp[y0 * r + e];
+            __syncthreads();
+            for (int e = tid; e < rb * rh; e += 256) {          // along x: real -> half complex, e^{-i theta}
+                const int y = e / rh, kx = e - y * rh;
+                float re = 0.f, im = 0.f;
+                for (int x = 0; x < r; ++x) {
+                    const float2 t = tw[(kx * x * tstep) & M];
+                    const float v = gl[y * r + x];
+                    re += v * t.x; im -= v * t.y;
+                }
+                T1[y0 + y][kx] = make_float2(re, im);
+            }
+            __syncthreads();
+        }
+        const float* gw = p.gauss[l];
+        for (int e = tid; e < r * rh; e += 256) {               // along y: complex, e^{-i theta}; weight, shift, embed
+            const int ky = e / rh, kx = e - ky * rh;
+            float re = 0.f, im = 0.f;
+            for (int y = 0; y < r; ++y) {
+                const float2 t = tw[(ky * y * tstep) & M];
+                const float2 v = T1[y][kx];
+                re += v.x * t.x + v.y * t.y;                     // (a + bi)(c - si)
+                im += v.y * t.x - v.x * t.y;
+            }
+            const int j = (ky + r / 2 - 1) & (r - 1);
+            const float wgt = gw[j * rh + kx] * ((kx == 0 || kx == r / 2) ? 1.f : 2.f);
+            float2& a = acc[N / 2 - r / 2 + j][kx];
+            a.x += wgt * re; a.y += wgt * im;
+        }
+        __syncthreads();
+    }
+    const long plane = N * NH;
+    float* ore = p.GS + ((long)n * 2 * p.C + c) * plane;
+    float* oim = p.GS + ((long)n * 2 * p.C + p.C + c) * plane;
+    for (int e = tid; e < plane; e += 256) {
+        const float2 a = acc[e / NH][e % NH];
+        ore[e] = a.x; oim[e] = a.y;
+    }
+}
+
+// res / g / g_batch_stride / gauss: arrays of `levels` entries (g[l] may be null); GS [N, 2C, size, size/2+1] is overwritten.
+extern "C" int shg_shu_split_adjoint_n_f32(const float* const* g, const long* g_batch_stride, const float* const* gauss, float* GS, int N,
+                                           int C, int size, const int* res, int levels, void* stream) {
+    SHG_CHECK_ARG(g && g_batch_stride && gauss && GS && res, "shu_split_adjoint_n: null pointer");
+    SHG_CHECK_ARG(shu_size_ok(size), "shu_split_adjoint_n: " SHU_SIZE_MSG ", got %d", size);
+    SHG_CHECK_ARG(shu_levels_ok(size, res, levels),
+                  "shu_split_adjoint_n: the levels must be 1 to %d consecutive powers of two from >= 4 up to the size %d", SHU_MAX_LEVELS, size);
+    SHG_CHECK_ARG(N >= 1 && N <= 65535 && C >= 1, "shu_split_adjoint_n: bad shape");
+    ShuSplitAdjNParams p{};
+    p.GS = GS; p.C = C; p.levels = levels; p.lowest = res[0];
+    for (int l = 0; l < levels; ++l) {
+        p.g[l] = g[l]; p.gbs[l] = g_batch_stride[l]; p.gauss[l] = gauss[l];
+        SHG_CHECK_ARG(!g[l] || gauss[l], "shu_split_adjoint_n: missing gaussian table for level %d", l);
+    }
+#define SHU_LAUNCH(S) hipLaunchKernelGGL(shu_split_adjoint_n_kernel<S>, dim3(C, N), dim3(256), 0, (hipStream_t)stream, p)
+    SHU_DISPATCH_SIZE(size, SHU_LAUNCH)
+#undef SHU_LAUNCH
     SHG_CHECK_LAUNCH();
     return SHG_OK;
 }

@@ -1045,29 +1045,49 @@ def modconv_style_prep_grouped(items):
 # SHU
 # ------------------------------------------------------------------------------------------------
 
+SHU_SIZES = (16, 32, 64, 128)     # transform sizes of csrc/shu.hip (one workgroup per plane; from 256 a plane + spectrum exceed its LDS)
+
+
+def _shu_levels(size, count, who):
+    """Level sizes of a pyramid of ``count`` levels that ends at ``size`` -> (list, int array or None for the shipped 64 / 5 levels)."""
+    if size not in SHU_SIZES:
+        raise _lib.ShgError(f'{who}: the transform size must be one of {SHU_SIZES}, got {size}')
+    if not (1 <= count <= 6 and size >> (count - 1) >= 4):
+        raise _lib.ShgError(f'{who}: {count} levels do not fit between 4 and {size}')
+    res = [size >> (count - 1 - l) for l in range(count)]
+    return res, (None if (size, count) == (64, 5) else (ctypes.c_int * count)(*res))
+
+
 def shu_rfft2_shift(x):
-    """x: [N,C,64,64] view whose channel planes are contiguous (a channel slice of an NCHW tensor is fine)."""
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.ndim == 4 and tuple(x.shape[2:]) == (64, 64)):
-        raise _lib.ShgError('shu_rfft2_shift: x must be a float32 HIP tensor [N,C,64,64]')
-    if x.stride(3) != 1 or x.stride(2) != 64 or x.stride(1) != 4096:
+    """x: [N,C,S,S] view (S in SHU_SIZES) whose channel planes are contiguous (a channel slice of an NCHW tensor is fine)."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.ndim == 4 and x.shape[2] == x.shape[3]
+            and x.shape[2] in SHU_SIZES):
+        raise _lib.ShgError(f'shu_rfft2_shift: x must be a float32 HIP tensor [N,C,S,S], S in {SHU_SIZES}')
+    sz = x.shape[2]
+    if x.stride(3) != 1 or x.stride(2) != sz or x.stride(1) != sz * sz:
         x = x.contiguous()
     L = _Launch()
     L.view(x, 'x')
     n, c = x.shape[:2]
-    t = L.new((n, 2 * c, 64, 33))
+    t = L.new((n, 2 * c, sz, sz // 2 + 1))
     with _timed(L, 'shu_rfft2', 4.0 * (x.numel() + t.numel())):
-        check(_lib.get_lib().shg_shu_rfft2_shift_f32(_ptr(x), x.stride(0), _ptr(t), n, c, L.stream()), 'shu_rfft2_shift')
+        if sz == 64:
+            check(_lib.get_lib().shg_shu_rfft2_shift_f32(_ptr(x), x.stride(0), _ptr(t), n, c, L.stream()), 'shu_rfft2_shift')
+        else:
+            check(_lib.get_lib().shg_shu_rfft2_shift_n_f32(_ptr(x), x.stride(0), _ptr(t), n, c, sz, L.stream()), 'shu_rfft2_shift')
     return t
 
 
-def shu_split_adjoint(grads, gauss, n, c):
-    """Transpose of ``shu_split_irfft2`` (bands == 1): grads = 5 tensors [N,C,r,r] (r = 4..64; None = no gradient) -> [N,2C,64,33]."""
+def shu_split_adjoint(grads, gauss, n, c, size=64):
+    """Transpose of ``shu_split_irfft2`` (bands == 1): grads = one tensor [N,C,r,r] per level (r = .., size/2, size; None = no gradient)
+    -> [N,2C,size,size/2+1]."""
     L = _Launch()
-    g_arr = (ctypes.c_void_p * 5)()
-    s_arr = (ctypes.c_long * 5)()
-    t_arr = (ctypes.c_void_p * 5)()
-    for l in range(5):
-        r = 4 << l
+    nl = len(grads)
+    res, res_arr = _shu_levels(size, nl, 'shu_split_adjoint')
+    g_arr = (ctypes.c_void_p * nl)()
+    s_arr = (ctypes.c_long * nl)()
+    t_arr = (ctypes.c_void_p * nl)()
+    for l, r in enumerate(res):
         t_arr[l] = L.req(gauss[l], 'gauss').data_ptr()
         g = grads[l]
         if g is None:
@@ -1078,9 +1098,13 @@ def shu_split_adjoint(grads, gauss, n, c):
             raise _lib.ShgError(f'shu_split_adjoint: grads[{l}] must be [N,{c},{r},{r}]')
         g_arr[l] = g.data_ptr()
         s_arr[l] = g.stride(0)
-    out = L.new((n, 2 * c, 64, 33))
+    out = L.new((n, 2 * c, size, size // 2 + 1))
     with _timed(L, 'shu_split_adjoint', 4.0 * out.numel()):
-        check(_lib.get_lib().shg_shu_split_adjoint_f32(g_arr, s_arr, t_arr, _ptr(out), n, c, L.stream()), 'shu_split_adjoint')
+        if res_arr is None:
+            check(_lib.get_lib().shg_shu_split_adjoint_f32(g_arr, s_arr, t_arr, _ptr(out), n, c, L.stream()), 'shu_split_adjoint')
+        else:
+            check(_lib.get_lib().shg_shu_split_adjoint_n_f32(g_arr, s_arr, t_arr, _ptr(out), n, c, size, res_arr, nl, L.stream()),
+                  'shu_split_adjoint')
     return out
 
 
@@ -1125,7 +1149,8 @@ def mfma_pack_rows(w):
 
 
 def shu_spectral(t, w0p, b0, w1p, cw):
-    """t [N,64,64,33] -> S [N,64,64,33]: conv0 + ReLU + heterogeneous filter + band sum in one launch (shg_shu_spectral_f32)."""
+    """t [N,64,S,S/2+1] -> S [N,64,S,S/2+1]: conv0 + ReLU + heterogeneous filter + band sum in one launch (shg_shu_spectral_f32; a
+    plane whose positions are no multiple of 64 -- S = 16, 32 -- goes through shg_shu_spectral_n_f32 and its guarded last tile)."""
     L = _Launch()
     t, w0p, b0, w1p, cw = L.req(t, 't'), L.req(w0p, 'w0p'), L.req(b0, 'b0'), L.req(w1p, 'w1p'), L.req(cw, 'cw')
     n, c2, h, w = t.shape
@@ -1135,32 +1160,37 @@ def shu_spectral(t, w0p, b0, w1p, cw):
     out = L.new((n, c2, h, w))
     # matrix work: conv0 (c2 x c2) + the band filter (bands c2 x c2) per spectral pixel, fp32 MFMA
     with _timed(L, 'shu_spectral', 2.0 * n * h * w * c2 * c2 * (1 + bands)):
-        check(_lib.get_lib().shg_shu_spectral_f32(_ptr(t), _ptr(w0p), _ptr(b0), _ptr(w1p), _ptr(cw), _ptr(out), n, c2, h * w, bands,
-                                                  L.stream()), 'shu_spectral')
+        fn = _lib.get_lib().shg_shu_spectral_f32 if (h * w) % 64 == 0 else _lib.get_lib().shg_shu_spectral_n_f32
+        check(fn(_ptr(t), _ptr(w0p), _ptr(b0), _ptr(w1p), _ptr(cw), _ptr(out), n, c2, h * w, bands, L.stream()), 'shu_spectral')
     return out
 
 
 def shu_split_irfft2(y, cw, gauss, outs, accumulate):
-    """y: [N, 2C*B, 64, 33]; cw: [B,64,33] or None; gauss: list of 5 tables (r=4..64);
-    outs: list of 5 tensors/views [N,C,r,r] with contiguous channel planes (or None to skip)."""
+    """y: [N, 2C*B, S, S/2+1]; cw: [B,S,S/2+1] or None; gauss: one table per level (r = .., S/2, S: as many levels as ``outs`` has);
+    outs: tensors/views [N,C,r,r] with contiguous channel planes (or None to skip).  S = 64 with five levels is the shipped entry point."""
     L = _Launch()
     y = L.req(y, 'y')
     cw = L.req(cw, 'cw')
     bands = cw.shape[0] if cw is not None else 1
     n = y.shape[0]
     c = y.shape[1] // (2 * bands)
-    g_arr = (ctypes.c_void_p * 5)()
-    o_arr = (ctypes.c_void_p * 5)()
-    s_arr = (ctypes.c_long * 5)()
+    size, nl = y.shape[2], len(outs)
+    res, res_arr = _shu_levels(size, nl, 'shu_split_irfft2')
+    if y.shape[3] != size // 2 + 1 or len(gauss) != nl or (cw is not None and tuple(cw.shape[1:]) != tuple(y.shape[2:])):
+        raise _lib.ShgError('shu_split_irfft2: y must be a half spectrum [N,2C*B,S,S/2+1] with one table per level and cw [B,S,S/2+1]')
+    g_arr = (ctypes.c_void_p * nl)()
+    o_arr = (ctypes.c_void_p * nl)()
+    s_arr = (ctypes.c_long * nl)()
     nbytes = 4.0 * y.numel()
-    for l in range(5):
-        r = 4 << l
+    for l, r in enumerate(res):
         g = L.req(gauss[l], 'gauss')
         g_arr[l] = g.data_ptr()
         o = outs[l]
         if o is None:
             o_arr[l] = None
             continue
+        if g.numel() != r * (r // 2 + 1):
+            raise _lib.ShgError(f'shu_split_irfft2: gauss[{l}] must be [{r},{r // 2 + 1}]')
         if not (o.is_cuda and o.dtype == torch.float32 and tuple(o.shape) == (n, c, r, r)
                 and o.stride(3) == 1 and o.stride(2) == r and o.stride(1) == r * r):
             raise _lib.ShgError(f'shu_split_irfft2: out[{l}] must be a float32 [N,{c},{r},{r}] view with contiguous planes')
@@ -1169,6 +1199,10 @@ def shu_split_irfft2(y, cw, gauss, outs, accumulate):
         s_arr[l] = o.stride(0)
         nbytes += 4.0 * o.numel() * (2 if accumulate else 1)
     with _timed(L, 'shu_irfft2', nbytes):
-        check(_lib.get_lib().shg_shu_split_irfft2_f32(_ptr(y), _ptr(cw), g_arr, o_arr, s_arr, n, c, bands, int(bool(accumulate)),
-                                                      L.stream()), 'shu_split_irfft2')
+        if res_arr is None:
+            check(_lib.get_lib().shg_shu_split_irfft2_f32(_ptr(y), _ptr(cw), g_arr, o_arr, s_arr, n, c, bands, int(bool(accumulate)),
+                                                          L.stream()), 'shu_split_irfft2')
+        else:
+            check(_lib.get_lib().shg_shu_split_irfft2_n_f32(_ptr(y), _ptr(cw), g_arr, o_arr, s_arr, n, c, bands, int(bool(accumulate)),
+                                                            size, res_arr, nl, L.stream()), 'shu_split_irfft2')
     return outs

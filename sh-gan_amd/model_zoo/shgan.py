@@ -124,11 +124,15 @@ class heterogeneous_filter(nn.Module):
         return _cache_of(self).get('w', [self.weight], build)
 
     def band_conv(self, x):
+        # a 1x1 convolution sees positions only: they are laid out as rows of 32, the last row zero-padded (16 x 9 = 144 positions)
         n, c, h, w = x.shape
-        if (h * w) % 32 != 0:
-            raise NotImplementedError('heterogeneous_filter: H*W must be a multiple of 32')
-        y = kernels.conv2d(x.reshape(n, c, (h * w) // 32, 32), self.prepped(), mode=kernels.MODE_SAME, pad=0)
-        return y.reshape(n, -1, h, w)
+        p = h * w
+        pp = -(-p // 32) * 32
+        xf = x.reshape(n, c, p)
+        if pp != p:
+            xf = torch.nn.functional.pad(xf, (0, pp - p))
+        y = kernels.conv2d(xf.reshape(n, c, pp // 32, 32), self.prepped(), mode=kernels.MODE_SAME, pad=0)
+        return y.reshape(n, -1, pp)[:, :, :p].reshape(n, -1, h, w)
 
     def cweight(self, h, w, device):
         """Band-weight table for an [h, w] half spectrum, built once per geometry (shgan.py:145-155)."""
@@ -198,23 +202,23 @@ class gaussian_heatmap_2d(object):
         return out
 
 
-def _adjoint_table(device):
-    """(1/c_k) / 4096 on [64,33], c_0 = c_32 = 1, else 2: with it the 64 x 64 level of ``shu_split_irfft2`` is the transpose of
-    ``shu_rfft2_shift`` (rfft2 with norm='forward' keeps half of a Hermitian spectrum; irfft2 counts the interior columns twice)."""
-    t = _ADJ_TABLE.get(str(device))
+def _adjoint_table(device, size=64):
+    """(1/c_k) / size^2 on [size, size/2+1], c_0 = c_{size/2} = 1, else 2: with it the top level of ``shu_split_irfft2`` is the
+    transpose of ``shu_rfft2_shift`` (rfft2 with norm='forward' keeps half of a Hermitian spectrum; irfft2 counts the interior
+    columns twice)."""
+    t = _ADJ_TABLE.get((str(device), size))
     if t is None:
-        w = torch.full((64, 33), 0.5 / 4096.0)
-        w[:, 0] = w[:, 32] = 1.0 / 4096.0
-        t = _ADJ_TABLE[str(device)] = w.to(device)
+        w = torch.full((size, size // 2 + 1), 0.5 / (size * size))
+        w[:, 0] = w[:, size // 2] = 1.0 / (size * size)
+        t = _ADJ_TABLE[(str(device), size)] = w.to(device)
     return t
 
 
 _ADJ_TABLE = {}
-_LEVELS = (4, 8, 16, 32, 64)
 
 
 class _ShuSpectrum(torch.autograd.Function):
-    """x [N,C,64,64] -> [N,2C,64,33] (rfft2, norm='forward', rows shifted: shgan.py:313-319); backward = its transpose."""
+    """x [N,C,S,S] -> [N,2C,S,S/2+1] (rfft2, norm='forward', rows shifted: shgan.py:313-319); backward = its transpose."""
     @staticmethod
     def forward(ctx, x):
         return kernels.shu_rfft2_shift(x.detach())
@@ -228,10 +232,11 @@ class _ShuSpectrumT(torch.autograd.Function):
     @staticmethod
     def forward(ctx, g):
         g = g.detach()
-        n, c = g.shape[0], g.shape[1] // 2
-        out = torch.empty((n, c, 64, 64), device=g.device, dtype=torch.float32)
-        tab = _adjoint_table(g.device)
-        kernels.shu_split_irfft2(g, None, [tab] * 5, [None, None, None, None, out], accumulate=False)
+        n, c, size = g.shape[0], g.shape[1] // 2, g.shape[2]
+        out = torch.empty((n, c, size, size), device=g.device, dtype=torch.float32)
+        tab = _adjoint_table(g.device, size)
+        skipped = 4 if size == 64 else 0       # 64: the shipped five-level entry point with its lower levels switched off
+        kernels.shu_split_irfft2(g, None, [tab] * (skipped + 1), [None] * skipped + [out], accumulate=False)
         return out
 
     @staticmethod
@@ -240,46 +245,58 @@ class _ShuSpectrumT(torch.autograd.Function):
 
 
 class _ShuSplit(torch.autograd.Function):
-    """S [N,2C,64,33] -> the five hints [N,C,r,r] (crop, Gaussian split, un-shift, irfft2: shgan.py:326-336); backward = its transpose."""
+    """S [N,2C,S,S/2+1] -> one hint [N,C,r,r] per Gaussian table, r = .., S/2, S (crop, Gaussian split, un-shift, irfft2:
+    shgan.py:326-336); backward = its transpose."""
     @staticmethod
     def forward(ctx, s, *gauss):
         s = s.detach()
         n, c = s.shape[0], s.shape[1] // 2
         ctx.gauss = gauss
-        outs = [torch.empty((n, c, r, r), device=s.device, dtype=torch.float32) for r in _LEVELS]
+        outs = [torch.empty((n, c, g.shape[0], g.shape[0]), device=s.device, dtype=torch.float32) for g in gauss]
         kernels.shu_split_irfft2(s, None, list(gauss), outs, accumulate=False)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *grads):
-        return (_ShuSplitT.apply(*[None if g is None else g.contiguous() for g in grads], *ctx.gauss),) + (None,) * 5
+        return (_ShuSplitT.apply(*[None if g is None else g.contiguous() for g in grads], *ctx.gauss),) + (None,) * len(ctx.gauss)
 
 
 class _ShuSplitT(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, g4, g8, g16, g32, g64, *gauss):
-        grads = [None if g is None else g.detach() for g in (g4, g8, g16, g32, g64)]
+    def forward(ctx, *grads_then_gauss):
+        nl = len(grads_then_gauss) // 2
+        grads = [None if g is None else g.detach() for g in grads_then_gauss[:nl]]
+        gauss = grads_then_gauss[nl:]
         ctx.gauss = gauss
         ctx.present = [g is not None for g in grads]
         ref = next(g for g in grads if g is not None)
-        return kernels.shu_split_adjoint(grads, list(gauss), ref.shape[0], ref.shape[1])
+        return kernels.shu_split_adjoint(grads, list(gauss), ref.shape[0], ref.shape[1], size=gauss[-1].shape[0])
 
     @staticmethod
     def backward(ctx, gs):
         outs = _ShuSplit.apply(gs.contiguous(), *ctx.gauss)
-        return tuple(o if pr else None for o, pr in zip(outs, ctx.present)) + (None,) * 5
+        return tuple(o if pr else None for o, pr in zip(outs, ctx.present)) + (None,) * len(ctx.gauss)
 
 
 class SHU(nn.Module):
     """Spectral Hint Unit (shgan.py:252-336): rFFT2 -> 1x1 conv + ReLU -> heterogeneous filter ->
-    Gaussian split into a pyramid of bands -> irFFT2 per band.  x [N,C,64,64] -> {r: [N,C,r,r]}."""
+    Gaussian split into a pyramid of bands -> irFFT2 per band.  x [N,C,S,S] -> {r: [N,C,r,r]}, S = ``input_res`` in 16..128 and
+    r = ``lowest_res`` (>= 4), .., S/2, S: the geometries the one-workgroup-per-plane kernels of csrc/shu.hip hold in LDS."""
 
     def __init__(self, in_channels, out_channels, dfilter_freedom=[3, 2], dfilter_type='piecewise_linear', input_res=256,
                  lowest_res=4, tail_sigma_mult=3, gaussian_at_input_res=False):
         super().__init__()
         from .stylegan import conv2d
-        if input_res != 64 or lowest_res != 4 or in_channels != out_channels:
-            raise NotImplementedError('the HIP SHU kernels are built for the shipped geometry: 64x64 input, levels 4..64')
+        if in_channels != out_channels:
+            raise NotImplementedError(f'SHU with in_channels {in_channels} != out_channels {out_channels}: the reference itself fails '
+                                      'there (heterogeneous_filter.forward views its output with the input channel count, shgan.py:158)')
+        if input_res < 16 or input_res & (input_res - 1):
+            raise NotImplementedError(f'SHU input_res {input_res}: the HIP transforms are built for the powers of two 16, 32, 64, 128')
+        if input_res >= 256:
+            raise NotImplementedError(f'SHU input_res {input_res}: a plane and its half spectrum no longer fit the 160 KiB of LDS of one '
+                                      'workgroup (the kernels hold both there); supported: 16, 32, 64, 128')
+        if lowest_res < 4 or lowest_res > input_res or lowest_res & (lowest_res - 1):
+            raise NotImplementedError(f'SHU lowest_res {lowest_res}: must be a power of two with 4 <= lowest_res <= input_res {input_res}')
         self.in_channels, self.out_channels = in_channels, out_channels
         self.input_res, self.lowest_res = input_res, lowest_res
         self.conv0 = conv2d(in_channels * 2, in_channels * 2, 1, 1, 0)
@@ -324,22 +341,22 @@ class SHU(nn.Module):
         return _cache_of(self).get('spec', [q for q in (self.conv0.weight, self.conv0.bias, self.df1.weight) if q is not None], build)
 
     def _spectral(self, x):
-        """-> (y, cw): y [N,2C*B,64,33] with its band table, or the band-summed [N,2C,64,33] and None."""
-        t = kernels.shu_rfft2_shift(x)                 # [N,2C,64,33]: Re | Im, DC on row 31
+        """-> (y, cw): y [N,2C*B,S,S/2+1] with its band table, or the band-summed [N,2C,S,S/2+1] and None."""
+        t = kernels.shu_rfft2_shift(x)                 # [N,2C,S,S/2+1]: Re | Im, DC on row S/2 - 1
         if self.FUSED_SPECTRAL and t.shape[1] == 64 and self._cw.shape[0] <= 8:
             w0p, b0, w1p = self._packed()
             return kernels.shu_spectral(t, w0p, b0, w1p, self._cw), None
         t = self.conv0(t, relu=True)                   # 1x1 conv + bias + ReLU on the MFMA kernel
-        return self.df1.band_conv(t), self._cw         # [N,2C*6,64,33]
+        return self.df1.band_conv(t), self._cw         # [N,2C*B,S,S/2+1]
 
     def _forward_train(self, x):
         """Training rows: shgan.py:312-336 on differentiable operators that are all HIP kernels -- the two transform stages through
         ``_ShuSpectrum`` / ``_ShuSplit`` (the inference kernels forward, their transposes backward: both stages are linear maps),
         the two 1x1 convolutions on the HIP conv kernels (forward / backward)."""
         gauss = [getattr(self, f'_gauss{r}') for r in self.reslist]
-        t = _ShuSpectrum.apply(x.contiguous())                                   # [N,2C,64,33]: Re | Im, DC on row 31, norm='forward'
+        t = _ShuSpectrum.apply(x.contiguous())                                   # [N,2C,S,S/2+1]: Re | Im, DC on row S/2 - 1, norm='forward'
         t = self.conv0(t, relu=True)
-        t = self.df1(t)                                                          # [N,2C,64,33], bands summed
+        t = self.df1(t)                                                          # [N,2C,S,S/2+1], bands summed
         outs = _ShuSplit.apply(t.contiguous(), *gauss)
         return dict(zip(self.reslist, outs))
 
@@ -363,8 +380,9 @@ class SHU(nn.Module):
 
 @register('shgan_encoder', version)
 class Encoder(Encoder_base):
-    """Co-modulation encoder + SHU: the last ``shu_channels`` channels of the 64x64 feature feed the SHU
-    and its band outputs are added to the same channels of the 4..64 skip features (shgan.py:338-383)."""
+    """Co-modulation encoder + SHU: the last ``shu_channels`` channels of the ``shu_input_res`` feature feed the SHU
+    and its band outputs are added to the same channels of the ``shu_lowest_res`` .. ``shu_input_res`` skip features
+    (shgan.py:338-383)."""
 
     def __init__(self, *args, **kwargs):
         self.shu_input_res = kwargs.pop('shu_input_res')
