@@ -348,6 +348,26 @@ size_t shg_inception_conv_workspace_bytes(const shg_inc_conv_desc* groups, int G
 int shg_inception_conv_f32(const shg_inc_conv_desc* groups, int G, int B, void* workspace, size_t ws_bytes, void* stream);
 int shg_inception_pool_f32(const float* x, float* y, int B, int C, int H, int W, int mode, int stride, int pad, int y_ctot, int y_coff, void* stream);
 int shg_inception_mean_f32(const float* x, float* y, int B, int C, int HW, void* stream);
+/* shg_inception_head_f32: the detector's classifier output (return_features=False): probs [B,C] = softmax(feats [B,D] . w [C,D]^T
+ *   (+ bias [C]; NULL = no_output_bias)) in one launch, one workgroup per image, fp32 FMA; D a multiple of 4, 4 (C + D) + 32 bytes of LDS <= 64 KiB,
+ *   feats and w 16-byte aligned. */
+int shg_inception_head_f32(const float* feats, const float* w, const float* bias, float* probs, int B, int C, int D, void* stream);
+
+/* ---- KID and Inception Score (lib/evaluator/stylegan_metrics/kernel_inception_distance.py:34-44, inception_score.py:30-36;
+ * sh-gan_amd/kid.py and inception_score.py drive them; csrc/kid.hip).
+ * shg_kid_sums_f64: fake [n_f,D], real [n_r,D] (float32, float64 when is_f64; 16-byte aligned; D >= 64, a multiple of 4), idx_f / idx_r
+ *   [S,m] int32 = the rows of subset s on each side (m >= 2, S <= 65535) -> out [S,3] float64 = { sum_{i!=j} k(x_i,x_j),
+ *   sum_{i!=j} k(y_i,y_j), sum_{i,j} k(x_i,y_j) }, k(u,v) = (u.v / D + 1)^3, x / y the gathered fake / real rows.  fp64 MFMA on 64 x 64
+ *   tiles, rows gathered through the index table while staged, the symmetric terms on the upper triangle only; one partial sum per tile
+ *   in `workspace` (shg_kid_workspace_bytes; 0 for invalid arguments), added per subset in a fixed order by a second launch: no atomics,
+ *   the same bits run to run and whichever subsets share the launch.  An index outside [0, n) makes its subset's sums NaN.
+ * shg_is_accumulate_f64: acc [num_splits, C+2] float64 += a batch of probs [B,C] float32; split [B] int32 names each image's split
+ *   (negative = skip).  Columns 0..C-1 = sum_i p_ic, column C = sum_i sum_c p_ic log p_ic (p == 0 contributes 0), column C+1 = the image
+ *   count.  Fixed order over the batch, no atomics. */
+size_t shg_kid_workspace_bytes(int S, int m);
+int shg_kid_sums_f64(const void* fake, const void* real, int is_f64, int n_f, int n_r, int D, const int* idx_f, const int* idx_r, int S, int m,
+                     void* workspace, size_t ws_bytes, double* out, void* stream);
+int shg_is_accumulate_f64(const float* probs, const int* split, double* acc, int B, int C, int num_splits, void* stream);
 
 /* ---- LPIPS, AlexNet backbone: `lpips.LPIPS(net='alex')` as lib/evaluator/eva_lpips.py:39-52 calls it (sh-gan_amd/lpips.py drives it;
  * csrc/lpips.hip).  conv2..conv5 and the max pools run on the detector's convolution and pool entry points above.

@@ -362,3 +362,74 @@ extern "C" int shg_inception_mean_f32(const float* x, float* y, int B, int C, in
     SHG_CHECK_LAUNCH();
     return SHG_OK;
 }
+
+// ---- classifier head (the detector's softmax output, return_features=False): probs [B, C] = softmax(feats [B, D] . w [C, D]^T (+ bias)).
+// One workgroup per image and one launch: the feature row sits in LDS, the waves stride over the classes (lane-strided float4
+// products in four fp32 FMA chains, then a fixed butterfly), the logits stay in LDS, max and sum go through LDS, and the row is
+// normalised on the way out.  B * C * D is far too small for matrix cores to matter; an image's row is the same bits in any batch.
+#define INC_HEAD_THREADS 512
+__device__ __forceinline__ float inc_head_block_reduce(float v, float* red, bool is_max) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const float u = __shfl_xor(v, o, 64);
+        v = is_max ? fmaxf(v, u) : v + u;
+    }
+    __syncthreads();                                   // red may still be read from the previous reduction
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    float r = red[0];
+#pragma unroll
+    for (int w = 1; w < INC_HEAD_THREADS / 64; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
+    return r;
+}
+
+__global__ __launch_bounds__(INC_HEAD_THREADS) void inc_head_kernel(const float* feats, const float* w, const float* bias, float* probs, int C, int D) {
+    extern __shared__ float inc_head_lds[];
+    float* sf = inc_head_lds;                          // [D] the image's pooled features
+    float* sl = inc_head_lds + D;                      // [C] logits, then exp(logit - max)
+    __shared__ float red[INC_HEAD_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    for (int k = tid * 4; k < D; k += INC_HEAD_THREADS * 4)
+        *reinterpret_cast<float4*>(sf + k) = *reinterpret_cast<const float4*>(feats + (long)b * D + k);
+    __syncthreads();
+    for (int c = wave; c < C; c += INC_HEAD_THREADS / 64) {
+        const float* wr = w + (long)c * D;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        for (int k = lane * 4; k < D; k += 256) {
+            const float4 x = *reinterpret_cast<const float4*>(sf + k), y = *reinterpret_cast<const float4*>(wr + k);
+            a0 = fmaf(x.x, y.x, a0);
+            a1 = fmaf(x.y, y.y, a1);
+            a2 = fmaf(x.z, y.z, a2);
+            a3 = fmaf(x.w, y.w, a3);
+        }
+        float a = (a0 + a1) + (a2 + a3);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64);
+        if (lane == 0) sl[c] = bias ? a + bias[c] : a;
+    }
+    __syncthreads();
+    float mx = -__builtin_inff();
+    for (int c = tid; c < C; c += INC_HEAD_THREADS) mx = fmaxf(mx, sl[c]);
+    mx = inc_head_block_reduce(mx, red, true);
+    float sum = 0.f;
+    for (int c = tid; c < C; c += INC_HEAD_THREADS) {
+        const float e = expf(sl[c] - mx);
+        sl[c] = e;                                     // (each thread rereads only what it wrote)
+        sum += e;
+    }
+    sum = inc_head_block_reduce(sum, red, false);
+    for (int c = tid; c < C; c += INC_HEAD_THREADS) probs[(long)b * C + c] = sl[c] / sum;
+}
+
+// feats [B, D] float32 (D a multiple of 4), w [C, D], bias [C] or NULL (no_output_bias), probs [B, C]; 4 (C + D) + 32 bytes of LDS (the
+// two arrays and the reduction scratch) <= 64 KiB.
+extern "C" int shg_inception_head_f32(const float* feats, const float* w, const float* bias, float* probs, int B, int C, int D, void* stream) {
+    SHG_CHECK_ARG(feats && w && probs, "inception_head: null pointer");
+    SHG_CHECK_ARG(B >= 1 && C >= 1 && D >= 4 && D % 4 == 0, "inception_head: need B, C >= 1 and D a positive multiple of 4");
+    SHG_CHECK_ARG(4L * ((long)C + D) + 32 <= 65536, "inception_head: 4 (C + D) + 32 = %ld bytes do not fit 64 KiB of LDS", 4L * ((long)C + D) + 32);
+    SHG_CHECK_ARG(((uintptr_t)feats | (uintptr_t)w) % 16 == 0, "inception_head: feats and w must be 16-byte aligned");
+    hipLaunchKernelGGL(inc_head_kernel, dim3(B), dim3(INC_HEAD_THREADS), (size_t)(C + D) * 4, (hipStream_t)stream, feats, w, bias, probs, C, D);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}

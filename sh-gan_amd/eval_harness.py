@@ -377,12 +377,26 @@ class EvalLoop:
     device, a torch stand-in in the CPU tests -- that writes the batch's float64 values into ``out``.  Per batch, on the batch's own stream
     after the composite, it fills this rank's NaN-initialised ``[n_local]`` buffer at the batch's shard position; ``gather`` carries the
     column in the same all-gather as PSNR / SSIM and sets ``image_metrics['lpips']`` (mean over exactly ``n_items`` in dataset order) and
-    ``['lpips_per_image']`` -- with ``metrics=None`` and with ``keep_images=False`` too."""
+    ``['lpips_per_image']`` -- with ``metrics=None`` and with ``keep_images=False`` too.
+
+    ``kid=True`` or ``kid=dict(num_subsets=100, max_subset_size=1000, seed=0)`` adds the Kernel Inception Distance (stylegan_metrics/
+    kernel_inception_distance.py; needs ``feature_fn`` and ``fid_real=True``): the feature rows the moments are accumulated from are also
+    written, on the batch's stream, into two per-rank float32 buffers ``[n_local, fid_dim]`` at the batch's shard position; ``gather``
+    all-gathers and re-interleaves them to exactly ``n_items`` rows per side and ``kid_value()`` runs kid.kid_from_features on them
+    (``sums_fn`` in the dict replaces the kernel: CPU tests).
+
+    ``inception_score=dict(num_splits=10)`` adds the Inception Score of the fakes (stylegan_metrics/inception_score.py; needs
+    ``feature_fn``): the detector is called once per batch as ``feature_fn(images, with_probs=True) -> (features, probabilities)`` -- one
+    run of the trunk -- and the probabilities go into a per-stream float64 ``[num_splits, C + 2]`` accumulator (inception_score.py of this
+    package; an image's split follows its dataset position, padded duplicates are skipped).  ``C`` is ``feature_fn.num_classes`` or the
+    dict's ``num_classes``; ``no_output_bias`` (default True, as the reference) is passed on when given; ``accumulate_fn(acc, probs,
+    splits)`` replaces the kernel (CPU tests).  ``gather`` adds the streams' accumulators and all-reduces the sum once; ``is_value()`` ->
+    (mean, std).  With both options absent no buffer is allocated and no launch is added."""
 
     def __init__(self, G, device, resolution, n_items, rank=0, world=1, noise_mode='random', seed=0, depth=None, feature_fn=None,
                  fid_dim=2048, latent_fn=None, device_masks=True, hole_range=(0, 1), keep_images=True, on_batch=None, step_fn=None,
                  fid_accumulate_fn=None, feeder_stream=False, timing=False, metrics=None, ssim_window=11, metrics_fn=None, fid_real=False,
-                 lpips=None):
+                 lpips=None, kid=None, inception_score=None):
         from .datasets import DeviceFeeder
         self.timing, self.batch_done_events = timing, []      # timing: one timing event per finished batch (bench: steady-state rate)
         self.G, self.device, self.res = G, torch.device(device), int(resolution)
@@ -412,6 +426,35 @@ class EvalLoop:
             raise ValueError('EvalLoop: lpips must be a callable lpips(pred_u8, real, out=slice)')
         self.lpips_fn = lpips
         self.lpips_values = (torch.full((len(self.ids),), float('nan'), dtype=torch.float64, device=self.device) if lpips is not None else None)
+        self.kid_opts = None            # kid: per-rank feature rows of both sides, the gathered [n_items, fid_dim] pair after gather()
+        self._kid_local = self.kid_features = None
+        if kid:
+            if feature_fn is None or not fid_real:
+                raise ValueError('EvalLoop: kid needs a feature_fn (the detector) and fid_real=True (the real side\'s features)')
+            self.kid_opts = dict(kid) if isinstance(kid, dict) else {}
+            unknown = set(self.kid_opts) - {'num_subsets', 'max_subset_size', 'seed', 'sums_fn'}
+            if unknown:
+                raise ValueError(f'EvalLoop: unknown kid option(s) {sorted(unknown)}')
+            self._kid_local = tuple(torch.zeros((len(self.ids), self.fid_dim), dtype=torch.float32, device=self.device) for _ in range(2))
+        self.is_opts = None             # inception_score: per-stream [num_splits, C + 2] accumulators, their all-reduced sum after gather()
+        self._is_parts, self.is_acc, self._is_splits = {}, None, None
+        if inception_score:
+            if feature_fn is None:
+                raise ValueError('EvalLoop: inception_score needs a feature_fn (the detector with its classifier head)')
+            self.is_opts = dict(inception_score) if isinstance(inception_score, dict) else {}
+            unknown = set(self.is_opts) - {'num_splits', 'num_classes', 'no_output_bias', 'accumulate_fn'}
+            if unknown:
+                raise ValueError(f'EvalLoop: unknown inception_score option(s) {sorted(unknown)}')
+            self.is_opts.setdefault('num_splits', 10)
+            if self.is_opts.get('num_classes') is None:
+                self.is_opts['num_classes'] = getattr(feature_fn, 'num_classes', None)
+            if self.is_opts['num_classes'] is None:
+                raise ValueError('EvalLoop: inception_score needs the class count (feature_fn.num_classes or num_classes=...): the detector '
+                                 'has no classifier head')
+            from .inception_score import split_of
+            # item k of this rank sits at dataset position k * world + rank; positions past n_items are padded duplicates (-1: skipped)
+            self._is_splits = torch.tensor([split_of(k * self.world + self.rank, self.n_items, self.is_opts['num_splits'])
+                                            for k in range(len(self.ids))], dtype=torch.int32).to(self.device)
 
     def _fid_part(self, key, real=False):
         from .fid_stats import FidStats
@@ -419,6 +462,28 @@ class EvalLoop:
         if key not in parts:
             parts[key] = FidStats(self.fid_dim, device=self.device, accumulate_fn=self._fid_fn)
         return parts[key]
+
+    def _is_part(self, key):
+        from .inception_score import new_accumulator
+        if key not in self._is_parts:
+            self._is_parts[key] = new_accumulator(self.is_opts['num_splits'], self.is_opts['num_classes'], self.device)
+        return self._is_parts[key]
+
+    def _fake_features(self, out, k0, cur):
+        """The detector on a batch of fakes: features for the moments (and KID); with ``inception_score`` the same run's probabilities go
+        into this stream's accumulator."""
+        kw = {'no_output_bias': self.is_opts['no_output_bias']} if 'no_output_bias' in self.is_opts else {}
+        feats, probs = self.feature_fn(out, with_probs=True, **kw)
+        acc = self._is_parts.get(cur)
+        if acc is None:
+            acc = self._is_part(None)
+        splits = self._is_splits[k0:k0 + probs.shape[0]]
+        if self.is_opts.get('accumulate_fn') is not None:
+            self.is_opts['accumulate_fn'](acc, probs, splits)
+        else:
+            from .inception_score import is_accumulate
+            is_accumulate(acc, probs, splits)
+        return feats
 
     def run(self, loader):
         """``loader`` yields this rank's items in ``shard_ids`` order as (images [B,3,R,R] uint8 or float32 in [-1,1], ids) or
@@ -432,6 +497,8 @@ class EvalLoop:
                 self._fid_part(key)
                 if self.fid_real_on:
                     self._fid_part(key, real=True)
+                if self.is_opts is not None:
+                    self._is_part(key)
         for x4, real, mask, ids in self.feeder(loader):
             b, k0 = x4.shape[0], self.seen
             if k0 + b > len(self.ids):
@@ -445,10 +512,16 @@ class EvalLoop:
                 if self.feature_fn is not None:
                     cur = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == 'cuda' else None
                     part = self._fid_parts.get(cur) or self._fid_part(None)
-                    part.add_shard(self.feature_fn(out), k0, self.rank, self.world, self.n_items)
+                    feats = self.feature_fn(out) if self.is_opts is None else self._fake_features(out, k0, cur)
+                    part.add_shard(feats, k0, self.rank, self.world, self.n_items)
+                    if self._kid_local is not None:
+                        self._kid_local[0][k0:k0 + feats.shape[0]].copy_(feats)
                     if self.fid_real_on:
                         part = self._fid_real_parts.get(cur) or self._fid_part(None, real=True)
-                        part.add_shard(self.feature_fn(real_, input_range='pm1'), k0, self.rank, self.world, self.n_items)
+                        feats = self.feature_fn(real_, input_range='pm1')
+                        part.add_shard(feats, k0, self.rank, self.world, self.n_items)
+                        if self._kid_local is not None:
+                            self._kid_local[1][k0:k0 + feats.shape[0]].copy_(feats)
                 if real_ is not None and self.metrics is not None:
                     self.metrics.add(out, real_, k0)
                 if self.lpips_fn is not None:
@@ -497,7 +570,47 @@ class EvalLoop:
             self.fid_real.all_reduce()
         if self.metrics is not None or self.lpips_fn is not None:
             self.image_metrics = self._gather_metrics(use)
+        if self._kid_local is not None:
+            self.kid_features = tuple(self._gather_rows(t, use) for t in self._kid_local)
+            self._kid_local = None
+        if self.is_opts is not None and self._is_parts:
+            parts = list(self._is_parts.values())
+            acc = parts.pop(0)
+            for p in parts:
+                acc += p
+            if use:
+                via_host = dist.get_backend() == 'gloo' and acc.is_cuda
+                h = acc.cpu() if via_host else acc
+                dist.all_reduce(h, op=dist.ReduceOp.SUM)
+                acc = h.to(self.device)
+            self.is_acc, self._is_parts = acc, {}
         return images, self.fid
+
+    def _gather_rows(self, local, use):
+        """This rank's [n_local, ...] rows -> [n_items, ...] in dataset order on the device (one all-gather + zipzap_device)."""
+        import torch.distributed as dist
+        if not use:
+            return zipzap_device(local[None], self.n_items)
+        via_host = dist.get_backend() == 'gloo' and local.is_cuda
+        src = local.cpu() if via_host else local
+        full = torch.empty((self.world,) + tuple(src.shape), dtype=src.dtype, device=src.device)
+        dist.all_gather_into_tensor(full.view((-1,) + tuple(src.shape[1:])), src)
+        return zipzap_device(full.to(self.device), self.n_items)
+
+    def kid_value(self):
+        """The KID of the gathered features (after ``gather``; ``kid=...``): exactly ``n_items`` rows per side in dataset order."""
+        from .kid import kid_from_features
+        if self.kid_features is None:
+            raise ValueError('EvalLoop.kid_value: needs kid=True (or its options) and a finished gather()')
+        fake, real = self.kid_features
+        return kid_from_features(fake.contiguous(), real.contiguous(), **self.kid_opts)
+
+    def is_value(self):
+        """(mean, std) of the Inception Score over the splits (after ``gather``; ``inception_score=...``)."""
+        from .inception_score import is_from_accumulator
+        if self.is_acc is None:
+            raise ValueError('EvalLoop.is_value: needs inception_score=dict(...) and a finished gather()')
+        return is_from_accumulator(self.is_acc)
 
     def _gather_metrics(self, use):
         import torch.distributed as dist

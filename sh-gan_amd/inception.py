@@ -16,12 +16,14 @@ it was NOT checked against the detector file itself, which is a download.
 Body: the FID variant of Inception-v3 (pytorch-fid's ``FIDInception*`` blocks): stem, Mixed_5b-5d, 6a, 6b-6e, 7a, 7b, 7c, global
 average pool -> 2048; every convolution is followed by BatchNorm (eps 1e-3) and ReLU; the pool branches of the A, C and Mixed_7b blocks
 average over the in-bounds taps (``count_include_pad=False``), Mixed_7c's pool branch is a 3 x 3 max pool; branches are concatenated in
-torchvision order; no classifier.
+torchvision order.  The classifier head (``fc.weight`` [C, 2048], ``fc.bias`` [C]) is optional: with it ``return_features=False`` gives
+the softmax probabilities [B, C] the Inception Score needs (one more launch on the pooled features; C = 1008 for the 2015 graph, 1000 for a
+torchvision file); without it that call raises.
 
 Weights: a ``state_dict`` in the torchvision / pytorch-fid key layout (``Conv2d_1a_3x3.conv.weight``, ``Conv2d_1a_3x3.bn.{weight, bias,
-running_mean, running_var}``, ..., ``Mixed_7c.branch_pool.*``; ``fc.*`` and ``AuxLogits.*`` are ignored, ``bn.num_batches_tracked`` is
-accepted).  This is the layout of pytorch-fid's ``pt_inception-2015-12-05-*.pth`` port of the TF weights; it was not checked against
-that file here.  BatchNorm is folded into the convolution weight and a per-channel bias once, on the host in float64."""
+running_mean, running_var}``, ..., ``Mixed_7c.branch_pool.*``; ``AuxLogits.*`` is ignored, ``fc.*`` is the optional head,
+``bn.num_batches_tracked`` is accepted).  This is the layout of pytorch-fid's ``pt_inception-2015-12-05-*.pth`` port of the TF weights; it was not checked against
+that file here, and neither was the head's key name (``fc``; the TorchScript detector may call its last layer otherwise).  BatchNorm is folded into the convolution weight and a per-channel bias once, on the host in float64."""
 import collections
 
 import torch
@@ -93,25 +95,41 @@ def _spec():
 LAYERS = _spec()
 BN_KEYS = ('weight', 'bias', 'running_mean', 'running_var')
 IGNORED_PREFIXES = ('fc.', 'AuxLogits.')
+HEAD_WEIGHT, HEAD_BIAS = 'fc.weight', 'fc.bias'      # the classifier head (optional; probabilities need it)
 
 
 def out_size(h, k, s, p):
     return (h + 2 * p - k) // s + 1
 
 
-def expected_shapes():
-    """state_dict key -> shape of every tensor the detector reads (``bn.num_batches_tracked`` is optional)."""
+def expected_shapes(head_classes=None):
+    """state_dict key -> shape of every tensor the detector reads (``bn.num_batches_tracked`` is optional); with ``head_classes`` = C
+    also the classifier head's ``fc.weight`` [C, 2048] and ``fc.bias`` [C]."""
     shapes = collections.OrderedDict()
     for name, (i, o, (kh, kw), _, _, _) in LAYERS.items():
         shapes[f'{name}.conv.weight'] = (o, i, kh, kw)
         for k in BN_KEYS:
             shapes[f'{name}.bn.{k}'] = (o,)
+    if head_classes is not None:
+        shapes[HEAD_WEIGHT] = (int(head_classes), DIM)
+        shapes[HEAD_BIAS] = (int(head_classes),)
     return shapes
 
 
-def validate_state_dict(sd):
-    """Raises ShgError naming the first missing key, unexpected key or wrong shape."""
+def validate_state_dict(sd, head=False):
+    """Raises ShgError naming the first missing key, unexpected key or wrong shape.  ``head=True`` also asks for the classifier head:
+    ``fc.weight`` [C, 2048] with any C >= 1 and ``fc.bias`` [C] (without it ``fc.*`` is ignored, whatever it holds)."""
     want = expected_shapes()
+    if head:
+        if HEAD_WEIGHT not in sd:
+            raise ShgError(f'inception: state_dict lacks {HEAD_WEIGHT!r} (the classifier head)')
+        w = sd[HEAD_WEIGHT]
+        if w.ndim != 2 or w.shape[0] < 1 or w.shape[1] != DIM:
+            raise ShgError(f'inception: {HEAD_WEIGHT!r} has shape {tuple(w.shape)}, expected (C, {DIM})')
+        if HEAD_BIAS not in sd:
+            raise ShgError(f'inception: state_dict lacks {HEAD_BIAS!r} (the classifier head)')
+        if tuple(sd[HEAD_BIAS].shape) != (w.shape[0],):
+            raise ShgError(f'inception: {HEAD_BIAS!r} has shape {tuple(sd[HEAD_BIAS].shape)}, expected {(w.shape[0],)}')
     for key in want:
         if key not in sd:
             raise ShgError(f'inception: state_dict lacks {key!r}')
@@ -237,6 +255,19 @@ def global_mean(x):
     return y
 
 
+def head_probs(feats, w, bias=None):
+    """softmax(feats [B, D] @ w [C, D].T (+ bias [C])) -> [B, C] float32 in one launch (csrc/inception.hip: one workgroup per image)."""
+    L = kernels._Launch()
+    feats, w, bias = L.req(feats, 'feats'), L.req(w, 'head weight'), L.req(bias, 'head bias')
+    if feats.ndim != 2 or w.ndim != 2 or w.shape[1] != feats.shape[1] or (bias is not None and tuple(bias.shape) != (w.shape[0],)):
+        raise ShgError(f'inception: head: feats [B, D], weight [C, D], bias [C] (got {tuple(feats.shape)}, {tuple(w.shape)})')
+    probs = L.new((feats.shape[0], w.shape[0]))
+    with L:
+        check(_lib.get_lib().shg_inception_head_f32(kernels._ptr(feats), kernels._ptr(w), kernels._ptr(bias), kernels._ptr(probs), feats.shape[0],
+                                                    w.shape[0], feats.shape[1], L.stream()), 'inception_head')
+    return probs
+
+
 _LUTS = {}
 
 
@@ -283,24 +314,46 @@ class InceptionFeatures:
     itself.  ``split_k=False`` keeps every launch plan independent of the batch size (an image's features are then the same bits in any
     batch); the default splits K in launches too small to fill the chip."""
 
-    def __init__(self, ops, device, split_k=True):
+    def __init__(self, ops, device, split_k=True, head=None):
         self.ops, self.device, self.split_k = ops, torch.device(device), split_k
+        self.head = head                # (weight [C, 2048], bias [C]) float32 on the device, or None: features only
+
+    @property
+    def num_classes(self):
+        return None if self.head is None else int(self.head[0].shape[0])
 
     @classmethod
     def from_state_dict(cls, sd, device='cuda', split_k=True):
-        validate_state_dict(sd)
+        validate_state_dict(sd, head=HEAD_WEIGHT in sd)
         ops = collections.OrderedDict()
         for name, (i, o, k, s, p, _) in LAYERS.items():
             w, b = fold_bn(sd[f'{name}.conv.weight'], *(sd[f'{name}.bn.{k_}'] for k_ in BN_KEYS))
             wp, bp = pack_weight(w.to(torch.float32).to(device), b.to(torch.float32).to(device))
             ops[name] = ConvOp(name, wp, bp, i, o, k, s, p)
-        return cls(ops, device, split_k)
+        head = None
+        if HEAD_WEIGHT in sd:
+            head = tuple(torch.as_tensor(sd[k]).detach().to(torch.float32).to(device).contiguous() for k in (HEAD_WEIGHT, HEAD_BIAS))
+        return cls(ops, device, split_k, head)
 
-    def __call__(self, images, return_features=True, input_range='0_255'):
-        if not return_features:
-            raise ShgError('inception: only the 2048-d pool features are built (return_features=True); the classifier is not')
+    def __call__(self, images, return_features=True, input_range='0_255', no_output_bias=True, with_probs=False):
+        """``return_features=True``: the pooled features [B, 2048].  ``return_features=False``: the classifier's softmax probabilities
+        [B, C] float32, without the output bias by default (the reference's Inception Score passes ``no_output_bias=True``,
+        inception_score.py:21).  ``with_probs=True``: (features, probabilities) of ONE run of the trunk (EvalLoop with FID / KID and the
+        Inception Score on the same images)."""
+        if (with_probs or not return_features) and self.head is None:
+            raise ShgError(f'inception: the softmax probabilities need the classifier head, and the state_dict had no {HEAD_WEIGHT!r}')
         with torch.no_grad():
-            return self.forward(frontend(images, input_range))
+            feats = self.forward(frontend(images, input_range))
+            if return_features and not with_probs:
+                return feats
+            probs = self.probs(feats, no_output_bias)
+        return (feats, probs) if with_probs else probs
+
+    def probs(self, feats, no_output_bias=True):
+        """Pooled features [B, 2048] -> softmax probabilities [B, C] (one launch)."""
+        if self.head is None:
+            raise ShgError(f'inception: the softmax probabilities need the classifier head, and the state_dict had no {HEAD_WEIGHT!r}')
+        return head_probs(feats, self.head[0], None if no_output_bias else self.head[1])
 
     def _new(self, B, C, H, W):
         return torch.empty((B, C, H, W), dtype=torch.float32, device=self.device)
