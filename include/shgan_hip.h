@@ -369,6 +369,33 @@ int shg_kid_sums_f64(const void* fake, const void* real, int is_f64, int n_f, in
                      void* workspace, size_t ws_bytes, double* out, void* stream);
 int shg_is_accumulate_f64(const float* probs, const int* split, double* acc, int B, int C, int num_splits, void* stream);
 
+/* ---- Improved precision / recall, `pr50k3_full` (lib/evaluator/stylegan_metrics/precision_recall.py:19-60; sh-gan_amd/
+ * precision_recall.py drives them; csrc/pr.hip).  Rows are fp16 [n,D], 16-byte aligned, D >= 64 a multiple of 8.  d16(i,j) = the
+ *   Euclidean distance as sqrt(max(0, |a|^2 + |b|^2 - 2 a.b)) -- a.b on the fp16 MFMA (exact products, fp32 sums), fp32 row norms --
+ *   rounded ONCE to fp16.
+ * shg_pr_radii_f16: radii_out [n] fp16 = the (k + 1)-th smallest d16(j, .) over all n rows, j itself included (line 53);
+ *   1 <= k <= 15, n >= k + 1; workspace of shg_pr_workspace_bytes(n, n, k).
+ * shg_pr_inside_f16: inside_out [m] uint8 = 1 when some manifold row j has d16(p, j) <= radii[j], compared as fp16 values (line 58);
+ *   m >= 1, n >= 2; workspace of shg_pr_workspace_bytes(m, n, 0).
+ *   A workgroup owns 128 points and sweeps a slice of the other side on 128 x 128 MFMA tiles; a point's k + 1 smallest distances (its
+ *   flag) stay in registers, no distance reaches memory; one partial result per slice in `workspace`, merged in slice order by a
+ *   last launch.  The slice count follows the swept side's row count alone.  No atomics: the same bits run to run.
+ * shg_pr_workspace_bytes(m, n, k): k >= 1 the radii call on n rows (m is not read), k == 0 the inside call; 0 for invalid arguments. */
+size_t shg_pr_workspace_bytes(int m, int n, int k);
+int shg_pr_radii_f16(const void* feats, int n, int D, int k, void* workspace, size_t ws_bytes, void* radii_out, void* stream);
+int shg_pr_inside_f16(const void* probes, int m, const void* manifold, int n, int D, const void* radii, void* workspace, size_t ws_bytes,
+                      unsigned char* inside_out, void* stream);
+
+/* ---- VGG16 up to fc2, the detector of `pr50k3_full` (precision_recall.py:64-76; sh-gan_amd/vgg16.py drives it; csrc/vgg16.hip).  The
+ * 13 convolutions run on shg_inception_conv_f32 after shg_inception_weight_prep_f32, fc1 / fc2 on shg_dense_f32.
+ * shg_vgg16_frontend_f32: x [B,3,H,W] -> y [B,3,224,224] = (area(v) - mean[c]) / std[c]; v as shg_inception_frontend_f32 (lut [256]
+ *   for uint8 x, else x*scale + bias); area = F.interpolate(mode='area'): the mean over the bin [floor(i*H/224), ceil((i+1)*H/224)) on
+ *   each axis, exact bins for any ratio; mean / std [3] host floats, std > 0.
+ * shg_vgg16_maxpool2_f32: y [B,C,H/2,W/2] = 2 x 2 max pool, stride 2, of x [B,C,H,W] (floor: an odd last row / column is dropped). */
+int shg_vgg16_frontend_f32(const void* x, const float* lut, float scale, float bias, const float* mean, const float* stdv, float* y, int B,
+                           int H, int W, void* stream);
+int shg_vgg16_maxpool2_f32(const float* x, float* y, int B, int C, int H, int W, void* stream);
+
 /* ---- LPIPS, AlexNet backbone: `lpips.LPIPS(net='alex')` as lib/evaluator/eva_lpips.py:39-52 calls it (sh-gan_amd/lpips.py drives it;
  * csrc/lpips.hip).  conv2..conv5 and the max pools run on the detector's convolution and pool entry points above.
  * Conv1 weight prep: w [64,3,11,11], bias [64] -> wp [SHG_LPIPS_CONV1_WP_ELEMS] floats ([368][64], k = (ky*11 + kx)*3 + c, zero

@@ -128,6 +128,11 @@ _SIGS = {
     'shg_kid_workspace_bytes': [c_i, c_i],
     'shg_kid_sums_f64': [c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_fp, ctypes.c_size_t, c_fp, c_fp],
     'shg_is_accumulate_f64': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
+    'shg_pr_workspace_bytes': [c_i, c_i, c_i],
+    'shg_pr_radii_f16': [c_fp, c_i, c_i, c_i, c_fp, ctypes.c_size_t, c_fp, c_fp],
+    'shg_pr_inside_f16': [c_fp, c_i, c_fp, c_i, c_i, c_fp, c_fp, ctypes.c_size_t, c_fp, c_fp],
+    'shg_vgg16_frontend_f32': [c_fp, c_fp, c_f, c_f, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp, c_i, c_i, c_i, c_fp],
+    'shg_vgg16_maxpool2_f32': [c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
     'shg_lpips_conv1_weight_prep_f32': [c_fp, c_fp, c_fp, c_fp, c_fp],
     'shg_lpips_conv1_f32': [c_fp, c_fp, c_f, c_f, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_lpips_head_scratch_bytes': [c_i] * 3,
@@ -195,6 +200,7 @@ def get_lib():
     lib.shg_lpips_head_scratch_bytes.restype = ctypes.c_size_t
     lib.shg_inception_conv_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_kid_workspace_bytes.restype = ctypes.c_size_t
+    lib.shg_pr_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_inception_packed_weight_elems.restype = c_l
     lib.shg_conv2d_f16_packed_weight_elems.restype = c_l
     lib.shg_conv_wino4_weight_elems.restype = c_l

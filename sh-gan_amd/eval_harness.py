@@ -391,12 +391,20 @@ class EvalLoop:
     package; an image's split follows its dataset position, padded duplicates are skipped).  ``C`` is ``feature_fn.num_classes`` or the
     dict's ``num_classes``; ``no_output_bias`` (default True, as the reference) is passed on when given; ``accumulate_fn(acc, probs,
     splits)`` replaces the kernel (CPU tests).  ``gather`` adds the streams' accumulators and all-reduces the sum once; ``is_value()`` ->
-    (mean, std).  With both options absent no buffer is allocated and no launch is added."""
+    (mean, std).  With both options absent no buffer is allocated and no launch is added.
+
+    ``pr=dict(detector=vgg, nhood_size=3)`` adds the improved precision and recall (stylegan_metrics/precision_recall.py, ``pr50k3_full``;
+    independent of ``feature_fn``, ``kid`` and ``fid_real``): per batch, on the batch's own stream after the composite,
+    ``detector(images)`` and ``detector(real, input_range='pm1')`` (``vgg16.Vgg16Features``, or any callable of that form) are rounded to
+    float16 into two per-rank buffers ``[n_local, dim]`` at the batch's shard position -- one real per fake; ``dim`` is ``detector.dim`` or
+    the dict's ``dim``.  ``gather`` all-gathers and re-interleaves them to exactly ``n_items`` rows per side and ``pr_value()`` ->
+    (precision, recall) runs precision_recall.pr_from_features on them on this device (the manifold sweep is not sharded over the ranks;
+    ``kernels_fn`` in the dict replaces the kernels: CPU tests).  With ``pr=None`` the loop is the loop it was."""
 
     def __init__(self, G, device, resolution, n_items, rank=0, world=1, noise_mode='random', seed=0, depth=None, feature_fn=None,
                  fid_dim=2048, latent_fn=None, device_masks=True, hole_range=(0, 1), keep_images=True, on_batch=None, step_fn=None,
                  fid_accumulate_fn=None, feeder_stream=False, timing=False, metrics=None, ssim_window=11, metrics_fn=None, fid_real=False,
-                 lpips=None, kid=None, inception_score=None):
+                 lpips=None, kid=None, inception_score=None, pr=None):
         from .datasets import DeviceFeeder
         self.timing, self.batch_done_events = timing, []      # timing: one timing event per finished batch (bench: steady-state rate)
         self.G, self.device, self.res = G, torch.device(device), int(resolution)
@@ -455,6 +463,27 @@ class EvalLoop:
             # item k of this rank sits at dataset position k * world + rank; positions past n_items are padded duplicates (-1: skipped)
             self._is_splits = torch.tensor([split_of(k * self.world + self.rank, self.n_items, self.is_opts['num_splits'])
                                             for k in range(len(self.ids))], dtype=torch.int32).to(self.device)
+
+        self.pr_opts = None             # pr: per-rank float16 feature rows of both sides, the gathered [n_items, dim] pair after gather()
+        self._pr_local = self.pr_features = self._pr_fn = None
+        if pr:
+            if not isinstance(pr, dict):
+                raise ValueError('EvalLoop: pr must be a dict(detector=..., nhood_size=3)')
+            self.pr_opts = dict(pr)
+            unknown = set(self.pr_opts) - {'detector', 'nhood_size', 'dim', 'kernels_fn'}
+            if unknown:
+                raise ValueError(f'EvalLoop: unknown pr option(s) {sorted(unknown)}')
+            self._pr_fn = self.pr_opts.pop('detector', None)
+            if not callable(self._pr_fn):
+                raise ValueError('EvalLoop: pr needs detector=..., a callable detector(images, input_range=None) -> [B, dim]')
+            dim = self.pr_opts.pop('dim', None)
+            dim = getattr(self._pr_fn, 'dim', None) if dim is None else dim
+            if dim is None:
+                raise ValueError('EvalLoop: pr needs the feature width (detector.dim or dim=...)')
+            self.pr_opts.setdefault('nhood_size', 3)
+            if not 1 <= int(self.pr_opts['nhood_size']) <= 15:
+                raise ValueError(f"EvalLoop: pr nhood_size must be 1..15 (got {self.pr_opts['nhood_size']})")
+            self._pr_local = tuple(torch.zeros((len(self.ids), int(dim)), dtype=torch.float16, device=self.device) for _ in range(2))
 
     def _fid_part(self, key, real=False):
         from .fid_stats import FidStats
@@ -526,8 +555,11 @@ class EvalLoop:
                     self.metrics.add(out, real_, k0)
                 if self.lpips_fn is not None:
                     self.lpips_fn(out, real_, out=self.lpips_values[k0:k0 + out.shape[0]])
+                if self._pr_local is not None:
+                    self._pr_local[0][k0:k0 + out.shape[0]].copy_(self._pr_fn(out))
+                    self._pr_local[1][k0:k0 + out.shape[0]].copy_(self._pr_fn(real_, input_range='pm1'))
                 return out
-            need_real = self.metrics is not None or self.fid_real_on or self.lpips_fn is not None
+            need_real = self.metrics is not None or self.fid_real_on or self.lpips_fn is not None or self._pr_local is not None
             out = pipe.run(step, x4, z, real) if need_real else pipe.run(step, x4, z)
             if self.timing and self.device.type == 'cuda':
                 tev = torch.cuda.Event(enable_timing=True)
@@ -573,6 +605,9 @@ class EvalLoop:
         if self._kid_local is not None:
             self.kid_features = tuple(self._gather_rows(t, use) for t in self._kid_local)
             self._kid_local = None
+        if self._pr_local is not None:
+            self.pr_features = tuple(self._gather_rows(t, use) for t in self._pr_local)
+            self._pr_local = None
         if self.is_opts is not None and self._is_parts:
             parts = list(self._is_parts.values())
             acc = parts.pop(0)
@@ -604,6 +639,15 @@ class EvalLoop:
             raise ValueError('EvalLoop.kid_value: needs kid=True (or its options) and a finished gather()')
         fake, real = self.kid_features
         return kid_from_features(fake.contiguous(), real.contiguous(), **self.kid_opts)
+
+    def pr_value(self):
+        """(precision, recall) of the gathered features (after ``gather``; ``pr=dict(...)``): exactly ``n_items`` rows per side in dataset
+        order, fakes against reals."""
+        from .precision_recall import pr_from_features
+        if self.pr_features is None:
+            raise ValueError('EvalLoop.pr_value: needs pr=dict(detector=...) and a finished gather()')
+        fake, real = self.pr_features
+        return pr_from_features(real.contiguous(), fake.contiguous(), **self.pr_opts)
 
     def is_value(self):
         """(mean, std) of the Inception Score over the splits (after ``gather``; ``inception_score=...``)."""
