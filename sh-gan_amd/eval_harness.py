@@ -3,11 +3,14 @@ lib/experiments/shgan_default.py:257-289 -- input assembly, generator call, uint
 batch-sharded multi-GPU loop (one process per GPU, rank-strided samples, no collective on the data
 path; an optional all-gather returns the uint8 results in dataset order: RCCL over xGMI on GPUs,
 gloo on the CPU for the world-size-2 tests)."""
+from operator import attrgetter
+
 import numpy as np
 import torch
 
 from . import kernels
 from .data import DistributedSampler, RandomMask, zipzap_arrange
+from .evaluators import Collective, DetectorStats, PerImageColumns, PrecisionRecall, zipzap_device  # noqa: F401 (zipzap_device: re-exported)
 
 
 def assemble_input(real, mask):
@@ -289,14 +292,6 @@ def sharded_eval(G, n_items, batch_size, resolution, rank=0, world=1, seed=0, ga
     return order, merged
 
 
-def zipzap_device(full, n_items):
-    """``zipzap_arrange`` (eva_base.py:196-230) of equally long rank shards, on the device: full [world, n_local, ...] (rank r's
-    k-th result at [r, k]) -> [n_items, ...] in dataset order (item k*world + r), the padded duplicates of
-    ``DistributedSampler(extend=True)`` cut off.  One transposing copy instead of a host round trip of the whole result set."""
-    world, n_local = full.shape[:2]
-    return full.transpose(0, 1).reshape((world * n_local,) + tuple(full.shape[2:]))[:n_items]
-
-
 def standin_features(images_u8, dim=2048):
     """Stand-in for the feature detector of the FID stage (eva_fid.py:145-158,194-206: an Inception-v3 TorchScript download, not
     reproducible offline): a fixed linear map of the uint8 images to [B, dim] -- the mean of ``dim`` contiguous pixel runs.  It only
@@ -341,6 +336,19 @@ def broadcast_state(module, src=0, group=None):
     return total
 
 
+def _of(name, attr):                # read-only EvalLoop property: that attribute of the evaluator ``name``, None while its option is off
+    return property(lambda self: attrgetter(attr)(self.evaluators[name]) if name in self.evaluators else None)
+
+
+def _value_of(name, method, needs):  # EvalLoop.<method>(): the evaluator's value (after ``gather``); ValueError before it or with the option off
+    def value(self):
+        v = getattr(self.evaluators[name], method)() if name in self.evaluators else None
+        if v is None:
+            raise ValueError(f'EvalLoop.{method}: needs {needs} and a finished gather()')
+        return v
+    return value
+
+
 class EvalLoop:
     """The evaluation loop the path exists for (lib/experiments/shgan_default.py:264-300; BASELINE config 4 = one rank of it), as a
     streamed loop on ONE rank's shard:
@@ -348,58 +356,20 @@ class EvalLoop:
         per batch   loader (host: decoded uint8 or float images, ids)  ->  H2D on the copy stream under the previous batch's kernels
                     (datasets.DeviceFeeder)  ->  freeform masks drawn on the device (masks.random_masks, the reference's numpy
                     draws in its order)  ->  x = cat([mask - .5, real * mask])  ->  z ~ N(0, 1)  ->  G + uint8 composite written
-                    INTO the rank's result buffer at the batch's position  ->  features (``feature_fn``, the detector hand-off of
-                    eva_fid.py:194-206)  ->  fp64 moments on the device (fid_stats.FidStats; padded duplicates weigh 0);
-        at the end  ONE all-reduce of the moments and ONE all-gather of the uint8 results + the zipzap re-interleave on the device
-                    (the reference: 3 x world broadcasts per batch, eva_base.py:96-188, python lists on rank 0).
+                    INTO the rank's result buffer at the batch's position  ->  every evaluator's ``add`` on the batch's own stream;
+        at the end  ONE all-gather of the uint8 results + the zipzap re-interleave on the device, then one collective per evaluator
+                    result (the reference: 3 x world broadcasts per batch, eva_base.py:96-188, python lists on rank 0).
 
-    Consecutive batches are issued round-robin on ``depth`` HIP streams (StreamPipeline, every batch on a side stream); the moment
-    kernel accumulates in place, so every stream owns a partial accumulator (33.6 MB of float64 each) and ``gather`` adds them up.
-    The only point where the host waits for the device is the mask rasteriser's hole-count read (one small D2H per batch), and it
-    waits on the COPY stream, which carries nothing but input staging.  The loop uses five streams -- caller's, copy, three for the
-    generator; a sixth (a statistics stream, the first form of this loop) made the staging stream share a hardware queue with a
-    generator stream and the hole-count read waited for a whole batch (MEASUREMENTS.md, round 6).  ``latent_fn(ids, B) -> z``
-    replaces ``torch.randn`` (tests: per-item latents so that a result can be compared id by id); ``on_batch(ids, images_u8, event)``
-    hands every finished batch to a consumer (host metrics) without ending the loop.
+    Consecutive batches are issued round-robin on ``depth`` HIP streams (StreamPipeline, every batch on a side stream).  The only point where the
+    host waits for the device is the mask rasteriser's hole-count read (one small D2H per batch), and it waits on the COPY stream, which carries
+    nothing but input staging.  The loop uses five streams -- caller's, copy, three for the generator; a sixth (a statistics stream, the first
+    form of this loop) made the staging stream share a hardware queue with a generator stream and the hole-count read waited for a whole batch
+    (MEASUREMENTS.md, round 6).  ``latent_fn(ids, B) -> z`` replaces ``torch.randn`` (tests: per-item latents so that a result can be compared
+    id by id); ``on_batch(ids, images_u8, event)`` hands every finished batch to a consumer (host metrics) without ending the loop.
 
-    ``metrics=('psnr', 'ssim')`` (or a subset) adds the image-quality evaluators of the reference (eva_psnr.py / eva_ssim.py on the
-    evaluator batch of shgan_default.py:279-291): per batch, on the batch's own stream, one HIP launch pair (image_metrics.py) writes the
-    per-image values of the composite against ``real`` into a per-rank float64 buffer at the batch's position; ``gather`` all-gathers
-    those buffers once, re-interleaves them to dataset order and sets ``image_metrics`` -- independent of ``keep_images``.
-    ``metrics_fn(pred, gt, window_size, psnr_out, ssim_out)`` replaces the kernel (CPU tests).
-
-    ``fid_real=True`` adds the real side of the FID (eva_fid.py's ``compute_fid`` without its cache file): per batch, on the batch's own
-    stream, ``feature_fn(real, input_range='pm1')`` (the detector maps [-1, 1] floats, or a loader's decoded uint8 pixels, as the
-    reference's ``real*127.5 + 127.5``) into per-stream partial moments, padded duplicates weighing 0; ``gather`` all-reduces both sides
-    once each (``self.fid`` fake, ``self.fid_real`` real) and ``fid_value()`` gives the FID.
-
-    ``lpips=net`` adds the fourth evaluator (eva_lpips.py): any callable ``lpips(pred_u8, real, out=slice)`` -- ``lpips.Lpips`` on the
-    device, a torch stand-in in the CPU tests -- that writes the batch's float64 values into ``out``.  Per batch, on the batch's own stream
-    after the composite, it fills this rank's NaN-initialised ``[n_local]`` buffer at the batch's shard position; ``gather`` carries the
-    column in the same all-gather as PSNR / SSIM and sets ``image_metrics['lpips']`` (mean over exactly ``n_items`` in dataset order) and
-    ``['lpips_per_image']`` -- with ``metrics=None`` and with ``keep_images=False`` too.
-
-    ``kid=True`` or ``kid=dict(num_subsets=100, max_subset_size=1000, seed=0)`` adds the Kernel Inception Distance (stylegan_metrics/
-    kernel_inception_distance.py; needs ``feature_fn`` and ``fid_real=True``): the feature rows the moments are accumulated from are also
-    written, on the batch's stream, into two per-rank float32 buffers ``[n_local, fid_dim]`` at the batch's shard position; ``gather``
-    all-gathers and re-interleaves them to exactly ``n_items`` rows per side and ``kid_value()`` runs kid.kid_from_features on them
-    (``sums_fn`` in the dict replaces the kernel: CPU tests).
-
-    ``inception_score=dict(num_splits=10)`` adds the Inception Score of the fakes (stylegan_metrics/inception_score.py; needs
-    ``feature_fn``): the detector is called once per batch as ``feature_fn(images, with_probs=True) -> (features, probabilities)`` -- one
-    run of the trunk -- and the probabilities go into a per-stream float64 ``[num_splits, C + 2]`` accumulator (inception_score.py of this
-    package; an image's split follows its dataset position, padded duplicates are skipped).  ``C`` is ``feature_fn.num_classes`` or the
-    dict's ``num_classes``; ``no_output_bias`` (default True, as the reference) is passed on when given; ``accumulate_fn(acc, probs,
-    splits)`` replaces the kernel (CPU tests).  ``gather`` adds the streams' accumulators and all-reduces the sum once; ``is_value()`` ->
-    (mean, std).  With both options absent no buffer is allocated and no launch is added.
-
-    ``pr=dict(detector=vgg, nhood_size=3)`` adds the improved precision and recall (stylegan_metrics/precision_recall.py, ``pr50k3_full``;
-    independent of ``feature_fn``, ``kid`` and ``fid_real``): per batch, on the batch's own stream after the composite,
-    ``detector(images)`` and ``detector(real, input_range='pm1')`` (``vgg16.Vgg16Features``, or any callable of that form) are rounded to
-    float16 into two per-rank buffers ``[n_local, dim]`` at the batch's shard position -- one real per fake; ``dim`` is ``detector.dim`` or
-    the dict's ``dim``.  ``gather`` all-gathers and re-interleaves them to exactly ``n_items`` rows per side and ``pr_value()`` ->
-    (precision, recall) runs precision_recall.pr_from_features on them on this device (the manifold sweep is not sharded over the ranks;
-    ``kernels_fn`` in the dict replaces the kernels: CPU tests).  With ``pr=None`` the loop is the loop it was."""
+    The options are documented with their evaluators (evaluators.py): ``feature_fn`` / ``fid_real`` / ``kid`` / ``inception_score`` ->
+    DetectorStats, ``metrics`` / ``lpips`` -> PerImageColumns, ``pr`` -> PrecisionRecall.  ``evaluators`` maps 'detector' / 'columns' / 'pr'
+    to those whose options are present, in batch order; an absent option means no object, buffer or launch and None for its results."""
 
     def __init__(self, G, device, resolution, n_items, rank=0, world=1, noise_mode='random', seed=0, depth=None, feature_fn=None,
                  fid_dim=2048, latent_fn=None, device_masks=True, hole_range=(0, 1), keep_images=True, on_batch=None, step_fn=None,
@@ -410,109 +380,24 @@ class EvalLoop:
         self.G, self.device, self.res = G, torch.device(device), int(resolution)
         self.n_items, self.rank, self.world = int(n_items), int(rank), int(world)
         self.noise_mode, self.seed, self.depth = noise_mode, seed, depth
-        self.feature_fn, self.latent_fn, self.on_batch = feature_fn, latent_fn, on_batch
+        self.feature_fn, self.fid_dim, self.latent_fn, self.on_batch = feature_fn, fid_dim, latent_fn, on_batch
         self.step_fn = step_fn          # (x4, z, out) -> uint8 images: the CPU world-size-2 tests inject a stand-in; the product path is run_generator
         self.ids = shard_ids(self.n_items, self.rank, self.world)
         self.feeder = DeviceFeeder(self.device, self.res, hole_range=hole_range, device_masks=device_masks, own_stream=feeder_stream)
-        self.fid_dim, self._fid_fn = fid_dim, fid_accumulate_fn
-        self._fid_parts = {}            # stream id -> FidStats (partial sums of the batches that ran on that stream)
-        self.fid = None                 # their sum, after gather()
-        if fid_real and feature_fn is None:
-            raise ValueError('EvalLoop: fid_real needs a feature_fn (the detector)')
-        self.fid_real_on = bool(fid_real)
-        self._fid_real_parts = {}       # the same for the real images (fid_real)
-        self.fid_real = None
         self.images = (torch.empty((len(self.ids), 3, self.res, self.res), dtype=torch.uint8, device=self.device) if keep_images else None)
         self.seen = 0
-        self.metrics = None             # image_metrics.MetricsAccumulator of this rank's shard
-        self.image_metrics = None       # after gather(): {'psnr': mean, 'psnr_per_image': [n_items], ...} in dataset order
-        if metrics:
-            from .image_metrics import MetricsAccumulator
-            self.metrics = MetricsAccumulator(len(self.ids), self.device, metrics=tuple(metrics), window_size=ssim_window,
-                                              metrics_fn=metrics_fn)
-        if lpips is not None and not callable(lpips):
-            raise ValueError('EvalLoop: lpips must be a callable lpips(pred_u8, real, out=slice)')
-        self.lpips_fn = lpips
-        self.lpips_values = (torch.full((len(self.ids),), float('nan'), dtype=torch.float64, device=self.device) if lpips is not None else None)
-        self.kid_opts = None            # kid: per-rank feature rows of both sides, the gathered [n_items, fid_dim] pair after gather()
-        self._kid_local = self.kid_features = None
-        if kid:
-            if feature_fn is None or not fid_real:
-                raise ValueError('EvalLoop: kid needs a feature_fn (the detector) and fid_real=True (the real side\'s features)')
-            self.kid_opts = dict(kid) if isinstance(kid, dict) else {}
-            unknown = set(self.kid_opts) - {'num_subsets', 'max_subset_size', 'seed', 'sums_fn'}
-            if unknown:
-                raise ValueError(f'EvalLoop: unknown kid option(s) {sorted(unknown)}')
-            self._kid_local = tuple(torch.zeros((len(self.ids), self.fid_dim), dtype=torch.float32, device=self.device) for _ in range(2))
-        self.is_opts = None             # inception_score: per-stream [num_splits, C + 2] accumulators, their all-reduced sum after gather()
-        self._is_parts, self.is_acc, self._is_splits = {}, None, None
-        if inception_score:
-            if feature_fn is None:
-                raise ValueError('EvalLoop: inception_score needs a feature_fn (the detector with its classifier head)')
-            self.is_opts = dict(inception_score) if isinstance(inception_score, dict) else {}
-            unknown = set(self.is_opts) - {'num_splits', 'num_classes', 'no_output_bias', 'accumulate_fn'}
-            if unknown:
-                raise ValueError(f'EvalLoop: unknown inception_score option(s) {sorted(unknown)}')
-            self.is_opts.setdefault('num_splits', 10)
-            if self.is_opts.get('num_classes') is None:
-                self.is_opts['num_classes'] = getattr(feature_fn, 'num_classes', None)
-            if self.is_opts['num_classes'] is None:
-                raise ValueError('EvalLoop: inception_score needs the class count (feature_fn.num_classes or num_classes=...): the detector '
-                                 'has no classifier head')
-            from .inception_score import split_of
-            # item k of this rank sits at dataset position k * world + rank; positions past n_items are padded duplicates (-1: skipped)
-            self._is_splits = torch.tensor([split_of(k * self.world + self.rank, self.n_items, self.is_opts['num_splits'])
-                                            for k in range(len(self.ids))], dtype=torch.int32).to(self.device)
-
-        self.pr_opts = None             # pr: per-rank float16 feature rows of both sides, the gathered [n_items, dim] pair after gather()
-        self._pr_local = self.pr_features = self._pr_fn = None
+        self.evaluators = {}
+        if feature_fn is not None or fid_real or kid or inception_score:
+            self.evaluators['detector'] = DetectorStats(self, feature_fn, fid_dim, fid_accumulate_fn, fid_real, kid, inception_score)
+        if metrics or lpips is not None:
+            self.evaluators['columns'] = PerImageColumns(self, metrics, ssim_window, metrics_fn, lpips)
         if pr:
-            if not isinstance(pr, dict):
-                raise ValueError('EvalLoop: pr must be a dict(detector=..., nhood_size=3)')
-            self.pr_opts = dict(pr)
-            unknown = set(self.pr_opts) - {'detector', 'nhood_size', 'dim', 'kernels_fn'}
-            if unknown:
-                raise ValueError(f'EvalLoop: unknown pr option(s) {sorted(unknown)}')
-            self._pr_fn = self.pr_opts.pop('detector', None)
-            if not callable(self._pr_fn):
-                raise ValueError('EvalLoop: pr needs detector=..., a callable detector(images, input_range=None) -> [B, dim]')
-            dim = self.pr_opts.pop('dim', None)
-            dim = getattr(self._pr_fn, 'dim', None) if dim is None else dim
-            if dim is None:
-                raise ValueError('EvalLoop: pr needs the feature width (detector.dim or dim=...)')
-            self.pr_opts.setdefault('nhood_size', 3)
-            if not 1 <= int(self.pr_opts['nhood_size']) <= 15:
-                raise ValueError(f"EvalLoop: pr nhood_size must be 1..15 (got {self.pr_opts['nhood_size']})")
-            self._pr_local = tuple(torch.zeros((len(self.ids), int(dim)), dtype=torch.float16, device=self.device) for _ in range(2))
+            self.evaluators['pr'] = PrecisionRecall(self, pr)
 
-    def _fid_part(self, key, real=False):
-        from .fid_stats import FidStats
-        parts = self._fid_real_parts if real else self._fid_parts
-        if key not in parts:
-            parts[key] = FidStats(self.fid_dim, device=self.device, accumulate_fn=self._fid_fn)
-        return parts[key]
-
-    def _is_part(self, key):
-        from .inception_score import new_accumulator
-        if key not in self._is_parts:
-            self._is_parts[key] = new_accumulator(self.is_opts['num_splits'], self.is_opts['num_classes'], self.device)
-        return self._is_parts[key]
-
-    def _fake_features(self, out, k0, cur):
-        """The detector on a batch of fakes: features for the moments (and KID); with ``inception_score`` the same run's probabilities go
-        into this stream's accumulator."""
-        kw = {'no_output_bias': self.is_opts['no_output_bias']} if 'no_output_bias' in self.is_opts else {}
-        feats, probs = self.feature_fn(out, with_probs=True, **kw)
-        acc = self._is_parts.get(cur)
-        if acc is None:
-            acc = self._is_part(None)
-        splits = self._is_splits[k0:k0 + probs.shape[0]]
-        if self.is_opts.get('accumulate_fn') is not None:
-            self.is_opts['accumulate_fn'](acc, probs, splits)
-        else:
-            from .inception_score import is_accumulate
-            is_accumulate(acc, probs, splits)
-        return feats
+    fid, fid_real = _of('detector', 'fake.sum'), _of('detector', 'real.sum')      # FidStats: this rank's after local_fid(), all ranks' after gather()
+    metrics, lpips_values, image_metrics = _of('columns', 'metrics'), _of('columns', 'lpips_values'), _of('columns', 'image_metrics')
+    kid_features, is_acc = _of('detector', 'kid_features'), _of('detector', 'is_parts.sum')
+    pr_opts, pr_features = _of('pr', 'pr_opts'), _of('pr', 'pr_features')
 
     def run(self, loader):
         """``loader`` yields this rank's items in ``shard_ids`` order as (images [B,3,R,R] uint8 or float32 in [-1,1], ids) or
@@ -520,14 +405,10 @@ class EvalLoop:
         if self.noise_mode == 'random':
             torch.manual_seed(self.seed * self.world + self.rank)          # shgan_default.py:165-167
         pipe = StreamPipeline(self.device, depth=self.depth, first_on_caller=False)
-        G, buf = self.G, self.images
-        if self.feature_fn is not None:                                    # accumulators exist before a side stream touches them
-            for key in [None] + [st.cuda_stream for st in pipe.streams]:
-                self._fid_part(key)
-                if self.fid_real_on:
-                    self._fid_part(key, real=True)
-                if self.is_opts is not None:
-                    self._is_part(key)
+        G, buf, evaluators = self.G, self.images, list(self.evaluators.values())
+        if 'detector' in self.evaluators:                                  # its accumulators exist before a side stream touches them
+            self.evaluators['detector'].prepare([None] + [st.cuda_stream for st in pipe.streams])
+        need_real = any(e.needs_real for e in evaluators)
         for x4, real, mask, ids in self.feeder(loader):
             b, k0 = x4.shape[0], self.seen
             if k0 + b > len(self.ids):
@@ -538,28 +419,9 @@ class EvalLoop:
 
             def step(x4_, z_, real_=None, dst=dst, k0=k0):
                 out = gen(x4_, z_, dst)
-                if self.feature_fn is not None:
-                    cur = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == 'cuda' else None
-                    part = self._fid_parts.get(cur) or self._fid_part(None)
-                    feats = self.feature_fn(out) if self.is_opts is None else self._fake_features(out, k0, cur)
-                    part.add_shard(feats, k0, self.rank, self.world, self.n_items)
-                    if self._kid_local is not None:
-                        self._kid_local[0][k0:k0 + feats.shape[0]].copy_(feats)
-                    if self.fid_real_on:
-                        part = self._fid_real_parts.get(cur) or self._fid_part(None, real=True)
-                        feats = self.feature_fn(real_, input_range='pm1')
-                        part.add_shard(feats, k0, self.rank, self.world, self.n_items)
-                        if self._kid_local is not None:
-                            self._kid_local[1][k0:k0 + feats.shape[0]].copy_(feats)
-                if real_ is not None and self.metrics is not None:
-                    self.metrics.add(out, real_, k0)
-                if self.lpips_fn is not None:
-                    self.lpips_fn(out, real_, out=self.lpips_values[k0:k0 + out.shape[0]])
-                if self._pr_local is not None:
-                    self._pr_local[0][k0:k0 + out.shape[0]].copy_(self._pr_fn(out))
-                    self._pr_local[1][k0:k0 + out.shape[0]].copy_(self._pr_fn(real_, input_range='pm1'))
+                for e in evaluators:
+                    e.add(out, real_, k0)
                 return out
-            need_real = self.metrics is not None or self.fid_real_on or self.lpips_fn is not None or self._pr_local is not None
             out = pipe.run(step, x4, z, real) if need_real else pipe.run(step, x4, z)
             if self.timing and self.device.type == 'cuda':
                 tev = torch.cuda.Event(enable_timing=True)
@@ -576,133 +438,32 @@ class EvalLoop:
         return self
 
     def gather(self):
-        """-> (uint8 images [n_items,3,R,R] in dataset order on the device, FidStats summed over the ranks | None).  One
-        ``all_gather_into_tensor`` + ``zipzap_device``; one ``all_reduce`` of the moments.  Every rank must have run its whole shard.
-        With ``metrics`` also one ``all_gather_into_tensor`` of the per-image values -> ``self.image_metrics`` (the reference's
-        ``compute()``: dataset order, ``[0:sample_n]``, mean)."""
-        import torch.distributed as dist
+        """-> (uint8 images [n_items,3,R,R] in dataset order on the device, FidStats summed over the ranks | None), and every evaluator's result.
+        One collective per result that is on: images all-gather, fake and real moments all-reduce, metrics columns all-gather, KID fake / real and
+        precision / recall fake / real all-gathers, Inception Score all-reduce, in this order on every rank (each must have run its whole shard)."""
         if self.seen != len(self.ids):
             raise ValueError(f'EvalLoop.gather: {self.seen} of {len(self.ids)} items of this rank\'s shard were processed')
-        use = dist.is_available() and dist.is_initialized()
-        images = None
-        if self.images is not None:
-            if use:
-                # RCCL gathers device tensors over xGMI; a gloo group (CPU tests, ranks sharing one device) is handed host tensors
-                via_host = dist.get_backend() == 'gloo' and self.images.is_cuda
-                local = self.images.cpu() if via_host else self.images
-                full = torch.empty((self.world,) + tuple(local.shape), dtype=torch.uint8, device=local.device)
-                dist.all_gather_into_tensor(full.view((-1,) + tuple(local.shape[1:])), local)
-                full = full.to(self.device)
-            else:
-                full = self.images[None]
-            images = zipzap_device(full, self.n_items)
-        if self.local_fid() is not None:
-            self.fid.all_reduce()
-        if self.fid_real_on and self.local_fid_real() is not None:
-            self.fid_real.all_reduce()
-        if self.metrics is not None or self.lpips_fn is not None:
-            self.image_metrics = self._gather_metrics(use)
-        if self._kid_local is not None:
-            self.kid_features = tuple(self._gather_rows(t, use) for t in self._kid_local)
-            self._kid_local = None
-        if self._pr_local is not None:
-            self.pr_features = tuple(self._gather_rows(t, use) for t in self._pr_local)
-            self._pr_local = None
-        if self.is_opts is not None and self._is_parts:
-            parts = list(self._is_parts.values())
-            acc = parts.pop(0)
-            for p in parts:
-                acc += p
-            if use:
-                via_host = dist.get_backend() == 'gloo' and acc.is_cuda
-                h = acc.cpu() if via_host else acc
-                dist.all_reduce(h, op=dist.ReduceOp.SUM)
-                acc = h.to(self.device)
-            self.is_acc, self._is_parts = acc, {}
+        collect = Collective(self.device, self.n_items, self.world)
+        images = collect.rows(self.images) if self.images is not None else None
+        det, cols, pr = (self.evaluators.get(name) for name in ('detector', 'columns', 'pr'))
+        # the ranks' contract fixes this order (a reordering can deadlock): hence the detector's three results are finished in three calls
+        for finish in (det and det.finish, cols and cols.finish, det and det.finish_kid, pr and pr.finish, det and det.finish_is):
+            if finish:
+                finish(collect)
         return images, self.fid
-
-    def _gather_rows(self, local, use):
-        """This rank's [n_local, ...] rows -> [n_items, ...] in dataset order on the device (one all-gather + zipzap_device)."""
-        import torch.distributed as dist
-        if not use:
-            return zipzap_device(local[None], self.n_items)
-        via_host = dist.get_backend() == 'gloo' and local.is_cuda
-        src = local.cpu() if via_host else local
-        full = torch.empty((self.world,) + tuple(src.shape), dtype=src.dtype, device=src.device)
-        dist.all_gather_into_tensor(full.view((-1,) + tuple(src.shape[1:])), src)
-        return zipzap_device(full.to(self.device), self.n_items)
-
-    def kid_value(self):
-        """The KID of the gathered features (after ``gather``; ``kid=...``): exactly ``n_items`` rows per side in dataset order."""
-        from .kid import kid_from_features
-        if self.kid_features is None:
-            raise ValueError('EvalLoop.kid_value: needs kid=True (or its options) and a finished gather()')
-        fake, real = self.kid_features
-        return kid_from_features(fake.contiguous(), real.contiguous(), **self.kid_opts)
-
-    def pr_value(self):
-        """(precision, recall) of the gathered features (after ``gather``; ``pr=dict(...)``): exactly ``n_items`` rows per side in dataset
-        order, fakes against reals."""
-        from .precision_recall import pr_from_features
-        if self.pr_features is None:
-            raise ValueError('EvalLoop.pr_value: needs pr=dict(detector=...) and a finished gather()')
-        fake, real = self.pr_features
-        return pr_from_features(real.contiguous(), fake.contiguous(), **self.pr_opts)
-
-    def is_value(self):
-        """(mean, std) of the Inception Score over the splits (after ``gather``; ``inception_score=...``)."""
-        from .inception_score import is_from_accumulator
-        if self.is_acc is None:
-            raise ValueError('EvalLoop.is_value: needs inception_score=dict(...) and a finished gather()')
-        return is_from_accumulator(self.is_acc)
-
-    def _gather_metrics(self, use):
-        import torch.distributed as dist
-        from .image_metrics import finish_metrics
-        values = dict(self.metrics.values) if self.metrics is not None else {}
-        if self.lpips_fn is not None:
-            values['lpips'] = self.lpips_values
-        names = list(values)
-        local = torch.stack([values[m] for m in names], dim=1)                      # [n_local, M] float64
-        if use:
-            via_host = dist.get_backend() == 'gloo' and local.is_cuda
-            src = local.cpu() if via_host else local
-            full = torch.empty((self.world,) + tuple(src.shape), dtype=src.dtype, device=src.device)
-            dist.all_gather_into_tensor(full.view((-1,) + tuple(src.shape[1:])), src)
-            full = full.to(self.device)
-        else:
-            full = local[None]
-        return finish_metrics({m: full[:, :, j] for j, m in enumerate(names)}, self.n_items)
 
     def local_fid(self):
         """This rank's moments (the per-stream partial accumulators added up; no collective)."""
-        if self._fid_parts:
-            parts = list(self._fid_parts.values())
-            base = self.fid if self.fid is not None else parts.pop(0)
-            for p in parts:
-                base.S += p.S
-            self.fid, self._fid_parts = base, {}
-        return self.fid
+        return self.evaluators['detector'].fake.total() if 'detector' in self.evaluators else None
 
     def local_fid_real(self):
         """The same for the real side (``fid_real``)."""
-        if self._fid_real_parts:
-            parts = list(self._fid_real_parts.values())
-            base = self.fid_real if self.fid_real is not None else parts.pop(0)
-            for p in parts:
-                base.S += p.S
-            self.fid_real, self._fid_real_parts = base, {}
-        return self.fid_real
+        return self.evaluators['detector'].real.total() if 'detector' in self.evaluators else None
 
-    def fid_value(self):
-        """The FID of the gathered moments (after ``gather``; ``fid_real=True``): ``fid_from_stats`` on the fake and real sides'
-        ``mean_cov`` -- the reference's ``compute_fid`` (eva_fid.py:243-263) without the cache file of real statistics."""
-        from .fid_stats import fid_from_stats
-        if not self.fid_real_on or self.fid is None or self.fid_real is None:
-            raise ValueError('EvalLoop.fid_value: needs fid_real=True, a feature_fn and a finished gather()')
-        _, mu_f, sg_f = self.fid.mean_cov()
-        _, mu_r, sg_r = self.fid_real.mean_cov()
-        return fid_from_stats(mu_f, sg_f, mu_r, sg_r)
+    fid_value = _value_of('detector', 'fid_value', 'fid_real=True, a feature_fn')
+    kid_value = _value_of('detector', 'kid_value', 'kid=True (or its options)')
+    is_value = _value_of('detector', 'is_value', 'inception_score=dict(...)')          # -> (mean, std)
+    pr_value = _value_of('pr', 'pr_value', 'pr=dict(detector=...)')                    # -> (precision, recall)
 
 
 class PinnedU8Loader:

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import torch
+
 from conftest import ROOT
 
 
@@ -127,3 +129,162 @@ def test_broadcast_state_without_a_process_group_is_a_no_op():
     net = torch.nn.Linear(3, 2)
     w = net.weight.detach().clone()
     assert hz.broadcast_state(net) == 0 and torch.equal(net.weight, w)
+
+
+# ---- every option on at once: the order of the calls inside a batch and of the collectives at the end
+
+ALL_ON = dict(R=16, N=11, B=4, D=64, C=9, SPLITS=3, PR_DIM=6, KID=dict(num_subsets=4, max_subset_size=6, seed=3))
+# what a batch does on its stream, in order (the KID copies and the writes into the buffers are plain tensor copies: no stand-in sees them)
+BATCH_CALLS = ['step', ('detector', None, True), 'is_accumulate', 'fid_accumulate', ('detector', 'pm1', False), 'fid_accumulate', 'metrics',
+               'lpips', ('pr_detector', None), ('pr_detector', 'pm1')]
+
+
+def all_on_loop(rank, world, log):
+    """EvalLoop on the CPU with every option on and a stand-in for every kernel; each stand-in appends its name to ``log`` (detectors:
+    with the ``input_range`` they were given), the generator step first."""
+    import kid_is_f64
+    import pr_f64
+    from shgan_amd import eval_harness as hz
+    R, N, B, D, C = (ALL_ON[k] for k in ('R', 'N', 'B', 'D', 'C'))
+
+    def step(x, z, out):
+        log.append('step')
+        out.copy_(((x[:, 1:4] * 0.5 + z[:, :3, None, None] * 0.2).tanh() * 127.5 + 127.5).clamp(0, 255).to(torch.uint8))
+        return out
+
+    def values(img, input_range):
+        return img.float() * 127.5 + 127.5 if input_range == 'pm1' else img.float()
+    W = torch.randn(C, D, generator=torch.Generator().manual_seed(1)) * 0.05
+
+    class Det:
+        num_classes = C
+
+        def __call__(self, img, input_range=None, with_probs=False):
+            log.append(('detector', input_range, with_probs))
+            f = hz.standin_features(values(img, input_range), D) / 64
+            # (one matrix-vector product per image: the same bits whatever batch the image arrives in)
+            return (f, torch.softmax(torch.stack([W @ fi for fi in f]), 1)) if with_probs else f
+
+    class PrDet:
+        dim = ALL_ON['PR_DIM']
+
+        def __call__(self, img, input_range=None):
+            log.append(('pr_detector', input_range))
+            return hz.standin_features(values(img, input_range), self.dim) / 64
+
+    def fid_acc(S, feats, w):
+        log.append('fid_accumulate')
+        f = torch.cat([feats.double(), torch.ones(feats.shape[0], 1, dtype=torch.float64)], 1)
+        S[:D + 1, :D + 1] += (f * w.double()[:, None]).t() @ f
+
+    def is_acc(a, probs, splits):
+        log.append('is_accumulate')
+        a += torch.from_numpy(kid_is_f64.is_accumulator_f64(probs.numpy(), splits.numpy(), a.shape[0]))
+
+    def diff(pred, real):
+        return pred.double() / 255 - (real.double() + 1) / 2
+
+    def metrics_fn(pred, gt, ws, p_out, s_out):
+        log.append('metrics')
+        p_out.copy_(diff(pred, gt).pow(2).mean(dim=(1, 2, 3)))
+        s_out.copy_(diff(pred, gt).abs().amax(dim=(1, 2, 3)))
+
+    def lpips(pred, real, out=None):
+        log.append('lpips')
+        out.copy_(diff(pred, real).abs().mean(dim=(1, 2, 3)))
+
+    def latents(ids, b):
+        g, out = torch.Generator(), torch.empty(b, 8)
+        for k, i in enumerate(ids):
+            g.manual_seed(100 + int(i))
+            out[k].normal_(generator=g)
+        return out
+
+    def loader(ids):
+        for b0 in range(0, len(ids), B):
+            g, imgs = torch.Generator(), []
+            for i in ids[b0:b0 + B]:
+                g.manual_seed(7000 + int(i))
+                imgs.append(torch.rand(3, R, R, generator=g) * 2 - 1)
+            yield torch.stack(imgs), torch.ones(len(imgs), R, R) * (torch.arange(R) % 3 > 0).float(), ids[b0:b0 + B]
+    pr_fns = (lambda f, k: torch.from_numpy(pr_f64.radii16(f.numpy(), k)),
+              lambda p, m, r: torch.from_numpy(pr_f64.inside16(p.numpy(), m.numpy(), r.numpy())))
+    loop = hz.EvalLoop(None, 'cpu', R, N, rank=rank, world=world, noise_mode='const', feature_fn=Det(), fid_dim=D, latent_fn=latents,
+                       device_masks=False, step_fn=step, fid_accumulate_fn=fid_acc, metrics=('psnr', 'ssim'), ssim_window=7,
+                       metrics_fn=metrics_fn, fid_real=True, lpips=lpips, kid=dict(ALL_ON['KID'], sums_fn=kid_is_f64.kid_sums_f64),
+                       inception_score=dict(num_splits=ALL_ON['SPLITS'], accumulate_fn=is_acc),
+                       pr=dict(detector=PrDet(), nhood_size=2, kernels_fn=pr_fns))
+    loop.run(loader(loop.ids))
+    return loop
+
+
+def test_every_option_on_one_rank_calls_in_order_per_batch():
+    """11 items in batches of 4 (a ragged last batch), every option on: each batch makes exactly the calls of BATCH_CALLS, in that order."""
+    import shgan_amd  # noqa: F401
+    log = []
+    loop = all_on_loop(0, 1, log)
+    assert log == BATCH_CALLS * 3
+    images, fid = loop.gather()
+    assert log == BATCH_CALLS * 3                                       # gather runs no stand-in
+    N, D = ALL_ON['N'], ALL_ON['D']
+    assert images.shape == (N, 3, 16, 16) and fid is loop.fid and fid.mean_cov()[0] == N == loop.fid_real.mean_cov()[0]
+    assert [t.shape for t in loop.kid_features] == [(N, D)] * 2 and [t.shape for t in loop.pr_features] == [(N, ALL_ON['PR_DIM'])] * 2
+    assert float(loop.is_acc[:, -1].sum()) == N
+    assert sorted(loop.image_metrics) == ['lpips', 'lpips_per_image', 'psnr', 'psnr_per_image', 'ssim', 'ssim_per_image']
+    assert torch.equal(loop.image_metrics['lpips_per_image'], loop.lpips_values)
+    for fn in (loop.fid_value, loop.kid_value, loop.is_value, loop.pr_value):
+        fn()
+
+
+def test_gloo_world2_every_option_on_collectives_in_order():
+    """World 2: the per-batch calls are those of one rank; ``gather`` issues one collective per result, in the order every rank relies
+    on; what it returns equals the 1-rank run (bit for bit where rows are only moved; sums of float64 terms taken in another order --
+    moments, Inception Score accumulators, means -- within 1e-12 relative)."""
+    script = r"""
+import os, sys, numpy as np, torch, torch.distributed as dist
+sys.path.insert(0, os.environ["SHG_ROOT"]); sys.path.insert(0, os.path.join(os.environ["SHG_ROOT"], "tests"))
+import shgan_amd
+from test_eval_loop_cpu import ALL_ON, BATCH_CALLS, all_on_loop
+dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%s" % os.environ["SHG_PORT"], rank=int(os.environ["RANK"]), world_size=2)
+r = dist.get_rank()
+N, D, C, S, P = (ALL_ON[k] for k in ("N", "D", "C", "SPLITS", "PR_DIM"))
+seen = []
+def record(name):
+    fn = getattr(dist, name)
+    def wrapped(*args, **kw):
+        t = args[1] if name == "all_gather_into_tensor" else args[0]           # the rank's own contribution
+        seen.append((name, t.dtype, tuple(t.shape)))
+        return fn(*args, **kw)
+    setattr(dist, name, wrapped)
+record("all_gather_into_tensor"); record("all_reduce")
+log = []
+loop = all_on_loop(r, 2, log)
+assert log == BATCH_CALLS * 2 and not seen                                     # 6 items per rank: batches of 4 and 2; no collective per batch
+images, fid = loop.gather()
+dp = (D + 1 + 31) // 32 * 32
+gather, reduce = "all_gather_into_tensor", "all_reduce"
+assert seen == [(gather, torch.uint8, (6, 3, 16, 16)), (reduce, torch.float64, (dp, dp)), (reduce, torch.float64, (dp, dp)),
+                (gather, torch.float64, (6, 3)), (gather, torch.float32, (6, D)), (gather, torch.float32, (6, D)),
+                (gather, torch.float16, (6, P)), (gather, torch.float16, (6, P)), (reduce, torch.float64, (S, C + 2))], seen
+values = (loop.fid_value(), loop.kid_value(), loop.is_value(), loop.pr_value())
+dist.destroy_process_group()
+one = all_on_loop(0, 1, [])
+images1, fid1 = one.gather()
+assert torch.equal(images, images1)
+for a, b in zip(loop.kid_features + loop.pr_features, one.kid_features + one.pr_features):
+    assert a.dtype == b.dtype and torch.equal(a, b)
+assert sorted(loop.image_metrics) == sorted(one.image_metrics)
+for k, v in one.image_metrics.items():
+    if torch.is_tensor(v):
+        assert torch.equal(loop.image_metrics[k], v), k
+    else:
+        assert abs(loop.image_metrics[k] - v) <= 1e-12 * abs(v), k
+close = lambda a, b: bool(np.allclose(np.asarray(a), np.asarray(b), rtol=1e-12, atol=0))
+assert close(fid.S, fid1.S) and close(loop.fid_real.S, one.fid_real.S) and close(loop.is_acc, one.is_acc)
+assert float(fid.S[D, D]) == N == float(loop.is_acc[:, -1].sum())              # the padded duplicate on rank 1 counts nowhere
+want = (one.fid_value(), one.kid_value(), one.is_value(), one.pr_value())
+assert values[1] == want[1] and values[3] == want[3]
+assert abs(values[0] - want[0]) <= 1e-9 * max(1.0, abs(want[0])) and close(values[2], want[2])
+print("rank", r, "ok")
+"""
+    _run_two(script, 43500)

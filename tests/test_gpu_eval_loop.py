@@ -147,3 +147,51 @@ def test_eval_loop_full_width_512_batch16_random_noise():
         assert torch.equal(torch.where(m, got, torch.zeros_like(got)), torch.where(m, src, torch.zeros_like(src))), k0
         k0 += len(ids)
     del kept
+
+
+def test_eval_loop_every_option_on_equals_one_option_group_at_a_time(small_g):
+    """11 items in batches of 4 on three streams (a ragged last batch, every side stream in use), every evaluator sharing each batch:
+    PSNR / SSIM / LPIPS, both FID sides + KID + Inception Score from one Inception-v3 with a head, precision / recall from a narrow VGG16
+    -- all three networks the product's, built from the seeded random weights of their own test files.  Every result is the same bits as in
+    a loop that has only its own option group on."""
+    import inception_f64
+    import lpips_f64
+    import pr_f64
+    from shgan_amd import eval_harness as hz, inception, lpips, vgg16
+    n_items, b, R = 11, 4, 256
+    sd = inception_f64.random_state_dict(7)
+    g = torch.Generator().manual_seed(70)
+    sd['fc.weight'] = torch.randn(1008, 2048, generator=g) * 0.05
+    sd['fc.bias'] = torch.randn(1008, generator=g) * 0.5
+    det = inception.InceptionFeatures.from_state_dict(sd, device=DEV, split_k=False)
+    net = lpips.Lpips.from_state_dict(lpips_f64.random_state_dict(11), device=DEV)
+    vgg = vgg16.Vgg16Features.from_state_dict(pr_f64.random_state_dict(3), device=DEV)
+    groups = {'detector': dict(feature_fn=det, fid_real=True, kid=dict(num_subsets=4, max_subset_size=8, seed=1),
+                               inception_score=dict(num_splits=3)),
+              'columns': dict(metrics=('psnr', 'ssim'), lpips=net),
+              'pr': dict(pr=dict(detector=vgg))}
+
+    def run(**kw):
+        loop = hz.EvalLoop(small_g, DEV, R, n_items, noise_mode='const', depth=3, latent_fn=_latents, **kw)
+        np.random.seed(21)
+        loop.run(hz.PinnedU8Loader(loop.ids, b, R, seed=13))
+        images, fid = loop.gather()
+        torch.cuda.synchronize()
+        assert fid is loop.fid and tuple(images.shape) == (n_items, 3, R, R)
+        return loop
+    every = run(**{k: v for kw in groups.values() for k, v in kw.items()})
+    alone = {name: run(**kw) for name, kw in groups.items()}
+    for name, loop in alone.items():
+        assert torch.equal(loop.images, every.images), name
+    d, c, p = alone['detector'], alone['columns'], alone['pr']
+    assert c.fid is None and p.fid is None and d.image_metrics is None and p.image_metrics is None and c.pr_features is None
+    assert torch.equal(every.fid.S, d.fid.S) and torch.equal(every.fid_real.S, d.fid_real.S) and float(every.fid.S[2048, 2048]) == n_items
+    assert torch.equal(every.is_acc, d.is_acc) and float(every.is_acc[:, -1].sum()) == n_items
+    for side in range(2):
+        assert every.kid_features[side].shape == (n_items, 2048) and torch.equal(every.kid_features[side], d.kid_features[side])
+        assert every.pr_features[side].shape == (n_items, vgg.dim) and torch.equal(every.pr_features[side], p.pr_features[side])
+        assert float(every.pr_features[side].float().abs().sum()) > 0
+    assert sorted(every.image_metrics) == sorted(c.image_metrics) == ['lpips', 'lpips_per_image', 'psnr', 'psnr_per_image', 'ssim', 'ssim_per_image']
+    for key in ('psnr_per_image', 'ssim_per_image', 'lpips_per_image'):
+        got, want = every.image_metrics[key].cpu().numpy(), c.image_metrics[key].cpu().numpy()
+        assert got.shape == (n_items,) and not np.isnan(want).any() and np.array_equal(got, want), key

@@ -298,7 +298,7 @@ def test_eval_loop_precision_recall(small_g, det):
     none, (images_n, fid_n) = run(pr=None)
     plain, (images_p, fid_p) = run()
     torch.cuda.synchronize()
-    assert none.pr_features is None and none._pr_local is None
+    assert none.pr_features is None and 'pr' not in none.evaluators and 'pr' not in plain.evaluators and 'pr' in loop.evaluators
     for other, im, fd in ((none, images_n, fid_n), (loop, images, fid)):
         assert torch.equal(im, images_p) and torch.equal(fd.S, fid_p.S) and torch.equal(other.fid_real.S, plain.fid_real.S)
         assert set(other.image_metrics) == set(plain.image_metrics)

@@ -155,7 +155,9 @@ def test_eval_loop_options_are_checked():
     with pytest.raises(ValueError, match='class count'):
         hz.EvalLoop(None, 'cpu', 8, 7, feature_fn=feat, fid_dim=6, inception_score=dict(num_splits=2))
     plain = hz.EvalLoop(None, 'cpu', 8, 7, feature_fn=feat, fid_dim=6)
-    assert plain._kid_local is None and plain._is_splits is None and plain._is_parts == {}
+    det = plain.evaluators['detector']                # the moments alone: no KID rows, no Inception Score accumulators or split table
+    assert list(plain.evaluators) == ['detector'] and det.kid_local is None and det.is_splits is None and det.is_parts.parts == {}
+    assert plain.kid_features is None and plain.is_acc is None
     for fn in (plain.kid_value, plain.is_value):
         with pytest.raises(ValueError):
             fn()

@@ -195,12 +195,14 @@ def test_eval_loop_pr_option_validation():
     with pytest.raises(ValueError, match='nhood_size'):
         hz.EvalLoop(None, 'cpu', 8, 7, pr=dict(detector=det, dim=6, nhood_size=16))
     plain = hz.EvalLoop(None, 'cpu', 8, 7)
-    assert plain._pr_local is None and plain.pr_opts is None and plain.pr_features is None
+    assert plain.evaluators == {} and plain.pr_opts is None and plain.pr_features is None          # no evaluator object, no buffer
     with pytest.raises(ValueError, match='pr=dict'):
         plain.pr_value()
     loop = hz.EvalLoop(None, 'cpu', 8, 7, pr=dict(detector=det, dim=6))
-    assert loop.pr_opts == dict(nhood_size=3) and loop._pr_local[0].shape == (7, 6) and loop._pr_local[0].dtype == torch.float16
-    assert loop.feature_fn is None and loop._kid_local is None
+    assert list(loop.evaluators) == ['pr'] and loop.pr_opts == dict(nhood_size=3)
+    rows = loop.evaluators['pr'].local
+    assert len(rows) == 2 and all(t.shape == (7, 6) and t.dtype == torch.float16 for t in rows)
+    assert loop.feature_fn is None and 'detector' not in loop.evaluators and loop.kid_features is None
 
 
 def test_eval_loop_pr_on_the_cpu_with_stand_ins():
