@@ -62,7 +62,8 @@ def test_upfirdn2d_halves_vs_reference(g):
 
 def test_same_size_fir_marching_kernel_vs_float64():
     """fir4_march_f16_kernel (same-size 4x4 filter): outer-product filters take the separable marching path, any other 4x4 filter the 16-tap
-    loop of the same launch; paddings incl. crops, flipped / asymmetric filters, gains, odd extents, 8...264 channels, every strip length."""
+    loop of the same launch; paddings incl. crops, flipped / asymmetric filters, gains, odd extents, 8...264 channels.  Every case here has fewer
+    than 524 288 lanes at 8 rows, so only the 4-row strips run; the 8-, 16- and 32-row strips are cases of tests/test_gpu_routes_fp16.py."""
     from shgan_amd import kernels_f16 as kf
     import torch.nn.functional as F
     gen = torch.Generator().manual_seed(7)

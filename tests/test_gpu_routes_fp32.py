@@ -548,7 +548,8 @@ NOT_ROUTED = {
     'planes_to_image_kernel, modtail_backward_f32_kernel, scale_cast_to_half_kernel, scale_cast_to_float_kernel, sum_partials_kernel, '
     'scale_channels_kernel, composite_u8_kernel, assemble_input_kernel, assemble_input_u8_kernel': 'single-kernel entry points without a '
     'route choice; covered by test_gpu_ops.py, test_gpu_r6_ops.py, test_gpu_parity_r2.py and test_gpu_eval_loop.py',
-    'float16 kernels of pointwise.hip and conv_f16*.hip': 'the fp16 routes are covered by test_gpu_fp16_routes.py and test_gpu_fp16.py',
+    'float16 kernels of pointwise.hip and conv_f16*.hip': 'the fp16 entry points have a route table of their own, test_gpu_routes_fp16.py (every '
+    'launch site of conv_f16*.hip by kernel name, both sides of each predicate, against float64)',
 }
 
 
