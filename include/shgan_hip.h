@@ -472,6 +472,20 @@ int shg_resize_bicubic_u8(const void* src, long src_bytes, const int* table, lon
 int shg_resize_fit_pad_u8(const void* src, long src_bytes, const int* table, long table_elems, void* dst, int B, int R, int chunks, int bands,
                           int lds_bytes, void* stream);
 
+/* ---- Training input of Places2, OpenImages and DTD: the "random scale, random crop" formatter (AdvInpaintingFormatter,
+ * ds_places2.py:183-207, ds_openimages.py:117-141; InpaintingFormatter, ds_texture.py:121-149).  dst float32 [B,3,s,s]: per image the
+ * window [ch:ch+s, cw:cw+s] of torch's bicubic resample (upsample_bicubic2d, align_corners = false, A = -0.75, 4 x 4 clamped taps,
+ * float32 coordinates) of the image to nh x nw, flipped vertically / horizontally when the flags say so; only the window is computed.
+ * A sample's value is lut[byte] (device float32 [256]).  desc / desc_dev: the same B rows of 9 ints {h, w, byte offset in src, nh, nw, ch,
+ * cw, flip_v, flip_h} in host and in device memory: the host copy is checked before the launch (h, w >= 1; the image inside src;
+ * nh, nw >= s; the window inside nh x nw; flags 0 / 1), the device copy is what the kernel reads.  ragged: src holds HWC RGB images of
+ * their own sizes (no alignment assumed); planar: three h x w planes per image at its offset (a uint8 [B,3,H,W] tensor).  One launch;
+ * no atomics: an image's window has the same bits alone and inside any batch. */
+int shg_randcrop_bicubic_ragged_f32(const void* src, long src_bytes, const int* desc, const int* desc_dev, const float* lut, float* dst, int B,
+                                    int s, void* stream);
+int shg_randcrop_bicubic_planar_f32(const void* src, long src_bytes, const int* desc, const int* desc_dev, const float* lut, float* dst, int B,
+                                    int s, void* stream);
+
 /* ---- next row N3 (training-side critic, forward only): minibatch_std_layer (stylegan.py:686-704).
  * x [N,C,H,W] -> y [N,C+F,H,W]; N % G == 0, C % F == 0; stat [N/G * F] is caller-owned scratch. */
 int shg_minibatch_std_f32(const float* x, float* y, float* stat, int N, int C, int H, int W, int G, int F, void* stream);

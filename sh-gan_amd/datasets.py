@@ -11,7 +11,12 @@ Mirrors ``lib/data_factory/ds_ffhq.py``:
   * ``FFHQZip``               -- the ``ds_base.__getitem__`` composition (element -> loader -> formatter);
   * ``DeviceFeeder``          -- what ``shgan_default.py:267-274`` does per batch (``x = cat([mask - 0.5, real * mask])``), on the device:
     pinned staging, H2D on a copy stream overlapped with the previous batch's kernels, masks either from the host formatter or
-    drawn on the device (``masks.random_masks``, bit-identical to the host implementation), ``assemble_input`` kernel."""
+    drawn on the device (``masks.random_masks``, bit-identical to the host implementation), ``assemble_input`` kernel.
+
+Training input of Places2, OpenImages and DTD: ``draw_scale_crop`` makes the draws of the reference's "random scale, random crop"
+formatters (``AdvInpaintingFormatter``, ds_places2.py:183-207 / ds_openimages.py:117-141; ``InpaintingFormatter``, ds_texture.py:121-149)
+on the host, items carry them as 'crop', and ``DeviceFeeder`` computes the window on the device (``resize.randcrop_bicubic``); ``Texture``
+is the DTD dataset of ds_texture.py."""
 import io
 import os
 from zipfile import ZipFile
@@ -165,14 +170,21 @@ class DeviceFeeder:
     def _resize_on_device(self, batch):
         """RaggedU8Batch -> uint8 [B,3,R,R] on the device: the packed bytes are uploaded like any other input and resized
         (resize.resize_bicubic_u8, Pillow's bicubic bit for bit, then the flips; a ``fit`` batch: resize.resize_fit_pad_u8, resized
-        to its boxes and padded) on the staging stream, behind their upload."""
-        from .resize import resize_bicubic_u8, resize_fit_pad_u8
+        to its boxes and padded) on the staging stream, behind their upload.  A batch with ``crop`` (the training formatters' random
+        scale and crop) -> float32 [B,3,R,R] in [-1,1]: resize.randcrop_bicubic on the same stream, fed the packed bytes themselves
+        (DTD) or the loader's resize (Places2, OpenImages: ``preresize``)."""
+        from .resize import randcrop_bicubic, resize_bicubic_u8, resize_fit_pad_u8
         if self.device.type != 'cuda':
             raise ValueError('DeviceFeeder: ragged uint8 batches are resized on a HIP device (there is no host path)')
         data = self._to_device(batch.data)
         st = self.copy_stream if self.copy_stream is not None else torch.cuda.current_stream(self.device)
+        if batch.crop is not None and not batch.preresize:           # DTD: the window straight from the images at their own sizes
+            return randcrop_bicubic(data, batch.shapes, self.resolution, batch.crop, stream=st)
         fn = resize_fit_pad_u8 if batch.fit else resize_bicubic_u8
-        return fn(data, batch.shapes, self.resolution, flip=batch.flip, stream=st)
+        u8 = fn(data, batch.shapes, self.resolution, flip=batch.flip, stream=st)
+        if batch.crop is None:
+            return u8
+        return randcrop_bicubic(u8, None, self.resolution, batch.crop, stream=st)     # Places2 / OpenImages 'adv': the loader's resize first
 
     def _stage(self, batch):
         boxes = None
@@ -180,7 +192,7 @@ class DeviceFeeder:
             mask, ids = batch.masks, batch.ids
             xd = self._resize_on_device(batch)
             x = xd
-            if batch.fit:
+            if batch.fit and batch.crop is None:      # AdvInpaintingFormatter has no box fill (ds_openimages.py:129-141)
                 boxes = np.asarray(batch.content_size, dtype=np.int32).reshape(-1, 2)
         else:
             x, mask, ids = (batch[0], batch[1], batch[2]) if len(batch) == 3 else (batch[0], None, batch[1])
@@ -291,14 +303,21 @@ class Places2(torch.utils.data.Dataset):
     reference), 'flip': the formatter's flip decision (one ``npr.rand()`` draw when ``random_flip``), 'unique_id'} and, with
     ``host_masks``, 'mask' = ``RandomMask(resolution, hole_range)[0]`` drawn after the flip, as the formatter does.  ``collate_ragged``
     batches items into a ``RaggedU8Batch``; ``DeviceFeeder`` resizes it (Pillow's bicubic bit for bit) and flips on the device.
-    Without ``host_masks`` the masks come from the device (``DeviceFeeder(device_masks=True)``, the same numpy draws)."""
+    Without ``host_masks`` the masks come from the device (``DeviceFeeder(device_masks=True)``, the same numpy draws).
 
-    def __init__(self, root_dir, mode, resolution=512, random_flip=False, hole_range=(0, 1), host_masks=False, try_sample=None, repeat=1):
+    ``formatter='adv'`` is the training input, ``AdvInpaintingFormatter`` (ds_places2.py:183-207) behind the same loader: no flip; the
+    item carries 'crop' = ``draw_scale_crop(R, R, R, flips=False)`` (the loader's output is R x R) and 'preresize', and the mask is
+    drawn after those draws.  ``DeviceFeeder`` resizes to R x R as above and cuts the window of the float bicubic rescale on the device."""
+
+    def __init__(self, root_dir, mode, resolution=512, random_flip=False, hole_range=(0, 1), host_masks=False, try_sample=None, repeat=1,
+                 formatter='freeform'):
+        if formatter not in ('freeform', 'adv'):
+            raise ValueError(f"Places2: formatter must be 'freeform' or 'adv' (got {formatter!r})")
         self.load_info = places2_list(root_dir, mode)
         if try_sample is not None:
             self.load_info = self.load_info[:try_sample]
         self.resolution, self.random_flip, self.hole_range = int(resolution), bool(random_flip), list(hole_range)
-        self.host_masks, self.repeat = bool(host_masks), repeat
+        self.host_masks, self.repeat, self.formatter = bool(host_masks), repeat, formatter
 
     def __len__(self):
         return len(self.load_info) * self.repeat
@@ -308,7 +327,11 @@ class Places2(torch.utils.data.Dataset):
         e = self.load_info[idx % len(self.load_info)]
         with Image.open(e['image_path']) as im:
             u8 = np.asarray(im.convert('RGB'))
-        item = {'image': u8, 'flip': bool(self.random_flip and npr.rand() < 0.5), 'unique_id': e['unique_id']}
+        if self.formatter == 'adv':
+            item = {'image': u8, 'flip': False, 'unique_id': e['unique_id'], 'preresize': True,
+                    'crop': draw_scale_crop(self.resolution, self.resolution, self.resolution, flips=False)}
+        else:
+            item = {'image': u8, 'flip': bool(self.random_flip and npr.rand() < 0.5), 'unique_id': e['unique_id']}
         if self.host_masks:
             item['mask'] = _data.RandomMask(self.resolution, self.hole_range)[0]
         return item
@@ -332,6 +355,16 @@ def places2_challenge256_inpainting(root_dir, **kw):
 def places2_challenge512_inpainting(root_dir, **kw):
     """configs/dataset/places2.yaml ``places2_challenge512_inpainting``."""
     return Places2(root_dir, 'challenge', resolution=512, random_flip=True, hole_range=(0.0, 1.0), **kw)
+
+
+def places2_train256_adv_inpainting(root_dir, **kw):
+    """Places2 training input at 256: ``FixResolutionLoader(256)`` + ``AdvInpaintingFormatter(256)`` (ds_places2.py:90-103,183-207)."""
+    return Places2(root_dir, 'train', resolution=256, formatter='adv', hole_range=(0.0, 1.0), **kw)
+
+
+def places2_train512_adv_inpainting(root_dir, **kw):
+    """Places2 training input at 512: ``FixResolutionLoader(512)`` + ``AdvInpaintingFormatter(512)``."""
+    return Places2(root_dir, 'train', resolution=512, formatter='adv', hole_range=(0.0, 1.0), **kw)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -393,10 +426,17 @@ class OpenImages(torch.utils.data.Dataset):
 
     The reference's quirk is kept: the fill uses the UNFLIPPED box even when the flip has moved the content to the right edge, and
     RandomMask's hole-ratio test sees the whole mask, before the fill.  ``collate_ragged`` makes a ``RaggedU8Batch`` with ``fit`` set;
-    ``DeviceFeeder`` resizes, pads and flips it on the device and, with device masks, applies the same fill there."""
+    ``DeviceFeeder`` resizes, pads and flips it on the device and, with device masks, applies the same fill there.
+
+    ``formatter='adv'`` is the training input, ``AdvInpaintingFormatter`` (ds_openimages.py:117-141) behind the same loader: no flip,
+    'crop' = ``draw_scale_crop(R, R, R, flips=False)`` of the padded R x R canvas, and -- as in the reference -- NO box fill: the mask is
+    ``RandomMask`` as drawn, on the host and on the device alike."""
 
     def __init__(self, root_dir, mode, resolution=1024, random_flip=False, hole_range=(0, 1), host_masks=False, try_sample=None,
-                 repeat=1):
+                 repeat=1, formatter='freeform'):
+        if formatter not in ('freeform', 'adv'):
+            raise ValueError(f"OpenImages: formatter must be 'freeform' or 'adv' (got {formatter!r})")
+        self.formatter = formatter
         self.load_info = openimages_list(root_dir, mode)
         if try_sample is not None:
             self.load_info = self.load_info[:try_sample]
@@ -414,6 +454,12 @@ class OpenImages(torch.utils.data.Dataset):
             box = fit_size(u8.shape[0], u8.shape[1], self.resolution)
         except ValueError as err:
             raise ValueError(f'{e["image_path"]}: {err}') from None
+        if self.formatter == 'adv':
+            item = {'image': u8, 'flip': False, 'unique_id': e['unique_id'], 'content_size': box, 'preresize': True,
+                    'crop': draw_scale_crop(self.resolution, self.resolution, self.resolution, flips=False)}
+            if self.host_masks:
+                item['mask'] = _data.RandomMask(self.resolution, self.hole_range)[0]
+            return item
         item = {'image': u8, 'flip': bool(self.random_flip and npr.rand() < 0.5), 'unique_id': e['unique_id'], 'content_size': box}
         if self.host_masks:
             item['mask'] = fill_outside_box(_data.RandomMask(self.resolution, self.hole_range)[0], box)
@@ -430,16 +476,119 @@ def openimages_train_1024(root_dir, **kw):
     return OpenImages(root_dir, 'train', resolution=1024, random_flip=True, hole_range=(0.0, 1.0), **kw)
 
 
+def openimages_train_1024_adv(root_dir, **kw):
+    """OpenImages training input: ``FixResolutionLoader(1024)`` + ``AdvInpaintingFormatter(1024)`` (ds_openimages.py:63-81,117-141)."""
+    return OpenImages(root_dir, 'train', resolution=1024, formatter='adv', hole_range=(0.0, 1.0), **kw)
+
+
+# ------------------------------------------------------------------------------------------------
+# random scale, random crop (the training formatters) and DTD (lib/data_factory/ds_texture.py)
+# ------------------------------------------------------------------------------------------------
+
+def draw_scale_crop(oh, ow, s, flips=False):
+    """The draws of AdvInpaintingFormatter / InpaintingFormatter for an oh x ow image and window s, in the reference's order
+    (ds_texture.py:138-147): nh, nw from ``npr.randint(s, max(o, int(s*1.2)) + 1)``, then ch, cw from ``npr.randint(0, n - s + 1)`` and,
+    with ``flips`` (the texture formatter), two ``npr.random() < 0.5`` draws, vertical first -> (nh, nw, ch, cw, flip_v, flip_h) ints.
+    The formatter draws its mask after these."""
+    oh, ow, s = int(oh), int(ow), int(s)
+    if s < 1 or oh < 1 or ow < 1:
+        raise ValueError(f'draw_scale_crop: sizes must be >= 1 (got {oh}x{ow}, s = {s})')
+    nh = npr.randint(s, max(oh, int(s * 1.2)) + 1)
+    nw = npr.randint(s, max(ow, int(s * 1.2)) + 1)
+    ch, cw = npr.randint(0, nh - s + 1), npr.randint(0, nw - s + 1)
+    fv = fh = False
+    if flips:
+        fv = npr.random() < 0.5
+        fh = npr.random() < 0.5
+    return int(nh), int(nw), int(ch), int(cw), int(fv), int(fh)
+
+
+def texture_list(root_dir, mode, mixed_order=False):
+    """load_info of ``texture`` (ds_texture.py:25-89): the lines 'type/file' of root_dir/dtd/labels/<name>.txt for every ``+``-separated
+    name in ``mode``, image at root_dir/dtd/images/<type>/<file>, unique_id = the file stem, in ds_base's order (sorted by unique_id).
+    The reference's check of the mode names never raises (each name fails one of its three ``find(...) != 0`` tests), so any list name is
+    accepted here too.  ``mixed_order`` (``mixed_order_on_texture_type``, :63-89): round-robin over the texture types in order of first
+    appearance, each id prefixed with its position as '{:05d}_' -- the prefix is what makes ds_base's sort keep that order."""
+    info = []
+    for m in mode.split('+'):
+        with open(os.path.join(root_dir, 'dtd', 'labels', m + '.txt')) as f:
+            refs = [li.strip() for li in f.readlines()]
+        for ref in refs:
+            texture_type, filename = os.path.split(ref)
+            info.append({'unique_id': os.path.splitext(filename)[0], 'filename': filename, 'texture_type': texture_type,
+                         'image_path': os.path.join(root_dir, 'dtd', 'images', texture_type, filename)})
+    if mixed_order:
+        group = {}
+        for e in info:
+            group.setdefault(e['texture_type'], []).append(e)
+        info, cnt = [], 0
+        while group:
+            for tt in list(group.keys()):
+                if not group[tt]:
+                    group.pop(tt)
+                    continue
+                e = dict(group[tt].pop(0))
+                e['unique_id'] = '{:05d}_'.format(cnt) + e['unique_id']
+                info.append(e)
+                cnt += 1
+    info = sorted(info, key=lambda x: x['unique_id'])
+    for idx, e in enumerate(info):
+        e['idx'] = idx
+    return info
+
+
+class Texture(torch.utils.data.Dataset):
+    """``texture`` + ``DefaultLoader`` + ``InpaintingFormatter`` (ds_texture.py:22-100,121-149) with the rescale, crop and flips moved
+    to the device: an item is {'image': uint8 [H,W,3] at the file's own size (``Image.open(...).convert('RGB')``), 'crop': the
+    formatter's draws for that size (``draw_scale_crop(H, W, resolution, flips=True)``), 'flip': False, 'unique_id'} and, with
+    ``host_masks``, 'mask' = ``RandomMask(resolution, hole_range)[0]`` drawn after them -- for the same numpy RNG state the reference
+    formatter's parameters and mask.  ``collate_ragged`` batches items into a ``RaggedU8Batch`` with ``crop``; ``DeviceFeeder`` computes
+    the windows on the device.  ``mode``: ``+``-separated list names under dtd/labels; the reference's mode check never raises, so any
+    name is accepted (``texture_list``)."""
+
+    def __init__(self, root_dir, mode, resolution, hole_range, mixed_order=False, host_masks=False, try_sample=None, repeat=1):
+        self.load_info = texture_list(root_dir, mode, mixed_order=mixed_order)
+        if try_sample is not None:
+            self.load_info = self.load_info[:try_sample]
+        self.resolution, self.hole_range = int(resolution), list(hole_range)
+        self.host_masks, self.repeat = bool(host_masks), repeat
+
+    def __len__(self):
+        return len(self.load_info) * self.repeat
+
+    def __getitem__(self, idx):
+        e = self.load_info[idx % len(self.load_info)]
+        u8 = _decode_rgb_unbounded(e['image_path'])           # ds_texture.py:12 lifts Pillow's pixel limit as ds_openimages.py does
+        item = {'image': u8, 'flip': False, 'unique_id': e['unique_id'],
+                'crop': draw_scale_crop(u8.shape[0], u8.shape[1], self.resolution, flips=True)}
+        if self.host_masks:
+            item['mask'] = _data.RandomMask(self.resolution, self.hole_range)[0]
+        return item
+
+
+def texture_train_256(root_dir, **kw):
+    """DTD training input at 256: ``texture`` (lists train1 + val1) + ``InpaintingFormatter(256)``."""
+    return Texture(root_dir, 'train1+val1', resolution=256, hole_range=(0.0, 1.0), **kw)
+
+
+def texture_train_512(root_dir, **kw):
+    """DTD training input at 512: ``texture`` (lists train1 + val1) + ``InpaintingFormatter(512)``."""
+    return Texture(root_dir, 'train1+val1', resolution=512, hole_range=(0.0, 1.0), **kw)
+
+
 class RaggedU8Batch:
     """A batch of decoded images of their own sizes: ``data`` uint8 [sum h*w*3] (HWC RGB images back to back, pinned when built in a
     process that owns the device), ``shapes`` int32 [B,3] = (h, w, byte offset), ``flip`` bool [B], ``ids``, ``masks`` float32 [B,R,R] or
     None.  ``DeviceFeeder`` / ``EvalLoop.run`` take it in place of an image tensor; ``pin_memory`` lets a DataLoader pin it.
     ``fit`` (OpenImages): the images are resized to ``content_size`` int32 [B,2] = (h', w') and padded to R x R instead of resized to
-    R x R (Places2: ``fit`` False, ``content_size`` None)."""
+    R x R (Places2: ``fit`` False, ``content_size`` None).
+    ``crop`` (the training formatters): int32 [B,6] = (nh, nw, ch, cw, flip_v, flip_h) of ``draw_scale_crop`` or None; with it the batch
+    becomes float32 windows on the device, cut from the images themselves or, when ``preresize``, from the loader's R x R resize."""
 
-    def __init__(self, data, shapes, flip, ids, masks=None, fit=False, content_size=None):
+    def __init__(self, data, shapes, flip, ids, masks=None, fit=False, content_size=None, crop=None, preresize=False):
         self.data, self.shapes, self.flip, self.ids, self.masks = data, shapes, flip, list(ids), masks
         self.fit, self.content_size = bool(fit), content_size
+        self.crop, self.preresize = crop, bool(preresize)
 
     def __len__(self):
         return int(self.shapes.shape[0])
@@ -451,8 +600,8 @@ class RaggedU8Batch:
 
 
 def collate_ragged(items):
-    """Places2 or OpenImages items -> RaggedU8Batch (``torch.utils.data.DataLoader(collate_fn=collate_ragged)``); items with a
-    'content_size' (OpenImages) make a ``fit`` batch."""
+    """Places2, OpenImages or Texture items -> RaggedU8Batch (``torch.utils.data.DataLoader(collate_fn=collate_ragged)``); items with a
+    'content_size' (OpenImages) make a ``fit`` batch, items with a 'crop' (the training formatters) a batch with ``crop``."""
     from .resize import pack_images
     data, shapes = pack_images([it['image'] for it in items])
     flip = torch.tensor([bool(it['flip']) for it in items], dtype=torch.bool)
@@ -465,4 +614,10 @@ def collate_ragged(items):
     if not fit and any('content_size' in it for it in items):
         raise ValueError('collate_ragged: a batch mixes OpenImages items (content_size) with items resized to R x R')
     content_size = torch.tensor([list(it['content_size']) for it in items], dtype=torch.int32).reshape(-1, 2) if fit else None
-    return RaggedU8Batch(data, shapes, flip, [it['unique_id'] for it in items], masks, fit=fit, content_size=content_size)
+    crop = None
+    if any('crop' in it for it in items):
+        if not all('crop' in it for it in items) or len({bool(it.get('preresize', False)) for it in items}) != 1:
+            raise ValueError('collate_ragged: a batch mixes items of different formatters (crop / preresize)')
+        crop = torch.tensor([list(it['crop']) for it in items], dtype=torch.int32).reshape(-1, 6)
+    return RaggedU8Batch(data, shapes, flip, [it['unique_id'] for it in items], masks, fit=fit, content_size=content_size, crop=crop,
+                         preresize=crop is not None and bool(items[0].get('preresize', False)))

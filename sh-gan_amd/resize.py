@@ -14,7 +14,12 @@ pass in the same arithmetic.  ``resize_reference`` is the same two passes in num
 
 OpenImages (``FixResolutionLoader`` of lib/data_factory/ds_openimages.py:63-81) resizes only images larger than R, to the box
 ``fit_size`` keeps their aspect ratio in, and pastes the result at the top-left of a zero R x R canvas: ``build_fit_table`` /
-``resize_fit_pad_u8`` (one launch, padding included) and the numpy ``fit_reference``."""
+``resize_fit_pad_u8`` (one launch, padding included) and the numpy ``fit_reference``.
+
+Training input of Places2, OpenImages and DTD (``AdvInpaintingFormatter`` / ``InpaintingFormatter``, ds_places2.py:183-207,
+ds_openimages.py:117-141, ds_texture.py:121-149): ``randcrop_bicubic`` -- the s x s window of torch's float bicubic resample to a drawn
+nh x nw, with the texture formatter's flips, straight from the decoded bytes in one launch (csrc/randcrop.hip); ``randcrop_reference``
+is the same arithmetic in numpy float32."""
 import ctypes
 
 import numpy as np
@@ -27,6 +32,8 @@ PRECISION_BITS = 22
 LDS_BYTES = 49152                    # csrc/resize.hip RS_LDS_BYTES: the horizontally resampled band of one workgroup
 DESC_INTS = 12                       # csrc/resize.hip: per-image descriptor
 FIT_DESC_INTS = 14                   # csrc/resize.hip: per-image descriptor of the fit-and-pad launch (+ h', w')
+RANDCROP_DESC_INTS = 9               # csrc/randcrop.hip: h, w, byte offset, nh, nw, ch, cw, flip_v, flip_h
+_RANDCROP_LUT = {}
 _COEF_CACHE = {}
 
 
@@ -291,3 +298,132 @@ def pack_images(images):
     for im, (h, w, o) in zip(images, shapes):
         buf[o:o + h * w * 3] = np.ascontiguousarray(im).reshape(-1)
     return packed, torch.from_numpy(shapes.astype(np.int32))
+
+
+# ------------------------------------------------------------------------------------------------
+# random scale, random crop: the training formatter of Places2 / OpenImages / DTD
+# ------------------------------------------------------------------------------------------------
+
+def randcrop_value_table():
+    """float32 [256]: the value the reference's formatter gives a byte -- ToTensor (``byte / 255``), then ``(v - 0.5) * 2``, each in
+    float32 (ds_places2.py:196-197)."""
+    return (np.arange(256, dtype=np.float32) / np.float32(255) - np.float32(0.5)) * np.float32(2)
+
+
+def _randcrop_lut(device):
+    key = str(device)
+    if key not in _RANDCROP_LUT:
+        _RANDCROP_LUT[key] = torch.from_numpy(randcrop_value_table()).to(device)
+    return _RANDCROP_LUT[key]
+
+
+def randcrop_desc(shapes, params):
+    """shapes int [B,3] = (h, w, byte offset), params int [B,6] = (nh, nw, ch, cw, flip_v, flip_h) -> the launch's int32 [B,9]
+    descriptor rows (h, w, offset, nh, nw, ch, cw, flip_v, flip_h)."""
+    shapes = np.asarray(shapes.numpy() if isinstance(shapes, torch.Tensor) else shapes, np.int64).reshape(-1, 3)
+    params = np.asarray(params.numpy() if isinstance(params, torch.Tensor) else params, np.int64).reshape(-1, 6)
+    if shapes.shape[0] != params.shape[0]:
+        raise ValueError(f'randcrop: {shapes.shape[0]} images but {params.shape[0]} parameter rows')
+    desc = np.concatenate([shapes, params], axis=1)
+    if desc.size and (np.abs(desc).max() >= 2 ** 31):
+        raise ValueError('randcrop: descriptor values must fit int32')
+    return np.ascontiguousarray(desc.astype(np.int32))
+
+
+def _cubic_axis(n_in, n_out, dst):
+    """torch's float32 source coordinate and cubic weights (A = -0.75) of the output indices ``dst`` along one axis ->
+    (first tap index i0 - 1, unclamped, int64 [n]; weights float32 [n, 4]); every step rounded to float32, in the kernel's order."""
+    f = np.float32
+    scale = f(n_in) / f(n_out)
+    src = scale * (np.asarray(dst).astype(f) + f(0.5)) - f(0.5)
+    fl = np.floor(src)
+    t = src - fl
+    A = f(-0.75)
+    x0, x1, x2, x3 = t + f(1), t, f(1) - t, f(2) - t
+
+    def inner(x):
+        return ((A + f(2)) * x - (A + f(3))) * x * x + f(1)
+
+    def outer(x):
+        return ((A * x - f(5) * A) * x + f(8) * A) * x - f(4) * A
+
+    w = np.stack([outer(x0), inner(x1), inner(x2), outer(x3)], axis=1)
+    assert w.dtype == f
+    return fl.astype(np.int64) - 1, w
+
+
+def _fma32(a, b, c):
+    """float32 fma: the product is exact in float64; the sum is rounded to float64 and then to float32."""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def randcrop_reference(img, s, params):
+    """Host reference of one image: uint8 HWC RGB, params = (nh, nw, ch, cw, flip_v, flip_h) -> float32 [3, s, s], the kernel's
+    arithmetic in numpy float32 (float32 coordinates and weights; per tap row the sum along x, then the four row sums along y, each
+    ``w0 * v0`` followed by three fused multiply-adds)."""
+    img = np.asarray(img, np.uint8)
+    h, w = img.shape[:2]
+    nh, nw, ch, cw, fv, fh = (int(v) for v in params)
+    s = int(s)
+    if s < 1 or nh < s or nw < s or ch < 0 or cw < 0 or ch + s > nh or cw + s > nw or h < 1 or w < 1:
+        raise ValueError(f'randcrop_reference: window [{ch}:{ch}+{s}, {cw}:{cw}+{s}] of {nh}x{nw} from a {h}x{w} image')
+    v = randcrop_value_table()[img]                                               # [h, w, 3]
+    ix, wx = _cubic_axis(w, nw, cw + np.arange(s))
+    iy, wy = _cubic_axis(h, nh, ch + np.arange(s))
+    cols = np.clip(ix[:, None] + np.arange(4), 0, w - 1)                          # [s, 4]
+    rows = np.clip(iy[:, None] + np.arange(4), 0, h - 1)
+    out = None
+    for jy in range(4):
+        r = v[rows[:, jy]]                                                        # [s, w, 3]
+        hsum = wx[None, :, 0, None] * r[:, cols[:, 0]]
+        for jx in range(1, 4):
+            hsum = _fma32(np.broadcast_to(wx[None, :, jx, None], hsum.shape), r[:, cols[:, jx]], hsum)
+        wj = np.broadcast_to(wy[:, jy, None, None], hsum.shape)
+        out = wj * hsum if out is None else _fma32(wj, hsum, out)
+    assert out.dtype == np.float32
+    if fv:
+        out = out[::-1]
+    if fh:
+        out = out[:, ::-1]
+    return np.ascontiguousarray(out.transpose(2, 0, 1))
+
+
+def randcrop_bicubic(src, desc_or_shapes, s, params=None, stream=None):
+    """The window launch.  Two source forms:
+      * ragged: ``src`` uint8 HIP tensor of packed HWC images (``pack_images`` / ``RaggedU8Batch.data``), ``desc_or_shapes`` the host
+        int [B,3] shapes (h, w, byte offset);
+      * planar: ``src`` uint8 HIP tensor [B,3,H,W] (what ``resize_bicubic_u8`` / ``resize_fit_pad_u8`` return), ``desc_or_shapes`` None.
+    ``params`` host int [B,6] = (nh, nw, ch, cw, flip_v, flip_h).  Alternatively ``desc_or_shapes`` is the full int [B,9] descriptor
+    (``randcrop_desc``) and ``params`` None.  -> float32 [B,3,s,s] in [-1, 1] (up to the cubic's overshoot) on src's device, computed
+    on ``stream`` (default: the current stream); the descriptor travels with the launch (pinned, asynchronous)."""
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8):
+        raise _lib.ShgError('randcrop_bicubic: src must be a uint8 HIP tensor: libshgan_hip has no CPU path')
+    planar = src.ndim == 4
+    if planar:
+        if src.shape[1] != 3:
+            raise _lib.ShgError(f'randcrop_bicubic: a planar source is [B,3,H,W] (got {tuple(src.shape)})')
+        src = src.contiguous()
+        B, _, H, W = src.shape
+        if desc_or_shapes is None:
+            desc_or_shapes = np.stack([np.full(B, H), np.full(B, W), np.arange(B) * (3 * H * W)], axis=1)
+    else:
+        src = src.contiguous().view(-1)
+    d = np.asarray(desc_or_shapes.numpy() if isinstance(desc_or_shapes, torch.Tensor) else desc_or_shapes)
+    if d.ndim == 2 and d.shape[1] == RANDCROP_DESC_INTS and params is None:
+        desc = np.ascontiguousarray(d.astype(np.int32))
+    elif params is None:
+        raise _lib.ShgError('randcrop_bicubic: params (nh, nw, ch, cw, flip_v, flip_h) are required with shapes')
+    else:
+        desc = randcrop_desc(d, params)
+    B, s = desc.shape[0], int(s)
+    dev = src.device
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    fn = _lib.get_lib().shg_randcrop_bicubic_planar_f32 if planar else _lib.get_lib().shg_randcrop_bicubic_ragged_f32
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        lut = _randcrop_lut(dev)
+        dd = torch.from_numpy(desc).pin_memory().to(dev, non_blocking=True)
+        out = torch.empty((B, 3, max(s, 0), max(s, 0)), dtype=torch.float32, device=dev)
+        check(fn(ctypes.c_void_p(src.data_ptr()), src.numel(), desc.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                 ctypes.c_void_p(dd.data_ptr()), ctypes.c_void_p(lut.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, s,
+                 ctypes.c_void_p(st.cuda_stream)), 'randcrop_bicubic')
+    return out
