@@ -417,6 +417,27 @@ size_t shg_lpips_head_scratch_bytes(int B, int h, int w);
 int shg_lpips_head_f32(const float* fp, const float* fg, const float* w, int B, int C, int h, int wd, void* scratch, size_t scratch_bytes,
                        double* out, void* stream);
 
+/* The scaling layer as a pass of its own, for a backbone whose first convolution is not conv1 above (net = 'vgg', sh-gan_amd/lpips.py):
+ * x [B,3,H,W] uint8 (lut [256]) or float32 -> y [B,3,H,W] float32 = s(v), v and s as in conv1 (same float32 steps, same host arrays). */
+int shg_lpips_scaling_f32(const void* x, const float* lut, float scale, float bias, const float* shift, const float* scaling, float* y, int B,
+                          int H, int W, void* stream);
+
+/* ---- Perceptual path length (`ppl2_wend`, lib/evaluator/stylegan_metrics/perceptual_path_length.py; sh-gan_amd/ppl.py drives it;
+ * csrc/ppl.hip): the sampler's image front end (:71-85) in one pass over the synthesis output.  x [N,C,H,W] float32 in [-1, 1], C = 1
+ * or 3, H == W -> y [N,3,S,S] float32:
+ *   crop (0 / 1): the window rows [3c, 7c), columns [2c, 6c), c = H / 8 (:72-75), else the whole image;
+ *   factor = img_resolution / 256 (:78): the mean over factor x factor boxes, S = side / factor; 0 and 1 copy; the side must be
+ *     divisible by the factor (the reference's reshape throws otherwise);
+ *   m = that mean rounded to float32 (the box is summed in float64: the correctly rounded mean up to a double rounding), then in
+ *     float32 u = (m + 1) * 127.5 (:83) and y = (u - mean[c]) / std[c], each step rounded once; a single-channel image is repeated to
+ *     three (:84-85) with each channel's own mean / std.  mean, std: HOST arrays of 3 floats, std > 0 (as shg_vgg16_frontend_f32).
+ * One thread per group of 4 / factor output pixels of a row reading float4 rows when factor is 1, 2 or 4, H % 4 == 0, the window's first
+ * column % 4 == 0, S divisible by the group and x, y 16-byte aligned; one output pixel per thread with scalar loads otherwise -- the
+ * same bits either way.  Every element of y is written exactly once; nothing outside the window is read.  C not in {1, 3}, H != W, an
+ * empty window, factor outside 0..256 or a side the factor does not divide: SHG_ERR_ARG, nothing launched. */
+int shg_ppl_frontend_f32(const float* x, float* y, int N, int C, int H, int W, int factor, int crop, const float* mean, const float* stdv,
+                         void* stream);
+
 /* ---- training tail on the gradient buckets (sh-gan_amd/optim.py drives it; csrc/optim.hip): gradient average + sanitisation + Adam
  * (lib/experiments/stylegan_default.py:159-166 with torch.optim.Adam, weight_decay 0, amsgrad off) and the G_ema update (:383-390).
  * Tables are int64 arrays ON THE DEVICE, one row per segment (= one parameter) plus a sentinel row; the last column of a row is the

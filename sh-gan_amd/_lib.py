@@ -137,6 +137,8 @@ _SIGS = {
     'shg_lpips_conv1_f32': [c_fp, c_fp, c_f, c_f, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_lpips_head_scratch_bytes': [c_i] * 3,
     'shg_lpips_head_f32': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, ctypes.c_size_t, c_fp, c_fp],
+    'shg_lpips_scaling_f32': [c_fp, c_fp, c_f, c_f, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp, c_i, c_i, c_i, c_fp],
+    'shg_ppl_frontend_f32': [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp],
     'shg_adam_tick': [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp],
     'shg_adam_buckets_f32': [c_fp, c_i, c_l, c_fp, c_f, c_i, c_i, c_fp],
     'shg_ema_lerp_f32': [c_fp, c_i, c_l, c_fp, c_fp],

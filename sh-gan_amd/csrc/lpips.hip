@@ -244,3 +244,43 @@ extern "C" int shg_lpips_head_f32(const float* fp, const float* fg, const float*
     SHG_CHECK_LAUNCH();
     return SHG_OK;
 }
+
+// ---- the scaling layer as a pass of its own, for a backbone whose first convolution is not conv1 above (net = 'vgg': its 3 x 3
+// convolutions run on the detector's kernel, which takes a finished float32 image).  Same operand forms and the same float32 steps as
+// conv1's load: v = lut[x] or ((x*scale + bias) - 0.5) * 2, then (v - shift_c) * float32(1 / scaling_c).
+namespace {
+template <bool U8>
+__global__ __launch_bounds__(256) void lp_scaling_kernel(const void* x, const float* lut, float scale, float bias, LpConv1Args k, float* y, long n,
+                                                         long HW) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const int c = (int)((e / HW) % 3);
+    float v;
+    if (U8) {
+        v = lut[reinterpret_cast<const uint8_t*>(x)[e]];
+    } else {
+        const float u = __fadd_rn(__fmul_rn(reinterpret_cast<const float*>(x)[e], scale), bias);
+        v = __fmul_rn(__fsub_rn(u, 0.5f), 2.f);
+    }
+    y[e] = lp_scaled(v, k.shift[c], k.inv[c]);
+}
+}  // namespace
+
+extern "C" int shg_lpips_scaling_f32(const void* x, const float* lut, float scale, float bias, const float* shift, const float* scaling, float* y,
+                                     int B, int H, int W, void* stream) {
+    SHG_CHECK_ARG(x && shift && scaling && y, "lpips_scaling: null pointer");
+    SHG_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && H <= 65536 && W <= 65536 && (long)B * 3 * H * W < (1L << 38), "lpips_scaling: bad geometry B %d %dx%d",
+                  B, H, W);
+    SHG_CHECK_ARG(scaling[0] != 0.f && scaling[1] != 0.f && scaling[2] != 0.f, "lpips_scaling: a scaling-layer scale of 0");
+    LpConv1Args k = {};
+    for (int c = 0; c < 3; ++c) {
+        k.shift[c] = shift[c];
+        k.inv[c] = (float)(1.0 / (double)scaling[c]);
+    }
+    const long HW = (long)H * W, n = (long)B * 3 * HW;
+    const dim3 grid((unsigned)shg_cdiv(n, 256));
+    if (lut) hipLaunchKernelGGL((lp_scaling_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, x, lut, scale, bias, k, y, n, HW);
+    else hipLaunchKernelGGL((lp_scaling_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, x, lut, scale, bias, k, y, n, HW);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}

@@ -27,14 +27,26 @@ Weights (``from_state_dict``): the package's own layout -- ``net.slice1.0.{weigh
 layouts were written from the published sources and NOT checked against the files, which are downloads and are not shipped.
 
 Pred and gt go through the network as one batch of 2B.  No launch plan depends on the batch size (``split_k=False``), the head adds in a
-fixed order without atomics: a pair's value is the same bits alone and inside any batch."""
+fixed order without atomics: a pair's value is the same bits alone and inside any batch.
+
+``net='vgg'`` (``LPIPS(net='vgg', ...)``, ``Lpips.from_state_dict(sd, net='vgg')``): the same class, operands, call and guarantees with the
+VGG16 backbone -- the thirteen 3 x 3 convolutions and 2 x 2 max pools of vgg16.py, taps after the ReLU of convolutions 1, 3, 6, 9 and 12
+of ``vgg16.CONV_IDS`` (relu1_2, 2_2, 3_3, 4_3, 5_3) before the pool that follows each, five ``lin`` vectors of the taps' widths.  The
+scaling layer is a pass of its own there (``scaling``: csrc/lpips.hip, the float32 steps of conv1's load), the convolutions run on
+``inception.conv_group(..., split_k=False)``, the pools on ``vgg16.maxpool2``; channel widths follow the tensors (a narrow net is a valid
+net); images of at least 16 x 16.  Keys: the package's ``net.slice1.{0,2}``, ``net.slice2.{5,7}``, ``net.slice3.{10,12,14}``,
+``net.slice4.{17,19,21}``, ``net.slice5.{24,26,28}`` ``.{weight,bias}`` + ``lin{0..4}.model.1.weight``, or torchvision's ``vgg16``
+``features.*`` (``classifier.*`` ignored) plus the package's ``vgg.pth``.  Like the alex layouts they were written from the published
+sources and NOT checked against the files.  ``mean`` / ``std`` / ``bgr`` are the constants of ``trunk``'s other caller, the path-length
+sampler (ppl.py), whose detector takes 0..255 images normalised as ``vgg16.Vgg16Features`` does; ``bgr=True`` flips the input-channel
+axis of the first convolution at load time and every per-channel constant (mean, std, shift, scale: given in the net's own order) with it."""
 import collections
 import ctypes
 
 import numpy as np
 import torch
 
-from . import _lib, inception, kernels
+from . import _lib, inception, kernels, vgg16
 from ._lib import ShgError, check
 
 SHIFT = (-.030, -.088, -.188)
@@ -45,6 +57,12 @@ TAP_CHANNELS = tuple(c[1] for c in CONVS)
 PACKAGE_CONV_KEYS = ('net.slice1.0', 'net.slice2.3', 'net.slice3.6', 'net.slice4.8', 'net.slice5.10')
 ALEXNET_CONV_KEYS = ('features.0', 'features.3', 'features.6', 'features.8', 'features.10')
 MIN_SIZE = 31             # the second max pool must see 3 x 3
+NETS = ('alex', 'vgg')
+VGG_TAPS = vgg16.POOL_AFTER               # index into vgg16.CONV_IDS of the convolution each tap follows (the one before every pool)
+VGG_SLICE_OF = (1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5)
+VGG_PACKAGE_CONV_KEYS = tuple(f'net.slice{s}.{i}' for s, i in zip(VGG_SLICE_OF, vgg16.CONV_IDS))
+VGG_FEATURES_CONV_KEYS = tuple(f'features.{i}' for i in vgg16.CONV_IDS)
+VGG_MIN_SIZE = 16         # four pools before the last tap
 
 
 def out_sizes(h):
@@ -127,6 +145,80 @@ def canonical_weights(sd, lin_sd=None):
     return out
 
 
+def _validate_vgg(sd, lins, prefixes, ignored_prefixes, what, lin_what):
+    """Widths follow the tensors: -> the 13 channel widths.  Raises ShgError naming the first missing key, unexpected key or wrong shape."""
+    conv_keys = [f'{k}.{p}' for k in prefixes for p in ('weight', 'bias')]
+    lin_keys = [f'lin{k}.model.1.weight' for k in range(5)]
+    same = lins is sd
+    for key in conv_keys + (lin_keys if same else []):
+        if key not in sd:
+            raise ShgError(f'lpips: {what} lacks {key!r}')
+    widths, cin, shapes = [], 3, {}
+    for k in prefixes:
+        w = sd[f'{k}.weight']
+        if w.ndim != 4 or w.shape[0] < 1:
+            raise ShgError(f"lpips: '{k}.weight' has shape {tuple(w.shape)}, expected (O, {cin}, 3, 3)")
+        shapes[f'{k}.weight'], shapes[f'{k}.bias'] = (int(w.shape[0]), cin, 3, 3), (int(w.shape[0]),)
+        cin = int(w.shape[0])
+        widths.append(cin)
+    lin_shapes = {f'lin{n}.model.1.weight': (1, widths[t], 1, 1) for n, t in enumerate(VGG_TAPS)}
+    optional = {}
+    if same:
+        shapes.update(lin_shapes)
+        optional = {f'lins.{n}.model.1.weight': (1, widths[t], 1, 1) for n, t in enumerate(VGG_TAPS)}
+        optional.update({'scaling_layer.shift': (1, 3, 1, 1), 'scaling_layer.scale': (1, 3, 1, 1)})
+    _validate(sd, shapes, optional, ignored_prefixes, what)
+    if not same:
+        _validate(lins, lin_shapes, {}, (), lin_what)
+    return widths
+
+
+def validate_vgg_state_dict(sd):
+    """The package's ``LPIPS(net='vgg')`` layout -> the 13 channel widths."""
+    return _validate_vgg(sd, sd, VGG_PACKAGE_CONV_KEYS, (), 'state_dict', None)
+
+
+def validate_vgg_state_dicts(vgg_sd, lin_sd):
+    """The two-file layout: torchvision ``vgg16`` (``classifier.*`` ignored) and the package's ``vgg.pth`` -> the 13 channel widths."""
+    return _validate_vgg(vgg_sd, lin_sd, VGG_FEATURES_CONV_KEYS, ('classifier.',), 'vgg16 state_dict', 'lin state_dict')
+
+
+def canonical_vgg_weights(sd, lin_sd=None):
+    """Either vgg layout (validated) -> {'conv{k}.weight', 'conv{k}.bias' (k < 13), 'lin{n}' [C_n], 'shift', 'scale', 'widths'} on the CPU."""
+    if lin_sd is None:
+        widths, prefixes, lins = validate_vgg_state_dict(sd), VGG_PACKAGE_CONV_KEYS, sd
+    else:
+        widths, prefixes, lins = validate_vgg_state_dicts(sd, lin_sd), VGG_FEATURES_CONV_KEYS, lin_sd
+    out = collections.OrderedDict(widths=tuple(widths))
+    for k, key in enumerate(prefixes):
+        out[f'conv{k}.weight'] = _f32(sd[f'{key}.weight'])
+        out[f'conv{k}.bias'] = _f32(sd[f'{key}.bias'])
+    for n in range(5):
+        out[f'lin{n}'] = _f32(lins[f'lin{n}.model.1.weight']).reshape(-1)
+        dup = f'lins.{n}.model.1.weight'
+        if lin_sd is None and dup in sd and not torch.equal(_f32(sd[dup]).reshape(-1), out[f'lin{n}']):
+            raise ShgError(f'lpips: {dup!r} differs from its duplicate \'lin{n}.model.1.weight\'')
+    out['shift'] = _f32(sd['scaling_layer.shift']).reshape(-1) if lin_sd is None and 'scaling_layer.shift' in sd else torch.tensor(SHIFT)
+    out['scale'] = _f32(sd['scaling_layer.scale']).reshape(-1) if lin_sd is None and 'scaling_layer.scale' in sd else torch.tensor(SCALE)
+    return out
+
+
+def vgg_out_sizes(h):
+    """Side of the five vgg taps for an input side h (2 x 2 floor pools)."""
+    return tuple(h >> k for k in range(5))
+
+
+def vgg_macs_per_image(widths, H, W):
+    """Multiply-adds of the thirteen convolutions of ONE image at H x W."""
+    total, cin, h, w = 0, 3, H, W
+    for k, c in enumerate(widths):
+        total += h * w * c * cin * 9
+        cin = c
+        if k in VGG_TAPS:
+            h, w = h // 2, w // 2
+    return total
+
+
 def value_table_cpu(operand, gt_range='pm1'):
     """float32 [256]: the value of every uint8 code as the network receives it.  'pred': the composite, ``float32(((u8 / 255) - 0.5) * 2)``
     with numpy float64 inside (shgan_default.py:283, eva_lpips.py:39,43).  'gt': a loader's decoded pixel -- its ``u8_value_table``
@@ -200,6 +292,35 @@ def conv1(images, wp, bp, operand='pred', gt_range='pm1', shift=SHIFT, scale=SCA
     return y
 
 
+def scaling(images, operand='pred', gt_range='pm1', shift=SHIFT, scale=SCALE, y=None):
+    """images [B,3,H,W] (uint8 or float32, forms of ``Lpips.__call__``) -> scaling_layer(value) [B,3,H,W] float32, the float32 steps of
+    conv1's load (one launch); ``y``: a contiguous float32 [B,3,H,W] view to write into."""
+    if operand not in ('pred', 'gt') or gt_range not in ('pm1', 'unit'):
+        raise ShgError(f"lpips: operand must be 'pred' or 'gt' and gt_range 'pm1' or 'unit' (got {operand!r}, {gt_range!r})")
+    if not isinstance(images, torch.Tensor) or images.ndim != 4 or images.shape[1] != 3:
+        raise ShgError('lpips: images must be a [B,3,H,W] tensor')
+    L = kernels._Launch()
+    if images.dtype == torch.uint8:
+        x = L.req(images, operand, dtype=torch.uint8)
+        lut = L.req(value_table(x.device, operand, gt_range), 'lut')
+        s, b = 1.0, 0.0
+    elif images.dtype == torch.float32:
+        x, lut = L.req(images, operand), None
+        s, b = (0.5, 0.5) if (operand == 'gt' and gt_range == 'pm1') else (1.0, 0.0)
+    else:
+        raise ShgError(f'lpips: {operand} must be uint8 or float32 (got {images.dtype})')
+    if y is None:
+        y = L.new(tuple(x.shape))
+    L.view(y, 'y')
+    if tuple(y.shape) != tuple(x.shape) or not y.is_contiguous() or y.dtype != torch.float32 or not y.is_cuda:
+        raise ShgError(f'lpips: scaling output {tuple(y.shape)} does not fit input {tuple(x.shape)}')
+    B, _, H, W = x.shape
+    with L:
+        check(_lib.get_lib().shg_lpips_scaling_f32(kernels._ptr(x), kernels._ptr(lut), s, b, _c3(shift), _c3(scale), kernels._ptr(y), B, H, W,
+                                                   L.stream()), 'lpips_scaling')
+    return y
+
+
 def head(fp, fg, w, out):
     """One tap: fp, fg [B,C,h,w] float32 (features of the preds / the gts), w [C] -> out [B] float64 += spatial mean of d."""
     L = kernels._Launch()
@@ -226,10 +347,16 @@ class Lpips:
     so the network runs on any stream (EvalLoop's side streams) concurrently with itself.  ``net(pred_u8, real, out=slice)`` is the
     callable ``EvalLoop(lpips=...)`` takes."""
 
-    def __init__(self, conv1_wb, ops, lins, shift, scale, device, split_k=False):
+    def __init__(self, conv1_wb, ops, lins, shift, scale, device, split_k=False, net='alex', mean=vgg16.CAFFE_MEAN, std=(1.0, 1.0, 1.0)):
+        if net not in NETS:
+            raise ShgError(f'lpips: net must be one of {NETS} (got {net!r})')
         self.conv1_wb, self.ops, self.lins = conv1_wb, ops, lins
         self.shift, self.scale = tuple(float(v) for v in shift), tuple(float(v) for v in scale)
-        self.device, self.split_k = torch.device(device), split_k
+        self.device, self.split_k, self.net = torch.device(device), split_k, net
+        self.min_size = MIN_SIZE if net == 'alex' else VGG_MIN_SIZE
+        # net='vgg' only: the normalisation of a 0..255 image for ``trunk``'s other caller (ppl.py), in the order the image is read (RGB)
+        self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+        self.widths = tuple(op.O for op in ops) if net == 'vgg' else None
 
     @classmethod
     def _from_canonical(cls, cw, device, split_k):
@@ -243,18 +370,67 @@ class Lpips:
         return cls(conv1_wb, ops, lins, cw['shift'].tolist(), cw['scale'].tolist(), dev, split_k)
 
     @classmethod
-    def from_state_dict(cls, sd, device='cuda', split_k=False):
-        """The package's full ``state_dict`` (``lpips.LPIPS(net='alex').state_dict()``)."""
+    def _from_canonical_vgg(cls, cw, device, mean, std, bgr):
+        if len(mean) != 3 or len(std) != 3 or min(float(v) for v in std) <= 0:
+            raise ShgError(f'lpips: mean and std must be three numbers each, std positive (got {mean!r}, {std!r})')
+        dev = torch.device(device)
+        ops, cin = [], 3
+        for k, c in enumerate(cw['widths']):
+            w = cw[f'conv{k}.weight']
+            if k == 0 and bgr:           # the net reads BGR planes: RGB images with the flipped weight are the same sum (as vgg16.py)
+                w = w.flip(1).contiguous()
+            wp, bp = inception.pack_weight(w.to(dev), cw[f'conv{k}.bias'].to(dev))
+            ops.append(inception.ConvOp(f'vgg.conv{k}', wp, bp, cin, c, (3, 3), (1, 1), (1, 1)))
+            cin = c
+        lins = [cw[f'lin{n}'].to(dev) for n in range(5)]
+        consts = [cw['shift'].tolist(), cw['scale'].tolist(), tuple(mean), tuple(std)]
+        if bgr:
+            consts = [tuple(v)[::-1] for v in consts]
+        return cls(None, ops, lins, consts[0], consts[1], dev, False, net='vgg', mean=consts[2], std=consts[3])
+
+    @classmethod
+    def from_state_dict(cls, sd, device='cuda', split_k=False, net='alex', mean=vgg16.CAFFE_MEAN, std=(1.0, 1.0, 1.0), bgr=False):
+        """The package's full ``state_dict`` (``lpips.LPIPS(net=net).state_dict()``).  ``mean``, ``std``, ``bgr``: net='vgg' only."""
+        if net not in NETS:
+            raise ShgError(f'lpips: net must be one of {NETS} (got {net!r})')
+        if net == 'vgg':
+            return cls._from_canonical_vgg(canonical_vgg_weights(sd), device, mean, std, bgr)
         return cls._from_canonical(canonical_weights(sd), device, split_k)
 
     @classmethod
-    def from_state_dicts(cls, alexnet_sd, lin_sd, device='cuda', split_k=False):
-        """torchvision's ``alexnet`` state_dict + the package's ``weights/v0.1/alex.pth``."""
+    def from_state_dicts(cls, alexnet_sd, lin_sd, device='cuda', split_k=False, net='alex', mean=vgg16.CAFFE_MEAN, std=(1.0, 1.0, 1.0), bgr=False):
+        """torchvision's ``alexnet`` (net='vgg': ``vgg16``) state_dict + the package's ``weights/v0.1/alex.pth`` (``vgg.pth``): the ``lin``
+        weights come from a file of their own."""
+        if net not in NETS:
+            raise ShgError(f'lpips: net must be one of {NETS} (got {net!r})')
+        if net == 'vgg':
+            return cls._from_canonical_vgg(canonical_vgg_weights(alexnet_sd, lin_sd), device, mean, std, bgr)
         return cls._from_canonical(canonical_weights(alexnet_sd, lin_sd), device, split_k)
+
+    def trunk(self, x):
+        """net='vgg': x [N,3,H,W] float32, a finished network input (after the scaling layer, or the path-length front end) -> the five
+        taps [N,C,h,w].  No launch plan depends on N."""
+        if self.net != 'vgg':
+            raise ShgError("lpips: trunk() is the net='vgg' backbone")
+        taps = []
+        for k, op in enumerate(self.ops):
+            y = torch.empty((x.shape[0], op.O) + tuple(x.shape[2:]), dtype=torch.float32, device=self.device)
+            inception.conv_group([(op, x, 0, y, 0)], split_k=False)
+            x = y
+            if k in VGG_TAPS:
+                taps.append(y)
+                if k != VGG_TAPS[-1]:
+                    x = vgg16.maxpool2(y)
+        return taps
 
     def features(self, pred, gt, gt_range='pm1'):
         """-> the five taps, each [2B,C,h,w] float32: the preds' features in [:B], the gts' in [B:]."""
         B, _, H, W = pred.shape
+        if self.net == 'vgg':
+            x = torch.empty((2 * B, 3, H, W), dtype=torch.float32, device=self.device)
+            scaling(pred, 'pred', gt_range, self.shift, self.scale, y=x[:B])
+            scaling(gt, 'gt', gt_range, self.shift, self.scale, y=x[B:])
+            return self.trunk(x)
         oh, ow = out_sizes(H), out_sizes(W)
         new = lambda k: torch.empty((2 * B, TAP_CHANNELS[k], oh[k], ow[k]), dtype=torch.float32, device=self.device)    # noqa: E731
         t0 = new(0)
@@ -277,8 +453,10 @@ class Lpips:
         if not (pred.is_cuda and gt.is_cuda):
             raise ShgError('lpips: pred and gt must reside on a HIP (cuda) device: there is no CPU path')
         B, _, H, W = pred.shape
-        if H < MIN_SIZE or W < MIN_SIZE:
-            raise ShgError(f'lpips: images of {H} x {W} are too small: the AlexNet taps need H, W >= {MIN_SIZE} (the second max pool must see 3 x 3)')
+        if H < self.min_size or W < self.min_size:
+            why = 'the AlexNet taps need H, W >= 31 (the second max pool must see 3 x 3)' if self.net == 'alex' else \
+                'the VGG16 taps need H, W >= 16 (four 2 x 2 pools before the last one)'
+            raise ShgError(f'lpips: images of {H} x {W} are too small: {why}')
         with torch.no_grad():
             if out is None:
                 out = torch.zeros(B, dtype=torch.float64, device=self.device)
@@ -289,3 +467,16 @@ class Lpips:
             for t, w in zip(self.features(pred, gt, gt_range), self.lins):
                 head(t[:B], t[B:], w, out)
         return out
+
+
+def LPIPS(net='alex', state_dict=None, lin_state_dict=None, device='cuda', **options):
+    """The package's constructor form: ``LPIPS(net='alex' | 'vgg', state_dict=full_sd)`` or ``LPIPS(net=..., state_dict=backbone_sd,
+    lin_state_dict=lin_sd)`` -> ``Lpips``.  The weights are downloads and are not shipped: a call without them raises.  ``options``:
+    ``split_k`` (alex), ``mean`` / ``std`` / ``bgr`` (vgg)."""
+    if net not in NETS:
+        raise ShgError(f'lpips: net must be one of {NETS} (got {net!r})')
+    if state_dict is None:
+        raise ShgError(f'lpips: LPIPS(net={net!r}) needs state_dict=...: the weights are downloads and are not shipped')
+    if lin_state_dict is None:
+        return Lpips.from_state_dict(state_dict, device=device, net=net, **options)
+    return Lpips.from_state_dicts(state_dict, lin_state_dict, device=device, net=net, **options)

@@ -926,10 +926,10 @@ class synthesis_block(nn.Module):
         if ic_n != 0 and res_link:
             self.skip = conv2d_layer(ic_n, oc_n, kernel_size=1, bias=False, up=2, down=1, resample_filter=resample_filter)
 
-    def forward(self, x, img, ws, fused_modconv=None, noise_mode='random'):
+    def forward(self, x, img, ws, fused_modconv=None, noise_mode='random', force_fp32=False):
         if self.const is not None:
             x = (self.const if grad_ops.wants_grad(self.const) else self.const.detach()).unsqueeze(0).repeat([ws.shape[0], 1, 1, 1])
-        x = grad_ops.to_block_dtype(x, self.use_fp16)                            # stylegan.py:486-495
+        x = grad_ops.to_block_dtype(x, self.use_fp16 and not force_fp32)         # stylegan.py:486-495
         fm = fused_modconv_rule(self, x, fused_modconv)                          # :488-490
         if self.res_link:
             y = self.skip(x, gain=np.sqrt(0.5))
@@ -969,13 +969,15 @@ class Synthesis(nn.Module):
                 self.num_ws += block.num_torgb
             setattr(self, 'b{}'.format(resj), block)
 
-    def forward(self, ws, noise_mode='random'):
+    def forward(self, ws, noise_mode='random', force_fp32=False):
+        """``force_fp32`` (the keyword perceptual_path_length.py:69 passes; the reference's own ``Synthesis`` does not take it): every
+        block runs in float32 whatever its ``use_fp16``."""
         ws = ws.to(torch.float32)
         x = img = None
         w_idx = 0
         for res in self.block_res:
             block = getattr(self, f'b{res}')
-            x, img = block(x, img, ws.narrow(1, w_idx, block.num_conv + block.num_torgb), noise_mode=noise_mode)
+            x, img = block(x, img, ws.narrow(1, w_idx, block.num_conv + block.num_torgb), noise_mode=noise_mode, force_fp32=force_fp32)
             w_idx += block.num_conv
         return img
 
