@@ -98,11 +98,11 @@ __device__ __forceinline__ void static_for(F&& f) {
     static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
 }
 
-__device__ __forceinline__ float conv_epilogue(const ConvParams& p, float v, int n, int o, long idx, float nz) {
+__device__ __forceinline__ float conv_epilogue(const ConvParams& p, const ShgAct& act, float v, int n, int o, long idx, float nz) {
     if (p.out_scale) v *= p.out_scale[n * p.O + o];
     v += nz;
     if (p.bias) v += p.bias[o];
-    v = p.act ? shg_lrelu_agc(v, p.alpha, p.gain, p.clamp) : v * p.gain;
+    v = shg_act_apply(v, act);
     if (p.residual) v += p.residual[idx];
     return v;
 }
@@ -433,6 +433,7 @@ __global__ __launch_bounds__(WO * WP * 64, OCC) void conv_mfma_kernel(const Conv
         ? p.tail_ws + ((size_t)(work - p.tail_first) * p.tail_ks + (tslice >= 0 ? tslice : 0)) * NREG * NT + tid : nullptr;
 
     // ---- epilogue: D[row = out channel][col = pixel]; row = (r&3) + 8*(r>>2) + 4*half
+    const ShgAct actc = shg_act_make(p.act, p.alpha, p.gain, p.clamp);
 #pragma unroll
     for (int np = 0; np < NP; ++np) {
         const int j = (wp * NP + np) * 32 + l31;
@@ -512,9 +513,8 @@ __global__ __launch_bounds__(WO * WP * 64, OCC) void conv_mfma_kernel(const Conv
                 for (int r = 0; r < 16; ++r) {
                     const int o = ob + (r & 3) + 8 * (r >> 2);
                     if (o >= p.O) continue;
-                    float v = acc[ph][mo][np][r] * osc[r] + nz + bs[r];
-                    v = p.act ? shg_lrelu_agc(v, p.alpha, p.gain, p.clamp) : v * p.gain;
-                    p.y[base + (long)o * plane] = v + rs[r];
+                    const float v = acc[ph][mo][np][r] * osc[r] + nz + bs[r];
+                    p.y[base + (long)o * plane] = shg_act_apply(v, actc) + rs[r];
                 }
             }
         }
@@ -524,6 +524,7 @@ __global__ __launch_bounds__(WO * WP * 64, OCC) void conv_mfma_kernel(const Conv
 // split-K tail: y = epilogue(sum_s part[s]) over an [NB, O, plane] tensor
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvParams p, long total, long plane) {
     const long stride = (long)gridDim.x * 256;
+    const ShgAct actc = shg_act_make(p.act, p.alpha, p.gain, p.clamp);
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += stride) {
         float v = 0.f;
         for (int s = 0; s < p.ksplit; ++s) v += p.part[(long)s * p.part_stride + e];
@@ -534,7 +535,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvParams p, 
         float nz = 0.f;
         if (p.noise_mode == 1) nz = p.noise[pix] * p.noise_strength;
         else if (p.noise_mode == 2) nz = p.noise[(long)n * plane + pix] * p.noise_strength;
-        p.y[e] = conv_epilogue(p, v, n, o, e, nz);
+        p.y[e] = conv_epilogue(p, actc, v, n, o, e, nz);
     }
 }
 
@@ -791,14 +792,11 @@ __global__ __launch_bounds__(256, 2) void conv1x1_gemm_kernel(const ConvParams p
                 for (int q = 0; q < 4; ++q) {
                     // (an expression of its own -- one contracted v4 * osc + bs -- not conv_epilogue's conditional multiply / adds and not shg_conv_tail's
                     // sum with a noise term: equal to either within rounding, bit identity is not claimed)
-                    float v = v4[q] * osc + bs;
-                    v = p.act ? shg_lrelu_agc(v, p.alpha, p.gain, p.clamp) : v * p.gain;
-                    out[q] = v + rs[q];
+                    out[q] = shg_act_apply(v4[q] * osc + bs, act) + rs[q];
                 }
                 *reinterpret_cast<f32x4*>(p.y + idx) = out;
             }
         }
-    (void)act;
 }
 
 // the GEMM form applies: stride-1 1x1 without style / noise operands, whole tiles, enough of them to fill the chip

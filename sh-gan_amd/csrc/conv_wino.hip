@@ -236,6 +236,7 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(const WinoParams p) {
     const long plane = (long)p.H * p.W;
     const int o_l = tid >> 5, t_l = tid & 31;
     // per-channel and per-pixel operands of all passes are requested up front (one latency, not four)
+    const ShgAct actc = shg_act_make(p.act, p.alpha, p.gain, p.clamp);
     float osc[2], bsv[2];
     f32x2 nzv[2][2];                          // [tb][row]
 #pragma unroll
@@ -293,7 +294,7 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(const WinoParams p) {
                 f32x2 out;
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) {
-                    out[jj] = shg_conv_tail(yv[i][jj], osc[ob], nzv[tb][i][jj] * p.noise_strength, bsv[ob], p.act, p.alpha, p.gain, p.clamp) + rs[jj];
+                    out[jj] = shg_conv_tail(yv[i][jj], osc[ob], nzv[tb][i][jj] * p.noise_strength, bsv[ob], actc) + rs[jj];
                 }
                 *reinterpret_cast<f32x2*>(p.y + blockIdx.y * p.part_stride + base + pix) = out;      // W % 4 == 0, ox even: aligned, both pixels inside
             }
@@ -365,6 +366,7 @@ extern "C" int shg_conv_weight_prep_wino_f32(const float* w, const float* wscale
 __global__ __launch_bounds__(256) void wino_split_reduce_kernel(const float* part, float* y, int ks, long total, long plane, int O, const float* out_scale,
                                                                 const float* bias, const float* noise, int noise_mode, float noise_strength, int act,
                                                                 float alpha, float gain, float clamp, const float* residual) {
+    const ShgAct actc = shg_act_make(act, alpha, gain, clamp);
     for (long e4 = (long)blockIdx.x * 256 + threadIdx.x; e4 * 4 < total; e4 += (long)gridDim.x * 256) {
         const long e = e4 * 4;                                    // W % 4 == 0: four pixels of one row
         f32x4 v = *reinterpret_cast<const f32x4*>(part + e);
@@ -382,7 +384,7 @@ __global__ __launch_bounds__(256) void wino_split_reduce_kernel(const float* par
         f32x4 out;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            out[j] = shg_conv_tail(v[j], osc, nz[j] * noise_strength, bs, act, alpha, gain, clamp) + rs[j];
+            out[j] = shg_conv_tail(v[j], osc, nz[j] * noise_strength, bs, actc) + rs[j];
         }
         *reinterpret_cast<f32x4*>(y + e) = out;
     }

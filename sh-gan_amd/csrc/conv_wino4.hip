@@ -54,7 +54,8 @@ __device__ __forceinline__ void wino4_bt(const T (&d)[6], T (&o)[6]) {
 }
 // 1-D output transform: A^T m, A^T = [[1,1,1,1,1,0],[0,1,-1,2,-2,0],[0,1,1,4,4,0],[0,1,-1,8,-8,1]]
 __device__ __forceinline__ void wino4_at(const float (&m)[6], float (&o)[4]) {
-    const float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
+    float s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
+    shg_opaque(s12); shg_opaque(d12); shg_opaque(s34); shg_opaque(d34);        // scalar on purpose (shg_device.h)
     o[0] = m[0] + s12 + s34;
     o[1] = d12 + 2.f * d34;
     o[2] = s12 + 4.f * s34;
@@ -181,11 +182,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
 #pragma unroll
             for (int j = 0; j < NU; ++j) ur[ks][j] = ubase[(size_t)c * ustride + (ks * NUNIT + j) * 64];
         };
-        f32x16 acc[NU];
-#pragma unroll
-        for (int j = 0; j < NU; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+        f32x16 acc[NU];                                          // first written by the first chunk's k-step 0 (C operand: inline 0), no zero fill
         const float* bbase = Vl + (pfirst * KC + half) * BT + l31;   // + pidx*KC*BT + ks*2*BT
 
         // prologue: weights of k-steps 0..2 of chunk 0 (slot 3 is filled at the top of the chunk that uses it), the first windows
@@ -193,10 +190,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
         float b[2][NP];
 #pragma unroll
         for (int ks = 0; ks < 3; ++ks) load_u(0, ks);
-#pragma unroll
-        for (int j = 0; j < NU; ++j) ur[3][j] = 0.f;
-#pragma unroll
-        for (int q = 0; q < NP; ++q) b[1][q] = 0.f;
         if constexpr (!XF) {
             dma_raw(0, 0);
             dma_raw(1, 1);
@@ -225,6 +218,9 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
         // while the first B operands of the next chunk are on their way from LDS.
         // Every iteration issues the same loads (past the end: re-fetches / zeros) so the compiler's wait counts for the weight
         // ring stay exact.
+        // The first chunk is peeled (FIRST): it has no previous k-step 3 to multiply -- those used to be NU MFMAs of zeros on
+        // zero-filled accumulators, 1 / 33 of the MFMA time of a 64-channel layer, plus 16 NU v_mov for the fill -- and its k-step 0
+        // takes an inline 0 as C operand.  Same bits (0 * 0 + 0 = +0), one register fewer, 1.5 KB more code.
         const int last = nch - 1;
         auto fetch = [&](const float* bb, int ks, int pb) __attribute__((always_inline)) {
 #pragma unroll
@@ -233,10 +229,15 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
         auto mma = [&](int ks, int pb, int j) __attribute__((always_inline)) {
             acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ur[ks][j], b[pb][j >> 1], acc[j], 0, 0, 0);
         };
+        auto mma_first = [&](int ks, int pb, int j) __attribute__((always_inline)) {
+            const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ur[ks][j], b[pb][j >> 1], z, 0, 0, 0);
+        };
         auto refill = [&](int c, int ks, int j) __attribute__((always_inline)) {
             ur[ks][j] = ubase[(size_t)c * ustride + (ks * NUNIT + j) * 64];
         };
-        for (int c = 0; c < nch; ++c) {
+        auto chunk = [&](auto first_c, int c) __attribute__((always_inline)) {
+            constexpr bool FIRST = decltype(first_c)::value;
             const int buf = c & 1;
             const int cn = c < last ? c + 1 : last;
             const float* bb = bbase + buf * V_SZ;
@@ -246,7 +247,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
             if constexpr (XF) sc = style_of(cn);
             fetch(bb, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            // MFMA m of the chunk: group m / NU (0 = k-step 3 of the previous chunk -- zeros the first time round --, 1..3 = k-steps
+            // MFMA m of the chunk: group m / NU (0 = k-step 3 of the previous chunk -- nothing the first time round --, 1..3 = k-steps
             // 0..2), unit m % NU.  The load that refills a weight slot is issued RFD MFMAs after the MFMA that read the slot: issued
             // right behind it, the load waits until the MFMA has released the register (about 30 cycles per MFMA when the wave has
             // the pipe to itself).
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
             };
 #pragma unroll
             for (int j = 0; j < NU; ++j) {
-                mma(3, 1, j);
+                if constexpr (!FIRST) mma(3, 1, j);
                 if constexpr (!XF) {
                     if (j < 2 * NPIECE) dma_piece(c + 2, buf, j / NPIECE, j % NPIECE);   // raw(c) was consumed during chunk c-1
                 }
@@ -274,7 +275,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int j = 0; j < NU; ++j) {
-                    mma(ks, ks & 1, j);
+                    if (FIRST && ks == 0) mma_first(ks, ks & 1, j);
+                    else mma(ks, ks & 1, j);
                     refill_m((ks + 1) * NU + j - RFD);
                     if constexpr (XF) {
                         if (ks == 0 && j < 6) tr_col(j, u, buf ^ 1);
@@ -292,7 +294,9 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-        }
+        };
+        chunk(std::true_type{}, 0);                              // nch >= 1: every K slice holds at least one chunk (shg_wino_split)
+        for (int c = 1; c < nch; ++c) chunk(std::false_type{}, c);
 #pragma unroll
         for (int j = 0; j < NU; ++j) mma(3, 1, j);
 
@@ -310,8 +314,9 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
         {
             const float* np_ = p.noise_mode ? p.noise + (p.noise_mode == 2 ? (long)n * plane : 0) : shg_wino4_zeros;
     #pragma unroll
-            for (int i = 0; i < 4; ++i) nz[i] = *reinterpret_cast<const f32x4*>(np_ + (p.noise_mode ? rowoff[i] : 0));
+            for (int i = 0; i < 4; ++i) nz[i] = *reinterpret_cast<const f32x4*>(np_ + (p.noise_mode ? rowoff[i] : 0)) * p.noise_strength;   // the noise term, once for all four passes
         }
+        const ShgAct actc = shg_act_make(p.act, p.alpha, p.gain, p.clamp);
         struct TailOps { float osc, bs; f32x4 rs[4]; };
         auto tail_load = [&](int pass, TailOps& t) __attribute__((always_inline)) {
             const int oo = o0 + (pass >> 1) * 32 + 16 * (pass & 1) + o_l;
@@ -334,7 +339,10 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
                 for (int cc = 0; cc < 6; ++cc) m[cc] = Mx[((r * 6 + cc) * 16 + o_l) * 32 + t_l];
                 wino4_at(m, a4);
     #pragma unroll
-                for (int k = 0; k < 4; ++k) tmp[r][k] = a4[k];
+                for (int k = 0; k < 4; ++k) {
+                    shg_opaque(a4[k]);
+                    tmp[r][k] = a4[k];
+                }
             }
             f32x4 out[4];
     #pragma unroll
@@ -344,7 +352,10 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
                 wino4_at(col, a4);
     #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    out[i][k] = shg_conv_tail(a4[i], t.osc, nz[i][k] * p.noise_strength, t.bs, p.act, p.alpha, p.gain, p.clamp) + t.rs[i][k];
+                    shg_opaque(a4[i]);
+                    float v = shg_conv_tail(a4[i], t.osc, nz[i][k], t.bs, actc);
+                    shg_opaque(v);                                    // (without this one the <2,16> and <4,8> tiles take 246 registers instead of 243)
+                    out[i][k] = v + t.rs[i][k];
                 }
             }
             if (pass < 3) tail_load(pass + 1, t);                     // ahead of this pass's stores

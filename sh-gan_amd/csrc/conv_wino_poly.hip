@@ -347,6 +347,7 @@ __device__ __forceinline__ void poly_body(const PolyParams& p, const PolySub& q,
     // (one memory latency instead of four)
     f32x2 pre_part[SCHEME == DB ? 4 : 1][2], pre_res[SCHEME == DB ? 4 : 1][2];
     float pre_bias[2] = {0.f, 0.f};
+    const ShgAct actc = shg_act_make(p.act, p.alpha, p.gain, p.clamp);      // (used by scheme DB's tail only)
     if constexpr (SCHEME == DB) {
 #pragma unroll
         for (int pass = 0; pass < 4; ++pass) {
@@ -421,8 +422,7 @@ __device__ __forceinline__ void poly_body(const PolyParams& p, const PolySub& q,
                         float v = part[cc] + m[j * 2 + cc] + m[(j + 1) * 2 + cc]                       // eo: m_j + m_{j+1}
                                 + m[6 + j * 3 + cc] + m[6 + j * 3 + cc + 1]                          // oe
                                 + m[12 + j * 2 + cc] + bs;
-                        v = p.act ? shg_lrelu_agc(v, p.alpha, p.gain, p.clamp) : v * p.gain;
-                        out[cc] = v + rs[cc];
+                        out[cc] = shg_act_apply(v, actc) + rs[cc];
                     }
                     *reinterpret_cast<f32x2*>(yr) = out;
                 }

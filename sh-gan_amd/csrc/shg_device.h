@@ -4,6 +4,12 @@
 #pragma once
 #include "shg_common.h"
 
+// Identity on a value in a VGPR that the optimiser cannot see through; it emits no instruction.  Placed on the scalars of a straight-line
+// fp32 chain (an inverse Winograd transform, a layer tail) it keeps the SLP vectoriser from pairing them into v_pk_* operations: a pair
+// wants its halves in adjacent registers, and in conv_wino4's epilogue the moves that arrange that outnumbered the instructions saved
+// and pushed the kernel from 243 registers into scratch.
+__device__ __forceinline__ void shg_opaque(float& v) { asm("" : "+v"(v)); }
+
 // native vectors: they stay in registers (HIP's float4 struct copies may not)
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -49,7 +55,9 @@ __device__ __forceinline__ unsigned shg_fastdiv(unsigned n, unsigned d, unsigned
 // The fused layer tail in its "defaults" form (absent operands passed as osc = 1, nzterm = 0, bs = 0), before the caller adds the
 // residual.  Sites that go through this function compute identical bits for identical operands; conv_mfma.hip's conv_epilogue
 // (conditional multiply / adds) and the polyphase kernels' tails (a different sum) are other expressions.
-__device__ __forceinline__ float shg_conv_tail(float v, float osc, float nzterm, float bs, int act, float alpha, float gain, float clamp) {
-    v = v * osc + nzterm + bs;
-    return act ? shg_lrelu_agc(v, alpha, gain, clamp) : v * gain;
+// The activation arrives as a ShgAct that the kernel builds ONCE from its launch parameters, outside every loop: the per-launch
+// decisions (activation on / off, clamp on / off) are then constants of the tail and not branches or compares per value.
+__device__ __forceinline__ float shg_conv_tail(float v, float osc, float nzterm, float bs, const ShgAct& a) {
+    v = __builtin_fmaf(v, osc, nzterm) + bs;         // the fused form the contraction of `v * osc + nzterm` always took, now independent of what the vectoriser pairs up
+    return shg_act_apply(v, a);
 }
