@@ -285,20 +285,22 @@ class _DemodWeightFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, prenorm):
         wn, wsq, sfac = kernels.demod_weight(weight.detach(), prenorm)
-        ctx.save_for_backward(wn, sfac)
+        ctx.save_for_backward(wn, sfac, weight)           # (the weight is an input of this node: saving it holds no extra memory)
         ctx.mark_non_differentiable(sfac)
         return wn, wsq, sfac
 
     @staticmethod
     def backward(ctx, gwn, gwsq, _gs):
-        wn, sfac = ctx.saved_tensors
+        wn, sfac, weight = ctx.saved_tensors
         if torch.is_grad_enabled():
             g = 0
             if gwn is not None:
                 g = g + gwn
             if gwsq is not None:
                 g = g + 2 * gwsq[:, :, None, None] * wn
-            s = sfac.reshape(-1, 1, 1, 1)
+            # sfac = wn / w = rsqrt(mean w^2) (the pre-normalisation cancels) depends on the weight: formed from it again here, so that a
+            # second derivative sees it (the saved ``sfac`` is a constant to autograd)
+            s = weight.square().mean([1, 2, 3], keepdim=True).rsqrt()
             return s * (g - wn * (g * wn).mean([1, 2, 3], keepdim=True)), None
         return kernels.demod_weight_backward(wn, sfac, None if gwn is None else gwn.contiguous(), None if gwsq is None else gwsq.contiguous()), None
 

@@ -384,4 +384,5 @@ def test_fused_modulation_tail_float32(gf, ch, shared_noise, act):
         g1, g2 = torch.autograd.grad([(y2 * gy.to(DEV)).sum()], [td2, dd2], create_graph=True)
         assert rel_err(c(g1), c(td.grad)) < 1e-6 and rel_err(c(g2), c(dd_.grad)) < 1e-5
         g1.square().sum().backward()
+    # (finite and non-zero only: the VALUE of the second gradient is pinned against float64 in tests/test_gpu_second_order.py, family modconv_tail)
     assert dd2.grad is not None and torch.isfinite(dd2.grad).all() and float(dd2.grad.abs().max()) > 0

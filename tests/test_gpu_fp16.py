@@ -334,6 +334,7 @@ def test_fused_modulation_tail_forward_backward(c, shared_noise):
         (g1, g2) = torch.autograd.grad([(y2.float() * gy.to(DEV).float()).sum()], [td2, dd2], create_graph=True)
         assert rel_err(c_(g1), c_(td.grad)) < 2e-3 and rel_err(c_(g2), c_(dd_.grad)) < 5e-3
         g1.float().square().sum().backward()             # d/dd of |gz * d|^2 exists (gz is constant in t)
+    # (finite and non-zero only: the VALUE of the second gradient is pinned against float64 in tests/test_gpu_second_order.py, the f16 rows of modconv_tail)
     assert dd2.grad is not None and torch.isfinite(dd2.grad).all() and float(dd2.grad.abs().max()) > 0
 
 
