@@ -315,6 +315,17 @@ int shg_mask_raster_f32(const int* records, const int* offsets, const int* flips
 int shg_mask_raster_box_f32(const int* records, const int* offsets, const int* flips, const int* disc_table, int max_half, const int* boxes,
                             float* mask, int* holes, int B, int s, void* stream);
 
+/* ---- LaMa thin / medium / thick masks (lib/data_factory/lama_mask_utils.py behind LamaMaskFormatter, ds_ffhq.py:352-381): the
+ * rasteriser of cv2.line(thickness > 1) -- OpenCV's ThickLine in 16.16 fixed point -- and of the box generator's rectangles, one
+ * workgroup per mask (csrc/mask_lama.hip).  Records of 8 int32 words: RECT (0, x0, x1, y0, y1) = columns [x0, x1) of rows [y0, y1);
+ * LINE (1, x0, y0, x1, y1, t, dpx, dpy) with dp = the 16.16 quad offset (cvRound(dy r), cvRound(dx r)) computed by the host.
+ * records_host / offsets_host are the HOST copies of records [total][8] / offsets [B+1] (device): every record is checked from them
+ * before the launch (type, |coordinate| <= 2048, t in [2, 1023], (t + 1) >> 1 <= rmax).  circle_table [rmax+1][rmax+1] (device): half
+ * width of row |j| of the filled circle of radius r, -1 = none.  mask [B,1,s,s] (1 keep / 0 hole, 16-byte aligned), holes [B] = hole
+ * pixel counts, WRITTEN (no zeroing needed).  s: multiple of 32 in [32, 512].  Not checked against cv2 itself. */
+int shg_mask_lama_f32(const int* records_host, const int* offsets_host, const int* records, const int* offsets, const int* circle_table,
+                      int rmax, float* mask, int* holes, int B, int total, int s, void* stream);
+
 /* ---- next row N1: FID statistics (lib/evaluator/eva_fid.py:251-263).  S [DP,DP] float64 += sum_b w_b [x_b,1][x_b,1]^T on the
  * fp64 matrix cores: S[:D,:D] = sum x x^T, S[:D,D] = sum x, S[D,D] = count (tiles on / above the diagonal only).
  * feats [B,D] float32 (float64 when is_f64), weights [B] or NULL, DP >= D+1 a multiple of 32. */

@@ -116,6 +116,7 @@ _SIGS = {
     'shg_conv2d_down_poly_f32': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_i, c_f, c_f, c_f, c_fp, c_fp],
     'shg_mask_raster_f32': [c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i, c_fp],
     'shg_mask_raster_box_f32': [c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_fp, c_i, c_i, c_fp],
+    'shg_mask_lama_f32': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_fid_accumulate_f64': [c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_inception_frontend_f32': [c_fp, c_fp, c_f, c_f, c_fp, c_i, c_i, c_i, c_fp],
     'shg_inception_packed_weight_elems': [c_i] * 4,

@@ -68,6 +68,16 @@ def RandomMask(s, hole_range=[0, 1]):
         return keep[np.newaxis, ...].astype(np.float32)
 
 
+def LamaMask(s, kind):
+    """One mask of the reference's ``LamaMaskFormatter(resolution=s, type=kind)`` (ds_ffhq.py:352-381): ``1 - MixedMaskGenerator(...)``,
+    1 = keep, 0 = hole -> float32 [1,s,s].  The draws come from numpy's global RNG in the reference's order; the strokes are rasterised
+    on the host by the restatement of OpenCV's thick line that the device kernel shares (masks.lama_draw_host) -- not checked against
+    ``cv2`` itself, which the reference draws with.  ``kind``: 'thin' | 'medium' | 'thick' (or 'lama_thin' ...), s: 256 | 512."""
+    from . import masks as _masks
+    painted = _masks.lama_draw_host(_masks.lama_mask_records(s, _masks.lama_setting(kind, s)), s)
+    return (1 - painted)[np.newaxis, ...].astype(np.float32)
+
+
 class DistributedSampler(torch.utils.data.Sampler):
     """Rank-strided index shard: indices[rank::world] of the (optionally shuffled) index list, padded
     with its leading entries (``extend``) or truncated so every rank gets the same count."""

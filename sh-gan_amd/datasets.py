@@ -8,6 +8,9 @@ Mirrors ``lib/data_factory/ds_ffhq.py``:
     (``torchvision.transforms.ToTensor``).  The reference decodes with ``pyspng``; Pillow yields the same pixels;
   * ``RandomMaskFormatter``   -- :332-347: ``x = image * 2 - 1``, horizontal flip with probability 1/2, ``RandomMask`` -- in this order of
     ``numpy.random`` draws, so a seeded worker produces the reference's sample stream;
+  * ``LamaMaskFormatter``     -- :352-381: the same with the LaMa thin / medium / thick masks (``data.LamaMask``; on the device:
+    ``masks.lama_masks``, ``DeviceFeeder(mask_kind='lama_thin', device_masks=True)``).  The reference draws these with ``cv2.line``; the
+    rasteriser here is a restatement of OpenCV's algorithm, not checked against ``cv2`` itself;
   * ``FFHQZip``               -- the ``ds_base.__getitem__`` composition (element -> loader -> formatter);
   * ``DeviceFeeder``          -- what ``shgan_default.py:267-274`` does per batch (``x = cat([mask - 0.5, real * mask])``), on the device:
     pinned staging, H2D on a copy stream overlapped with the previous batch's kernels, masks either from the host formatter or
@@ -110,10 +113,45 @@ class RandomMaskFormatter:
         return x, mask, element['unique_id']
 
 
-class FFHQZip(torch.utils.data.Dataset):
-    """``ffhqzip`` + ``ZipLoader`` + a formatter (ds_base.__getitem__ without its cache / transform options)."""
+MASK_KINDS = ('freeform', 'lama_thin', 'lama_medium', 'lama_thick')
 
-    def __init__(self, root_dir, mode, formatter=None, try_sample=None, repeat=1):
+
+def _check_mask_kind(who, mask_kind):
+    if mask_kind not in MASK_KINDS:
+        raise ValueError(f'{who}: mask_kind must be one of {MASK_KINDS} (got {mask_kind!r})')
+    return mask_kind
+
+
+class LamaMaskFormatter:
+    """ds_ffhq.py:352-381: (x in [-1,1], mask [s,s] float32 with 1 = known, unique_id) with the LaMa thin / medium / thick masks
+    (lama_mask_utils.py: ``1 - MixedMaskGenerator(**setting)(x)[0]``); one ``npr.rand()`` flip draw when ``random_flip``, then the mask's
+    draws.  Any (type, resolution) outside thin / medium / thick x 256 / 512 raises ``ValueError``, as in the reference.  The strokes are
+    rasterised by ``data.LamaMask`` -- a restatement of OpenCV's thick line, not checked against ``cv2`` itself."""
+
+    def __init__(self, random_flip=True, resolution=256, type='thin'):
+        from . import masks as _masks
+        if (type, resolution) not in _masks.LAMA_SETTINGS:
+            raise ValueError(f'LamaMaskFormatter: no setting for type {type!r} at resolution {resolution!r}')
+        self.random_flip, self.resolution, self.type = random_flip, resolution, type
+
+    def __call__(self, element):
+        x = element['image'] * 2 - 1
+        if self.random_flip and npr.rand() < 0.5:
+            x = x.flip(-1)
+        mask = _data.LamaMask(self.resolution, self.type)[0]
+        return x, mask, element['unique_id']
+
+
+class FFHQZip(torch.utils.data.Dataset):
+    """``ffhqzip`` + ``ZipLoader`` + a formatter (ds_base.__getitem__ without its cache / transform options).  ``mask_kind`` other than
+    'freeform' (configs ``ffhqzip_val{256,512}_inpainting_lama{1,2,3}``) installs ``LamaMaskFormatter(random_flip=False, resolution of
+    the mode, type)`` and takes no ``formatter`` of the caller's."""
+
+    def __init__(self, root_dir, mode, formatter=None, try_sample=None, repeat=1, mask_kind='freeform'):
+        if _check_mask_kind('FFHQZip', mask_kind) != 'freeform':
+            if formatter is not None:
+                raise ValueError('FFHQZip: pass either a formatter or a LaMa mask_kind, not both')
+            formatter = LamaMaskFormatter(random_flip=False, resolution=512 if '512' in mode else 256, type=mask_kind[5:])
         self.load_info = ffhqzip_list(root_dir, mode)
         if try_sample is not None:
             self.load_info = self.load_info[:try_sample]
@@ -137,9 +175,12 @@ class DeviceFeeder:
 
     The H2D copies of batch k+1 run on a copy stream while batch k's kernels execute (pinned staging buffers, one event per batch);
     ``device_masks`` draws the freeform masks on the device instead of taking the formatter's (same distribution and, for the same
-    numpy RNG state, the same bits: ``masks.random_masks``)."""
+    numpy RNG state, the same bits: ``masks.random_masks``).  ``mask_kind`` = 'lama_thin' | 'lama_medium' | 'lama_thick' draws the LaMa
+    masks of ``LamaMaskFormatter`` there instead (``masks.lama_masks``: one copy, one launch, no hole-count read); ``hole_range`` is
+    then ignored -- the LaMa generator has no rejection loop -- and a batch with content boxes (OpenImages) is refused: the reference
+    has no such config.  Host masks are staged as they come, whatever their kind."""
 
-    def __init__(self, device, resolution, hole_range=(0, 1), device_masks=False, own_stream=True):
+    def __init__(self, device, resolution, hole_range=(0, 1), device_masks=False, own_stream=True, mask_kind='freeform'):
         """``own_stream=False``: stage on the CALLER's stream instead of a copy stream -- for callers whose own stream carries nothing
         but this staging (EvalLoop: the generator runs on three side streams).  The copies still overlap with the generator (pinned
         source, asynchronous), the process stays within four HIP streams = the default number of hardware queues, and the mask
@@ -147,6 +188,7 @@ class DeviceFeeder:
         stream (measured: a full pipeline drain every third batch, MEASUREMENTS.md round 6)."""
         self.device = torch.device(device)
         self.resolution, self.hole_range, self.device_masks = resolution, tuple(hole_range), device_masks
+        self.mask_kind = _check_mask_kind('DeviceFeeder', mask_kind)
         if self.device.type == 'cuda' and not own_stream:
             self.copy_stream = None
             self._inline = True
@@ -190,6 +232,9 @@ class DeviceFeeder:
         boxes = None
         if isinstance(batch, RaggedU8Batch):
             mask, ids = batch.masks, batch.ids
+            if batch.fit and self.mask_kind != 'freeform':
+                from ._lib import ShgError
+                raise ShgError('DeviceFeeder: LaMa masks with content boxes (OpenImages) are not served: the reference has no such config')
             xd = self._resize_on_device(batch)
             x = xd
             if batch.fit and batch.crop is None:      # AdvInpaintingFormatter has no box fill (ds_openimages.py:129-141)
@@ -227,7 +272,10 @@ class DeviceFeeder:
             xd.record_stream(cur)
             if md is not None:
                 md.record_stream(cur)
-        if md is None:
+        if md is None and self.mask_kind != 'freeform':
+            # on the caller's stream, behind the wait above: nothing reads the device back, so there is nothing to keep off this stream
+            md, _ = _masks.lama_masks(xd.shape[0], self.resolution, self.mask_kind, device=self.device)
+        elif md is None:
             # on the copy stream: the rasteriser's hole-count read makes the host wait for the stream it runs on, and this one carries
             # input staging only (on the caller's stream the read waited behind whatever else the caller had queued there)
             if self.copy_stream is not None:
@@ -305,14 +353,22 @@ class Places2(torch.utils.data.Dataset):
     batches items into a ``RaggedU8Batch``; ``DeviceFeeder`` resizes it (Pillow's bicubic bit for bit) and flips on the device.
     Without ``host_masks`` the masks come from the device (``DeviceFeeder(device_masks=True)``, the same numpy draws).
 
+    ``mask_kind`` = 'lama_thin' | 'lama_medium' | 'lama_thick' (``LamaMaskFormatter``, the configs ``places2_val*_inpainting_lama{1,2,3}``):
+    host masks are ``data.LamaMask(resolution, kind)[0]`` instead, drawn after the flip; on the device, ``DeviceFeeder(mask_kind=...)``.
+
     ``formatter='adv'`` is the training input, ``AdvInpaintingFormatter`` (ds_places2.py:183-207) behind the same loader: no flip; the
     item carries 'crop' = ``draw_scale_crop(R, R, R, flips=False)`` (the loader's output is R x R) and 'preresize', and the mask is
     drawn after those draws.  ``DeviceFeeder`` resizes to R x R as above and cuts the window of the float bicubic rescale on the device."""
 
     def __init__(self, root_dir, mode, resolution=512, random_flip=False, hole_range=(0, 1), host_masks=False, try_sample=None, repeat=1,
-                 formatter='freeform'):
+                 formatter='freeform', mask_kind='freeform'):
         if formatter not in ('freeform', 'adv'):
             raise ValueError(f"Places2: formatter must be 'freeform' or 'adv' (got {formatter!r})")
+        self.mask_kind = _check_mask_kind('Places2', mask_kind)
+        if mask_kind != 'freeform':
+            if formatter != 'freeform':
+                raise ValueError("Places2: LaMa masks go with formatter='freeform' (LamaMaskFormatter has no scale / crop draws)")
+            LamaMaskFormatter(resolution=int(resolution), type=mask_kind[5:])        # ValueError outside the six settings
         self.load_info = places2_list(root_dir, mode)
         if try_sample is not None:
             self.load_info = self.load_info[:try_sample]
@@ -332,7 +388,9 @@ class Places2(torch.utils.data.Dataset):
                     'crop': draw_scale_crop(self.resolution, self.resolution, self.resolution, flips=False)}
         else:
             item = {'image': u8, 'flip': bool(self.random_flip and npr.rand() < 0.5), 'unique_id': e['unique_id']}
-        if self.host_masks:
+        if self.host_masks and self.mask_kind != 'freeform':
+            item['mask'] = _data.LamaMask(self.resolution, self.mask_kind)[0]
+        elif self.host_masks:
             item['mask'] = _data.RandomMask(self.resolution, self.hole_range)[0]
         return item
 
@@ -345,6 +403,20 @@ def places2_val256_inpainting(root_dir, **kw):
 def places2_val512_inpainting(root_dir, **kw):
     """configs/dataset/places2.yaml ``places2_val512_inpainting``."""
     return Places2(root_dir, 'val', resolution=512, random_flip=False, hole_range=(0.0, 1.0), **kw)
+
+
+def _places2_lama(resolution, kind):
+    def make(root_dir, **kw):
+        return Places2(root_dir, 'val', resolution=resolution, random_flip=False, hole_range=(0.0, 1.0), mask_kind=kind, **kw)
+    make.__doc__ = f"configs/dataset/places2.yaml: ``places2_val{resolution}_inpainting`` with ``LamaMaskFormatter(False, {resolution}, '{kind[5:]}')``."
+    return make
+
+
+# configs/dataset/places2.yaml ``places2_val{256,512}_inpainting_lama{1,2,3}``: 1 = thin, 2 = medium, 3 = thick
+places2_val256_inpainting_lama1, places2_val256_inpainting_lama2, places2_val256_inpainting_lama3 = (
+    _places2_lama(256, k) for k in ('lama_thin', 'lama_medium', 'lama_thick'))
+places2_val512_inpainting_lama1, places2_val512_inpainting_lama2, places2_val512_inpainting_lama3 = (
+    _places2_lama(512, k) for k in ('lama_thin', 'lama_medium', 'lama_thick'))
 
 
 def places2_challenge256_inpainting(root_dir, **kw):

@@ -366,6 +366,8 @@ class EvalLoop:
     form of this loop) made the staging stream share a hardware queue with a generator stream and the hole-count read waited for a whole batch
     (MEASUREMENTS.md, round 6).  ``latent_fn(ids, B) -> z`` replaces ``torch.randn`` (tests: per-item latents so that a result can be compared
     id by id); ``on_batch(ids, images_u8, event)`` hands every finished batch to a consumer (host metrics) without ending the loop.
+    ``mask_kind`` = 'lama_thin' | 'lama_medium' | 'lama_thick' draws the LaMa masks of ``LamaMaskFormatter`` instead (masks.lama_masks: no
+    hole-count read, so the host never waits for the device; ``hole_range`` is ignored).
 
     The options are documented with their evaluators (evaluators.py): ``feature_fn`` / ``fid_real`` / ``kid`` / ``inception_score`` ->
     DetectorStats, ``metrics`` / ``lpips`` -> PerImageColumns, ``pr`` -> PrecisionRecall.  ``evaluators`` maps 'detector' / 'columns' / 'pr'
@@ -374,7 +376,7 @@ class EvalLoop:
     def __init__(self, G, device, resolution, n_items, rank=0, world=1, noise_mode='random', seed=0, depth=None, feature_fn=None,
                  fid_dim=2048, latent_fn=None, device_masks=True, hole_range=(0, 1), keep_images=True, on_batch=None, step_fn=None,
                  fid_accumulate_fn=None, feeder_stream=False, timing=False, metrics=None, ssim_window=11, metrics_fn=None, fid_real=False,
-                 lpips=None, kid=None, inception_score=None, pr=None):
+                 lpips=None, kid=None, inception_score=None, pr=None, mask_kind='freeform'):
         from .datasets import DeviceFeeder
         self.timing, self.batch_done_events = timing, []      # timing: one timing event per finished batch (bench: steady-state rate)
         self.G, self.device, self.res = G, torch.device(device), int(resolution)
@@ -383,7 +385,8 @@ class EvalLoop:
         self.feature_fn, self.fid_dim, self.latent_fn, self.on_batch = feature_fn, fid_dim, latent_fn, on_batch
         self.step_fn = step_fn          # (x4, z, out) -> uint8 images: the CPU world-size-2 tests inject a stand-in; the product path is run_generator
         self.ids = shard_ids(self.n_items, self.rank, self.world)
-        self.feeder = DeviceFeeder(self.device, self.res, hole_range=hole_range, device_masks=device_masks, own_stream=feeder_stream)
+        self.feeder = DeviceFeeder(self.device, self.res, hole_range=hole_range, device_masks=device_masks, own_stream=feeder_stream,
+                                   mask_kind=mask_kind)
         self.images = (torch.empty((len(self.ids), 3, self.res, self.res), dtype=torch.uint8, device=self.device) if keep_images else None)
         self.seen = 0
         self.evaluators = {}
