@@ -140,6 +140,14 @@ int shg_conv2d_wino4_ws_f32(const float* x, const float* wu, float* y, int NB, i
                             const float* in_scale, const float* out_scale, const float* bias, const float* noise, int noise_mode,
                             float noise_strength, int act, float alpha, float gain, float clamp, const float* residual, void* workspace,
                             size_t ws_bytes, void* stream);
+/* the same launch with the route of the weight operands chosen by the caller (A/B measurements, route-agreement test): 0 as
+ * shg_conv2d_wino4_ws_f32 takes it (LDS ring; W >= 256 on 8 x 64 pixel tiles from 64 input channels on), 1 register ring, 2
+ * wave-private LDS ring on the tile shapes that hold one, both with W >= 256 on the 4 x 128 pixel tiles, 3 like 2 with W >= 256 on
+ * the 8 x 64 pixel tiles.  Same bits on every route. */
+int shg_conv2d_wino4_route_f32(const float* x, const float* wu, float* y, int NB, int I, int O, int OP, int H, int W,
+                               const float* in_scale, const float* out_scale, const float* bias, const float* noise, int noise_mode,
+                               float noise_strength, int act, float alpha, float gain, float clamp, const float* residual, int route,
+                               void* workspace, size_t ws_bytes, void* stream);
 /* mode 2 with out_mode 1 writes the four sub-pixel phases as planes [4][NB,O,H+1,W+1] (coalesced); this kernel applies the
  * 4x4 FIR of conv2d_resample.py:138 (pad 1) straight from the planes and fuses the synthesis-layer tail:
  * y [N,C,2H,2W] = lrelu_agc(FIR(mid)*gain*scale[n,c] + noise*noise_strength + bias[c]) + residual.  H, W = low-res extents. */

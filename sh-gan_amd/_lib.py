@@ -67,6 +67,7 @@ _SIGS = {
     'shg_conv2d_wino4_supported': [c_i] * 5,
     'shg_conv2d_wino4_f32': [c_fp, c_fp, c_fp] + [c_i] * 6 + [c_fp, c_fp, c_fp, c_fp, c_i, c_f, c_i, c_f, c_f, c_f, c_fp, c_fp],
     'shg_conv2d_wino4_ws_f32': [c_fp, c_fp, c_fp] + [c_i] * 6 + [c_fp, c_fp, c_fp, c_fp, c_i, c_f, c_i, c_f, c_f, c_f, c_fp, c_fp, ctypes.c_size_t, c_fp],
+    'shg_conv2d_wino4_route_f32': [c_fp, c_fp, c_fp] + [c_i] * 6 + [c_fp, c_fp, c_fp, c_fp, c_i, c_f, c_i, c_f, c_f, c_f, c_fp, c_i, c_fp, ctypes.c_size_t, c_fp],
     'shg_conv2d_wino4_workspace_bytes': [c_i] * 6,
     'shg_upfir_planar_f32': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_f, c_fp, c_fp, c_fp, c_i, c_f, c_i, c_f, c_f, c_f, c_fp, c_fp],
     'shg_upfir_planar_sep_supported': [c_i, c_i],

@@ -11,8 +11,11 @@
 // GEMM view: 36 independent products M_xi[o,t] = sum_i U_xi[i,o] V_xi[i,t] over 64 output channels x 32 blocks (4 x 8
 // blocks = 16 x 32 pixels) = 72 accumulator tiles of 32x32 on 8 waves: waves 0-3 own four positions (8 tiles) each, waves
 // 4-7 five positions (10 tiles) each -- one wave of either kind per SIMD.  K is consumed in chunks of 8 input channels:
-//   * U (pre-transformed weights, [O/64][chunk][k-step][unit][lane]) goes straight into registers: a ring of one chunk
-//     (4 k-steps x 8 or 10 operands), every slot re-loaded for the next chunk two MFMAs after the MFMA that read it;
+//   * U (pre-transformed weights, [O/64][chunk][k-step][unit][lane]) takes one of two routes (URING below).  Register ring: straight
+//     into registers, a ring of one chunk (4 k-steps x 8 or 10 operands), every slot re-loaded for the next chunk two MFMAs after
+//     the MFMA that read it.  LDS ring: every U operand is read by exactly one wave, so each wave copies its own operands by 16-byte
+//     LDS-DMA (four units = 1 KB per instruction, verbatim) into a private ring of two k-steps and reads them back with ds_read_b32
+//     two MFMAs behind the reader of the register it refills; its own counted vmcnt is the only ordering, no barrier is added;
 //   * the raw 18 x 40 window of a channel arrives by 16-byte LDS-DMA (waves 4-7, two channels each, issued as inline
 //     assembly so that the compiler does not drain the weight prefetch behind it);
 //   * waves 0-3 transform two channels each (B^T d B on the 6x6 patch read as conflict-free b128, styles applied) into
@@ -41,6 +44,20 @@ struct Tile {
     static constexpr int NPIECE = (PATCH4 + 63) / 64, RP = NPIECE * 256, R_SZ = KC * RP;
 };
 static_assert(2 * V_SZ >= NPOS * 16 * 32, "epilogue exchange buffer lives in the V region");
+// Wave-private U ring in LDS: two k-steps per wave.  A transform wave's k-step is 8 units = two DMA pieces; a fetch wave's is 10 units,
+// copied as three whole pieces into a slot of 12 (the upper half of the third piece re-copies units 8 and 9 into the padding: a half
+// piece would need a masked instruction).  4 x 2 x 8 + 4 x 2 x 12 units of 256 B = 40 960 B.
+constexpr int UR_XF = 2 * 8 * 64, UR_FE = 2 * 12 * 64, UR_SZ = 4 * UR_XF + 4 * UR_FE;            // floats
+constexpr int LDS_BYTES = 163840;
+// Which shapes can hold the ring beside V and the windows (the 4 x 128 px shape cannot: 24 576 B are left), and which ship with it.
+template <int TY, int TX> constexpr bool uring_fits() { return (2 * V_SZ + 2 * Tile<TY, TX>::R_SZ + UR_SZ) * 4 <= LDS_BYTES; }
+// Measured per layer of the 512^2 x 16 step (register ring -> LDS ring, same launch, arms interleaved): 16 x 32 px tiles 802 -> 746 us
+// (512 channels, 64^2), 204 -> 191 us (32^2, K split); 8 x 64 px 839 -> 806 us (256 channels, 128^2).
+template <int TY, int TX> constexpr bool uring_default() { return uring_fits<TY, TX>(); }
+// W >= 256 from this many input channels on: the 8 x 64 px tiles with the ring beat the 4 x 128 px tiles without (128 channels at
+// 256^2: 966 -> 939 us, 64 channels at 512^2: 1165 -> 1134 us).  Fewer channels were not measured and keep the 4 x 128 px tiles:
+// the ring saves per k-step, the longer store rows per tile, and with a chunk or two of K there is little loop to save in.
+constexpr int URING_WIDE_MIN_I = 64;
 }   // namespace wino4
 
 // 1-D input transform of F(4,3): B^T d, B^T = [[4,0,-5,0,1,0],[0,-4,-4,1,1,0],[0,4,-4,-1,1,0],[0,-2,-1,2,1,0],[0,2,-1,-2,1,0],[0,4,0,-5,0,1]]
@@ -62,13 +79,15 @@ __device__ __forceinline__ void wino4_at(const float (&m)[6], float (&o)[4]) {
     o[3] = d12 + 8.f * d34 + m[5];
 }
 
-template <int TY, int TX>
-__global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) {
+template <int TY, int TX, bool URING>
+__device__ __forceinline__ void conv_wino4_body(const WinoParams& p) {
     using namespace wino4;
     using T = Tile<TY, TX>;
     constexpr int PW = T::PW, PW4 = T::PW4, PATCH4 = T::PATCH4, RP = T::RP, R_SZ = T::R_SZ, NPIECE = T::NPIECE;
+    static_assert(!URING || (uring_fits<TY, TX>() && 2 * NPIECE == 6), "the U ring needs 40 960 B beside V and the windows; its load counts assume six window pieces");
     __shared__ __attribute__((aligned(16))) float Vl[2 * V_SZ];      // [2][36][KC][32]
     __shared__ __attribute__((aligned(16))) float Rl[2 * R_SZ];      // [2][KC][RP]
+    __shared__ __attribute__((aligned(16))) float Ul[URING ? UR_SZ : 4];     // [wave][2 slots][8 or 12 units][64 lanes]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -177,10 +196,64 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
         // weights: a register ring of one chunk; slot (ks, j) = MFMA A operand of unit 2*pfirst + j at k-step ks
         constexpr size_t ustride = (size_t)4 * NUNIT * 64;       // floats per chunk
         const float* ubase = p.wu + ((size_t)otile * p.nchunk * 4 * NUNIT + 2 * pfirst) * 64 + lane + (size_t)c0 * ustride;
-        float ur[4][NU];
+        float ur[URING ? 1 : 4][NU];                             // LDS ring: the operands of the k-step being multiplied only
         auto load_u = [&](int c, int ks) __attribute__((always_inline)) {
 #pragma unroll
             for (int j = 0; j < NU; ++j) ur[ks][j] = ubase[(size_t)c * ustride + (ks * NUNIT + j) * 64];
+        };
+        // LDS ring.  The MFMA groups of the whole K loop are numbered g = -1, 0, 1, ...: group g multiplies k-step g (chunk g / 4,
+        // k-step g % 4) out of ur[0]; slot g & 1 of the ring holds k-step g.  In chunk c the groups are G = 0..3 with g = 4c - 1 + G,
+        // so every slot index below is a constant.  MFMA j of group g is followed by
+        //   * the read that refills the register MFMA j-2 used: unit j-2 of k-step g+1 (slot G & 1), for j < 2 unit NU-2+j of k-step g
+        //     itself (slot (G+1) & 1) -- the same two-MFMA distance as the register ring's refills;
+        //   * behind MFMA 3, 7 (and 9): the DMA piece that overwrites units 0..3, 4..7 (8..9) of slot (G+1) & 1 with k-step g+2.  Those
+        //     units were read during group g-1 (the last two just now) and their reads have returned once MFMA 3, 7 (9) could issue.
+        // A read is ordered behind its piece by this wave's counted vmcnt alone (u_wait below): no other wave touches the ring.
+        constexpr int SU = XF ? 8 : 12, NPC = XF ? 2 : 3;        // units per slot, pieces per k-step
+        float* uring = Ul + (XF ? wave * UR_XF : 4 * UR_XF + (wave - 4) * UR_FE);
+        const float* usrc = ubase - lane + lane * 4;             // piece q of a k-step: + q * 256
+        const float* usrc2 = ubase - lane + 512 + (lane & 31) * 4;   // third piece of a fetch wave: units 8, 9, and 8, 9 again
+        auto u_piece = [&](int c, int ks, int slot, int q) __attribute__((always_inline)) {
+            const float* src = (q < 2 ? usrc + q * 256 : usrc2) + ((size_t)c * ustride + ks * NUNIT * 64);
+            const unsigned lds = __builtin_amdgcn_readfirstlane(
+                (unsigned)(size_t)(__attribute__((address_space(3))) void*)(uring + (slot * SU + q * 4) * 64));
+            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(src) : "m0", "memory");
+        };
+        auto u_wait = [&](int n) __attribute__((always_inline)) {       // n is a constant wherever this is called
+            switch (n) {
+            case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+            case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+            case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+            case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+            case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+            case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
+            case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
+            default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+            }
+        };
+        // What follows MFMA j of group G in chunk c (cn: the next chunk, clamped; first: the peeled chunk's group 0, which has no
+        // k-step of its own).  The in-order vmcnt queue of a transform wave holds U pieces only: the piece about to be read is always
+        // the older of two.  A fetch wave also issues the six window pieces, behind MFMAs 0..5 of group 0 and ahead of that MFMA's U
+        // traffic; counting the instructions issued after the needed piece:
+        //   j = 0 (piece 2 of k-step g, issued behind MFMA 9 of group G-2): the 3 pieces of group G-1, + 6 windows when G-1 = 0,
+        //          + the window just issued when G = 0;
+        //   j = 2 (piece 0 of k-step g+1, behind MFMA 3 of group G-1): pieces 1, 2 of that group, + windows 4, 5 when G-1 = 0,
+        //          + windows 0..2 when G = 0;
+        //   j = 6 (piece 1 of k-step g+1, behind MFMA 7 of group G-1): piece 2 of that group and piece 0 of this one, + 6 windows when G = 0.
+        // The peeled chunk issues the same loads as any other, so the counts hold from its group 1 on; in its group 0 k-step 0 is
+        // complete already (prologue), and any count is a safe one.
+        auto u_step = [&](bool first, int c, int cn, int G, int j) __attribute__((always_inline)) {
+            if constexpr (XF) {
+                if (j == 2 || j == 6) u_wait(1);
+            } else {
+                if (j == 0) u_wait(3 + (G == 1 ? 6 : 0) + (G == 0 ? 1 : 0));
+                if (j == 2) u_wait(2 + (G == 1 ? 2 : 0) + (G == 0 ? 3 : 0));
+                if (j == 6) u_wait(2 + (G == 0 ? 6 : 0));
+            }
+            if (j >= 2) ur[0][j - 2] = uring[((G & 1) * SU + j - 2) * 64 + lane];
+            else if (!first) ur[0][NU - 2 + j] = uring[(((G + 1) & 1) * SU + NU - 2 + j) * 64 + lane];
+            if (j == 3 || j == 7 || (!XF && j == 9))             // k-step g+2 = (c, G+1), from group 3: k-step 0 of the next chunk
+                u_piece(G < 3 ? c : cn, (G + 1) & 3, (G + 1) & 1, j == 3 ? 0 : (j == 7 ? 1 : 2));
         };
         f32x16 acc[NU];                                          // first written by the first chunk's k-step 0 (C operand: inline 0), no zero fill
         const float* bbase = Vl + (pfirst * KC + half) * BT + l31;   // + pidx*KC*BT + ks*2*BT
@@ -188,8 +261,13 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
         // prologue: weights of k-steps 0..2 of chunk 0 (slot 3 is filled at the top of the chunk that uses it), the first windows
         // and the first transform
         float b[2][NP];
+        if constexpr (URING) {
 #pragma unroll
-        for (int ks = 0; ks < 3; ++ks) load_u(0, ks);
+            for (int q = 0; q < NPC; ++q) u_piece(0, 0, 0, q);   // k-step 0; the peeled chunk's group 0 fetches k-step 1 and reads k-step 0
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < 3; ++ks) load_u(0, ks);
+        }
         if constexpr (!XF) {
             dma_raw(0, 0);
             dma_raw(1, 1);
@@ -227,11 +305,11 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
             for (int q = 0; q < NP; ++q) b[pb][q] = bb[(q * KC + ks * 2) * BT];
         };
         auto mma = [&](int ks, int pb, int j) __attribute__((always_inline)) {
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ur[ks][j], b[pb][j >> 1], acc[j], 0, 0, 0);
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ur[URING ? 0 : ks][j], b[pb][j >> 1], acc[j], 0, 0, 0);
         };
         auto mma_first = [&](int ks, int pb, int j) __attribute__((always_inline)) {
             const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ur[ks][j], b[pb][j >> 1], z, 0, 0, 0);
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ur[URING ? 0 : ks][j], b[pb][j >> 1], z, 0, 0, 0);
         };
         auto refill = [&](int c, int ks, int j) __attribute__((always_inline)) {
             ur[ks][j] = ubase[(size_t)c * ustride + (ks * NUNIT + j) * 64];
@@ -262,7 +340,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
                 if constexpr (!XF) {
                     if (j < 2 * NPIECE) dma_piece(c + 2, buf, j / NPIECE, j % NPIECE);   // raw(c) was consumed during chunk c-1
                 }
-                if (j >= RFD) refill_m(j - RFD);
+                if constexpr (URING) u_step(FIRST, c, cn, 0, j);
+                else if (j >= RFD) refill_m(j - RFD);
                 if constexpr (XF) {
                     if (j < 6) tr_read(j, w[j & 1], buf ^ 1);                     // raw(c+1) landed before the previous barrier
                     if (j >= 1 && j < 7) tr_row(j - 1, w[(j - 1) & 1], u, sc);
@@ -277,18 +356,22 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
                 for (int j = 0; j < NU; ++j) {
                     if (FIRST && ks == 0) mma_first(ks, ks & 1, j);
                     else mma(ks, ks & 1, j);
-                    refill_m((ks + 1) * NU + j - RFD);
+                    if constexpr (URING) u_step(false, c, cn, ks + 1, j);
+                    else refill_m((ks + 1) * NU + j - RFD);
                     if constexpr (XF) {
                         if (ks == 0 && j < 6) tr_col(j, u, buf ^ 1);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
+            if constexpr (!URING) {
 #pragma unroll
-            for (int m = 4 * NU - RFD; m < 4 * NU; ++m) refill_m(m);
+                for (int m = 4 * NU - RFD; m < 4 * NU; ++m) refill_m(m);
+            }
             // the last window piece went out ahead of all but 2*NPIECE - 1 - RFD of the chunk's 4*NU weight loads: in-order retirement makes
-            // "at most that many outstanding" mean "the window has landed" without waiting for the weights
-            if constexpr (!XF) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * NU - 2 * NPIECE + 1 + RFD) : "memory");
+            // "at most that many outstanding" mean "the window has landed" without waiting for the weights.  LDS ring: behind the last
+            // window piece came pieces 1, 2 of group 0 and the three of groups 1..3 each (the ring's own waits retired it long ago).
+            if constexpr (!XF) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(URING ? 2 + 3 * NPC : 4 * NU - 2 * NPIECE + 1 + RFD) : "memory");
             // raw barrier: __syncthreads() carries a release fence that the compiler lowers to `s_waitcnt vmcnt(0)`, i.e. a wait for
             // the weight loads just issued.  LDS traffic is ordered by lgkmcnt(0), the DMA by the count above.
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -298,7 +381,16 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
         chunk(std::true_type{}, 0);                              // nch >= 1: every K slice holds at least one chunk (shg_wino_split)
         for (int c = 1; c < nch; ++c) chunk(std::false_type{}, c);
 #pragma unroll
-        for (int j = 0; j < NU; ++j) mma(3, 1, j);
+        for (int j = 0; j < NU; ++j) {
+            mma(3, 1, j);
+            if constexpr (URING) {                               // the last two operands of the last k-step; nothing is fetched any more
+                if (!XF && j == 0) u_wait(3);                    // (piece 2 of this k-step, then the three pieces of the last group 3)
+                if (j < 2) ur[0][NU - 2 + j] = uring[(SU + NU - 2 + j) * 64 + lane];
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // the pieces fetched past the end of K land in the ring while the MFMAs above run; none is left in flight behind the kernel
+        if constexpr (URING) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
         // epilogue: four passes (channel block ob, row half h) of 16 channels x 32 blocks x 36 positions through LDS
         // Operands of the fused tail.  Every load is unconditional (absent operands read a block of zeros) and the loads of pass
@@ -390,6 +482,17 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) 
     else body(std::integral_constant<int, 10>{}, std::false_type{});
 }
 
+// The U route a shape ships with runs under the plain name; the other one under conv_wino4_alt_kernel (route argument of
+// shg_conv2d_wino4_route_f32: the A/B arm, and the comparator of tests/test_gpu_wino4_uring.py -- both routes give the same bits).
+template <int TY, int TX>
+__global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const WinoParams p) {
+    conv_wino4_body<TY, TX, wino4::uring_default<TY, TX>()>(p);
+}
+template <int TY, int TX>
+__global__ __launch_bounds__(512, 2) void conv_wino4_alt_kernel(const WinoParams p) {
+    conv_wino4_body<TY, TX, !wino4::uring_default<TY, TX>()>(p);
+}
+
 // U = G g G^T per (o, i), G = [[1/4,0,0],[-1/6,-1/6,-1/6],[-1/6,1/6,-1/6],[1/24,1/12,1/6],[1/24,-1/12,1/6],[0,0,1]]; g = w[o,i] * scale[o].
 // Layout wu[otile][chunk][k-step][unit][lane]: unit u = (position u/2, channel block u%2); lane = (i & 1) * 32
 // + o % 32 holds the MFMA A operand of k-step (i % 8) / 2.
@@ -457,12 +560,15 @@ extern "C" int shg_conv2d_wino4_supported(int NB, int I, int O, int H, int W) {
 }
 
 // y = act(out_scale[n,o] * conv3x3_same(x * in_scale[n,i], w) + noise*noise_strength + bias[o]) + residual, stride 1, pad 1.
-static int wino4_plan(WinoParams& p, int NB, int I, int OP, int H, int W) {
+static int wino4_plan(WinoParams& p, int NB, int I, int OP, int H, int W, int route = 0) {
     // tile shape: the same 32 blocks as 16 x 32 pixels, 8 x 64 for W >= 128 or 4 x 128 for W >= 256.  The 8 x 64 window has the
     // same area as the 16 x 32 one (10 x 72 against 18 x 40 floats per channel), the 4 x 128 one a fourth piece per channel
     // (6 x 136), but every output row piece is 256 / 512 contiguous bytes instead of 128, which is what the store path wants
     // (DESIGN section 5): syn512.conv1 1286 -> 1237 -> 1226 us, 256^2 layers 1037 -> 1004 -> 990; at W = 64 no gain (809 vs 813).
-    const int shape = (W >= 256 && H >= 4) ? 2 : ((W >= 128 && H >= 8) ? 1 : 0);
+    // The 4 x 128 shape has no room for the LDS weight ring: from URING_WIDE_MIN_I channels on, W >= 256 stays on the 8 x 64 shape
+    // (route: the A/B arms of shg_conv2d_wino4_route_f32 -- 1 and 2 keep the rule above, 3 takes the 8 x 64 shape whatever I).
+    const bool narrow = route == 3 || (route == 0 && I >= wino4::URING_WIDE_MIN_I);
+    const int shape = (W >= 256 && H >= 4 && !(narrow && H >= 8)) ? 2 : ((W >= 128 && H >= 8) ? 1 : 0);
     p.tiles_x = shg_cdiv(W, 32 << shape); p.tiles_y = shg_cdiv(H, 16 >> shape);
     p.n_ttiles = p.tiles_x * p.tiles_y * NB; p.n_otiles = OP / 64; p.nchunk = shg_cdiv(I, wino4::KC);
     return shape;
@@ -476,23 +582,40 @@ extern "C" size_t shg_conv2d_wino4_workspace_bytes(int NB, int I, int O, int OP,
     return shg_wino_split_bytes((long)p.n_ttiles * p.n_otiles, p.nchunk, (size_t)NB * O * H * W * sizeof(float));
 }
 
-extern "C" int shg_conv2d_wino4_ws_f32(const float* x, const float* wu, float* y, int NB, int I, int O, int OP, int H, int W,
-                                       const float* in_scale, const float* out_scale, const float* bias, const float* noise,
-                                       int noise_mode, float noise_strength, int act, float alpha, float gain, float clamp,
-                                       const float* residual, void* workspace, size_t ws_bytes, void* stream) {
+// Launch of one tile shape: the weight route the shape ships with, or the other one where the shape has both
+template <int TY, int TX>
+static void wino4_launch(const WinoParams& p, dim3 grid, bool uring, hipStream_t s) {
+    if constexpr (wino4::uring_fits<TY, TX>()) {
+        if (uring != wino4::uring_default<TY, TX>()) {
+            hipLaunchKernelGGL((conv_wino4_alt_kernel<TY, TX>), grid, dim3(wino4::NT), 0, s, p);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((conv_wino4_kernel<TY, TX>), grid, dim3(wino4::NT), 0, s, p);
+}
+
+// shg_conv2d_wino4_ws_f32 with the weight route chosen by the caller: 0 as shipped (per tile shape, by measurement), 1 register
+// ring, 2 wave-private LDS ring on the shapes that hold one (16 x 32 and 8 x 64 px; 4 x 128 px has the register ring only), both with
+// W >= 256 on the 4 x 128 px tiles, 3 like 2 with W >= 256 on the 8 x 64 px tiles.  Every 4 x 4 output block is the same sums in
+// the same order on every route and tile shape: the routes give the same bits (as long as the K split is the same).
+extern "C" int shg_conv2d_wino4_route_f32(const float* x, const float* wu, float* y, int NB, int I, int O, int OP, int H, int W,
+                                          const float* in_scale, const float* out_scale, const float* bias, const float* noise,
+                                          int noise_mode, float noise_strength, int act, float alpha, float gain, float clamp,
+                                          const float* residual, int route, void* workspace, size_t ws_bytes, void* stream) {
+    SHG_CHECK_ARG(route >= 0 && route <= 3, "conv2d_wino4: route must be 0..3");
     SHG_CHECK_ARG(x && wu && y, "conv2d_wino4: null pointer");
     SHG_CHECK_ARG(shg_conv2d_wino4_supported(NB, I, O, H, W), "conv2d_wino4: unsupported geometry (use shg_conv2d_wino_f32)");
     SHG_CHECK_ARG(OP % 64 == 0 && OP >= O, "conv2d_wino4: OP must be a multiple of 64 and >= O");
     SHG_CHECK_ARG((long)NB * I * H * W < 2147483647L && (long)NB * O * H * W < 2147483647L, "conv2d_wino4: tensor too large");
     SHG_CHECK_ARG(((shg_addr(x) | shg_addr(y) | shg_addr(noise) | shg_addr(residual)) & 15) == 0, "conv2d_wino4: x / y / noise / residual must be 16-byte aligned");
     WinoParams p = shg_wino_params(x, wu, y, NB, I, O, OP, H, W, in_scale, out_scale, bias, noise, noise_mode, noise_strength, act, alpha, gain, clamp, residual);
-    const int shape = wino4_plan(p, NB, I, OP, H, W);
+    const int shape = wino4_plan(p, NB, I, OP, H, W, route);
     // K split: the tail operands are 16-byte aligned already (checked above), which leaves the workspace
     const int ks = shg_wino_split(p, workspace, ws_bytes, shg_addr(workspace));
     const dim3 grid(p.n_ttiles * p.n_otiles, ks);
-    if (shape == 2) hipLaunchKernelGGL((conv_wino4_kernel<1, 32>), grid, dim3(wino4::NT), 0, (hipStream_t)stream, p);
-    else if (shape == 1) hipLaunchKernelGGL((conv_wino4_kernel<2, 16>), grid, dim3(wino4::NT), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((conv_wino4_kernel<4, 8>), grid, dim3(wino4::NT), 0, (hipStream_t)stream, p);
+    if (shape == 2) wino4_launch<1, 32>(p, grid, false, (hipStream_t)stream);
+    else if (shape == 1) wino4_launch<2, 16>(p, grid, route ? route >= 2 : wino4::uring_default<2, 16>(), (hipStream_t)stream);
+    else wino4_launch<4, 8>(p, grid, route ? route >= 2 : wino4::uring_default<4, 8>(), (hipStream_t)stream);
     SHG_CHECK_LAUNCH();
     if (ks > 1) {
         shg_launch_wino_split_reduce((const float*)workspace, y, ks, NB, O, H, W, out_scale, bias, noise_mode ? noise : nullptr, noise ? noise_mode : 0,
@@ -500,6 +623,14 @@ extern "C" int shg_conv2d_wino4_ws_f32(const float* x, const float* wu, float* y
         SHG_CHECK_LAUNCH();
     }
     return SHG_OK;
+}
+
+extern "C" int shg_conv2d_wino4_ws_f32(const float* x, const float* wu, float* y, int NB, int I, int O, int OP, int H, int W,
+                                       const float* in_scale, const float* out_scale, const float* bias, const float* noise,
+                                       int noise_mode, float noise_strength, int act, float alpha, float gain, float clamp,
+                                       const float* residual, void* workspace, size_t ws_bytes, void* stream) {
+    return shg_conv2d_wino4_route_f32(x, wu, y, NB, I, O, OP, H, W, in_scale, out_scale, bias, noise, noise_mode, noise_strength, act, alpha, gain, clamp,
+                                      residual, 0, workspace, ws_bytes, stream);
 }
 
 extern "C" int shg_conv2d_wino4_f32(const float* x, const float* wu, float* y, int NB, int I, int O, int OP, int H, int W,

@@ -658,6 +658,10 @@ WINO = True
 WINO_MIN = 16
 WINO4 = True            # F(4x4,3x3) (conv_wino4.hip) where it is served and the image has at least WINO4_MIN rows; else F(2x2,3x3)
 WINO4_MIN = 32
+WINO4_U = None          # (A/B switch: weight operands of conv_wino4 -- None as shipped: wave-private LDS ring, W >= 256 on 8 x 64 px tiles from 64
+                        # channels on; 'reg' register ring, 'lds' LDS ring on the 16 x 32 and 8 x 64 px tiles, both with W >= 256 on 4 x 128 px
+                        # tiles; 'lds_8x64' the ring with every W >= 256 on 8 x 64 px tiles; same bits)
+_WINO4_ROUTES = {None: 0, 'reg': 1, 'lds': 2, 'lds_8x64': 3}
 WINO_SPLIT = True       # (A/B switch: Winograd launches whose grid does not fill the chip split along the input channels)
 UP_POLY = True          # stride-2 transposed 3x3 convolutions in the polyphase-Winograd form (conv_wino_poly.hip)
 DOWN_POLY = True        # FIR-filtered stride-2 3x3 convolutions likewise (fir_down_planar + conv2d_down_poly)
@@ -709,9 +713,10 @@ def conv2d(x, pw, mode=MODE_SAME, pad=0, in_scale=None, out_scale=None, bias=Non
             executed = 2.0 * nb * pw.o * i * 36.0 * ((h + 3) // 4) * ((w + 3) // 4)
             ws, ws_bytes = _wino_workspace(L, lib.shg_conv2d_wino4_workspace_bytes, nb, i, pw.o, pw.op, h, w)
             with _timed(L, 'conv_wino4', direct, executed):
-                check(lib.shg_conv2d_wino4_ws_f32(
+                check(lib.shg_conv2d_wino4_route_f32(
                     _ptr(x), _ptr(wu), _ptr(y), nb, i, pw.o, pw.op, h, w, _ptr(in_scale), _ptr(out_scale), _ptr(bias), _ptr(noise),
-                    nmode, float(noise_strength), a, al, g, cl, _ptr(residual), _ptr(ws), ws_bytes, L.stream()), 'conv2d_wino4')
+                    nmode, float(noise_strength), a, al, g, cl, _ptr(residual), _WINO4_ROUTES[WINO4_U], _ptr(ws), ws_bytes, L.stream()),
+                    'conv2d_wino4')
             return y
         wu = pw.wino()
         ws, ws_bytes = _wino_workspace(L, lib.shg_conv2d_wino_workspace_bytes, nb, i, pw.o, pw.op, h, w)
