@@ -526,6 +526,32 @@ int shg_randcrop_bicubic_ragged_f32(const void* src, long src_bytes, const int* 
 int shg_randcrop_bicubic_planar_f32(const void* src, long src_bytes, const int* desc, const int* desc_dev, const float* lut, float* dst, int B,
                                     int s, void* stream);
 
+/* ---- the ADA augmentation pipe for the critic's input (sh-gan_amd/ada.py drives it; csrc/ada.hip): StyleGAN2-ADA's AugmentPipe, blit +
+ * geometry + colour categories.  shg_ada_params_f32: draws u [N,24] (uniform in [0,1)) and g [N,8] (standard normal), column layout in
+ * ada.py, and the probability p (ONE float in device memory, read on the device) -> G_inv [N,3,3], the colour matrix [N,3,4] (rows 0..2 of
+ * ADA's 4x4) and margins int32 [4] = {mx0, my0, mx1, my1}, the batch-wide reflect-pad extents.  One workgroup, float64 arithmetic, no host
+ * synchronisation.  cfg is HOST memory (copied into the kernel arguments).
+ * shg_ada_apply_f32: y = pipe(x), x and y [N,C,H,W], x != y.  geom = 1: reflect-pad by the margins -> x2 upsampling with the 12-tap sym6
+ * low-pass -> bilinear resampling by G_inv (zeros outside) -> x2 decimation, fused into one launch; geom = 0: G_inv and margins are not read.
+ * color_count = 3: channels [color_first, color_first + 3) become M x + t (bias = 0: M x only, the operator's linear part);
+ * color_count = 1: channel color_first becomes x * mean_r(sum_c M[r][c]) + mean_r(t[r]); 0: no colour stage, Cm is not read.  Every other
+ * channel passes the geometry alone.  geom = 0 and color_count = 0 together: SHG_ERR_ARG (the caller passes the tensor through).
+ * shg_ada_apply_adjoint_f32: gx = A^T gy, A the linear part of the same call.  With geom = 1 gx must be ZERO on entry (float atomics
+ * accumulate into it, staged through LDS); their order is not fixed, so gx is not bit-reproducible from run to run.  N * C <= 65535. */
+typedef struct {
+    float xflip, rotate90, xint, scale, rotate, aniso, xfrac;          /* probability multipliers, geometry */
+    float brightness, contrast, lumaflip, hue, saturation;             /* probability multipliers, colour */
+    float xint_max, scale_std, rotate_max, aniso_std, xfrac_std;
+    float brightness_std, contrast_std, hue_max, saturation_std;
+    int color_count;                                                   /* 1 or 3 (hue and saturation exist for 3 only) */
+} shg_ada_config;
+int shg_ada_params_f32(const float* u, const float* g, const float* p, const shg_ada_config* cfg, float* G_inv, float* Cm, int* margins,
+                       int N, int H, int W, void* stream);
+int shg_ada_apply_f32(const float* x, const float* G_inv, const float* Cm, const int* margins, float* y, int N, int C, int H, int W, int geom,
+                      int color_first, int color_count, int bias, void* stream);
+int shg_ada_apply_adjoint_f32(const float* gy, const float* G_inv, const float* Cm, const int* margins, float* gx, int N, int C, int H, int W,
+                              int geom, int color_first, int color_count, void* stream);
+
 /* ---- next row N3 (training-side critic, forward only): minibatch_std_layer (stylegan.py:686-704).
  * x [N,C,H,W] -> y [N,C+F,H,W]; N % G == 0, C % F == 0; stat [N/G * F] is caller-owned scratch. */
 int shg_minibatch_std_f32(const float* x, float* y, float* stat, int N, int C, int H, int W, int G, int F, void* stream);

@@ -31,6 +31,12 @@ class StyleGroup(ctypes.Structure):          # shg_style_group
                 ('ld', c_i), ('I', c_i), ('O', c_i), ('OP', c_i), ('demod', c_i), ('pre_gain', c_f)]
 
 
+class AdaConfig(ctypes.Structure):           # shg_ada_config
+    _fields_ = [(n, c_f) for n in ('xflip', 'rotate90', 'xint', 'scale', 'rotate', 'aniso', 'xfrac', 'brightness', 'contrast', 'lumaflip', 'hue',
+                                   'saturation', 'xint_max', 'scale_std', 'rotate_max', 'aniso_std', 'xfrac_std', 'brightness_std',
+                                   'contrast_std', 'hue_max', 'saturation_std')] + [('color_count', c_i)]
+
+
 class IncConv(ctypes.Structure):             # shg_inc_conv_desc
     _fields_ = [('x', c_fp), ('w', c_fp), ('bias', c_fp), ('y', c_fp)] + [
         (n, c_i) for n in ('I', 'H', 'W', 'x_ctot', 'x_coff', 'O', 'kh', 'kw', 'sh', 'sw', 'ph', 'pw', 'OH', 'OW', 'y_ctot', 'y_coff', 'splitk')]
@@ -150,6 +156,9 @@ _SIGS = {
     'shg_resize_fit_pad_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
     'shg_randcrop_bicubic_ragged_f32': [c_fp, c_l, ctypes.POINTER(c_i), c_fp, c_fp, c_fp, c_i, c_i, c_fp],
     'shg_randcrop_bicubic_planar_f32': [c_fp, c_l, ctypes.POINTER(c_i), c_fp, c_fp, c_fp, c_i, c_i, c_fp],
+    'shg_ada_params_f32': [c_fp, c_fp, c_fp, ctypes.POINTER(AdaConfig), c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
+    'shg_ada_apply_f32': [c_fp] * 5 + [c_i] * 8 + [c_fp],
+    'shg_ada_apply_adjoint_f32': [c_fp] * 5 + [c_i] * 7 + [c_fp],
     'shg_minibatch_std_f32': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
     'shg_conv2d_f16': [c_fp, c_fp, c_fp, c_fp] + [c_i] * 12 + [c_fp],
     'shg_conv2d_f16_needs_clear': [c_i] * 5,

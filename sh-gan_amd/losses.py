@@ -8,12 +8,15 @@ What differs: gradients flow through this package's differentiable operators (``
 ``sync`` keeps the reference's meaning -- only the LAST backward pass of a phase call with ``sync=True`` may reduce gradients
 across ranks (``misc.ddp_sync``: Gmain ``sync and not do_Gpl``, Gpl ``sync``, Dgen never, Dreal ``sync``; ``:56-106``) -- and is
 delivered to ``grad_sync.BucketedAllReduce`` as ``self.grad_sync.arm()`` right before that backward (``grad_sync`` is set by the
-training stage per phase; None = single process); an ADA ``augment_pipe`` is not supported; the statistics reporting of the
-reference (``training_stats.report``) is replaced by ``self.stats``, a plain dict of the last values."""
+training stage per phase; None = single process); ``augment_pipe`` is an ``ada.AugmentPipe`` (the ADA pipe on the device: the critic's
+input passes it in ``run_D`` / ``run_D_pair``, ``stylegan_default_loss.py:47-48``; its draws come from ``self.draw_fn(n)``, the pipe's own
+``draw`` unless a test pins them) and nothing else -- any other object raises; Dmain records ``Loss/signs/real`` for ``ada.AdaController``;
+the statistics reporting of the reference (``training_stats.report``) is replaced by ``self.stats``, a plain dict of the last values."""
 import numpy as np
 import torch
 import torch.nn.functional as F
 
+from .ada import AugmentPipe
 from .model_zoo.stylegan_utils import conv2d_gradfix
 
 PHASES = ('Gmain', 'Greg', 'Gboth', 'Dmain', 'Dreg', 'Dboth')
@@ -35,8 +38,10 @@ class StyleGAN2Loss(Loss):
                  pl_decay=0.01, pl_weight=2, batch_critic=True):
         super().__init__()
         self.batch_critic = batch_critic            # Dmain: generated and real images through the critic as ONE batch (see accumulate_gradients)
-        if augment_pipe is not None:
-            raise NotImplementedError('ADA augmentation is not part of the HIP path')
+        if augment_pipe is not None and not isinstance(augment_pipe, AugmentPipe):
+            raise NotImplementedError('ADA augmentation is not part of the HIP path unless augment_pipe is an ada.AugmentPipe')
+        self.augment_pipe = augment_pipe
+        self.draw_fn = augment_pipe.draw if augment_pipe is not None else None      # n -> (u [n,24], g [n,8]); tests pin the draws here
         self.device = device
         self.G_mapping, self.G_synthesis, self.D = G_mapping, G_synthesis, D
         self.style_mixing_prob = style_mixing_prob
@@ -67,12 +72,18 @@ class StyleGAN2Loss(Loss):
         ws = self._style_mix(self.G_mapping(z, c), z, c)
         return self.G_synthesis(ws), ws
 
+    def _augment(self, img):
+        """The critic's input through the ADA pipe (one parameter launch + one fused launch for the whole batch)."""
+        if self.augment_pipe is None:
+            return img
+        return self.augment_pipe(img, self.draw_fn(img.shape[0]))
+
     def run_D(self, img, c, sync=True):
-        return self.D(img, c)
+        return self.D(self._augment(img), c)
 
     def run_D_pair(self, gen_img, gen_c, real_img, real_c):
         """-> (gen_logits, real_logits) from one critic pass over cat([gen, real]) with the minibatch statistic per half."""
-        logits = self.D(torch.cat([gen_img, real_img]), torch.cat([gen_c, real_c]), segments=2)
+        logits = self.D(self._augment(torch.cat([gen_img, real_img])), torch.cat([gen_c, real_c]), segments=2)
         return logits[:gen_img.shape[0]], logits[gen_img.shape[0]:]
 
     # -- one phase (stylegan_default_loss.py:53-128) -----------------------------------------------------------------------
@@ -118,7 +129,7 @@ class StyleGAN2Loss(Loss):
                 gen_logits, real_logits = self.run_D_pair(gen_img, gen_c, real_img.detach(), real_c)
                 loss_Dgen, loss_Dreal = F.softplus(gen_logits), F.softplus(-real_logits)
                 self.stats.update({'Loss/scores/fake': gen_logits.detach(), 'Loss/scores/real': real_logits.detach(),
-                                   'Loss/D/loss': (loss_Dgen + loss_Dreal).detach()})
+                                   'Loss/signs/real': real_logits.detach().sign(), 'Loss/D/loss': (loss_Dgen + loss_Dreal).detach()})
                 self._arm(sync)
                 (loss_Dgen.mean() + loss_Dreal.mean()).mul(gain).backward()
                 return
@@ -139,6 +150,7 @@ class StyleGAN2Loss(Loss):
                 loss_Dreal = 0
                 if do_Dmain:
                     loss_Dreal = F.softplus(-real_logits)
+                    self.stats['Loss/signs/real'] = real_logits.detach().sign()
                     self.stats['Loss/D/loss'] = (loss_Dgen + loss_Dreal).detach()
                 loss_Dr1 = 0
                 if do_Dr1:
@@ -202,10 +214,10 @@ class InpaintingLoss(StyleGAN2Loss):
     def run_D(self, img, c, sync=True):
         if img.shape[1] == 3:                                   # a generated image: prepend the mask channel it was conditioned on
             img = torch.cat([self._m05[:img.shape[0]], img], dim=1)
-        return self.D(img, c)
+        return self.D(self._augment(img), c)                   # (the mask channel moves with the image; colour leaves it alone)
 
     def run_D_pair(self, gen_img, gen_c, real_img, real_c):
         n = gen_img.shape[0]
         both = torch.cat([torch.cat([self._m05[:n], gen_img], dim=1), real_img])       # (one write pass: cat of the cat's pieces)
-        logits = self.D(both, torch.cat([gen_c, real_c]), segments=2)
+        logits = self.D(self._augment(both), torch.cat([gen_c, real_c]), segments=2)
         return logits[:n], logits[n:]

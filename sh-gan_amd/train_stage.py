@@ -276,10 +276,11 @@ def update_ema(G_ema, G, batch_size, cur_nimg, ema_kimg=10.0, ema_rampup=None):
 
 
 def train(G, D, G_ema, loss, batches, phases, z_dim, batch_size, batch_gpu, total_kimg, effective_batch_gpu=None, ema_kimg=10.0,
-          ema_rampup=None, kimg_per_tick=4, on_tick=None, device=None, ema=None):
+          ema_rampup=None, kimg_per_tick=4, on_tick=None, device=None, ema=None, ada=None):
     """The iteration loop of stylegan_default.py:370-396: ``batches`` yields real images [batch_gpu, C, H, W] for this rank,
     ``batch_size`` is the GLOBAL batch (= batch_gpu * world).  ``ema``: an ``optim.EmaUpdater(G_ema, G)`` (one launch per iteration)
-    in place of ``update_ema``.  Returns (cur_nimg, batch_idx)."""
+    in place of ``update_ema``.  ``ada``: an ``ada.AdaController`` over the loss's augment pipe, fed the signs of the real logits after the
+    EMA update (stylegan_default.py:397-400).  Returns (cur_nimg, batch_idx)."""
     cur_nimg, batch_idx, cur_tick, tick_start = 0, 0, 0, 0
     for real_img in batches:
         run_phases(real_img, z_dim, phases, batch_idx, loss, batch_gpu, effective_batch_gpu, device)
@@ -287,6 +288,8 @@ def train(G, D, G_ema, loss, batches, phases, z_dim, batch_size, batch_gpu, tota
             ema.update(batch_size, cur_nimg, ema_kimg, ema_rampup)
         else:
             update_ema(G_ema, G, batch_size, cur_nimg, ema_kimg, ema_rampup)
+        if ada is not None and 'Loss/signs/real' in getattr(loss, 'stats', {}):
+            ada.update(loss.stats['Loss/signs/real'], batch_size)
         cur_nimg += batch_size
         batch_idx += 1
         done = cur_nimg >= total_kimg * 1000
