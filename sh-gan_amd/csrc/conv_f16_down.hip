@@ -25,34 +25,21 @@ constexpr int PR = 2 * TH + 1, PC = 2 * TW + 1;   // window: 17 rows x 65 column
 constexpr int ROWS = PC + 1;                      // slots of a window row: 33 even columns, 33 slots for the 32 odd ones (66)
 constexpr int PSTAGE = 40 * 1024, WSTAGE = 36 * 1024;
 constexpr int L_W = 0, L_P = 2 * WSTAGE, L_PRM = L_P + 2 * PSTAGE, LDS_BYTES = L_PRM + 2 * 2048;
-constexpr unsigned OOB = 0x80000000u;
 
-struct DownP {
-    ConvP c;
+struct DownP {                                    // (the TileWalk fields with pad among them: this kernel's argument layout as it has always been --
+    ConvP c;                                      // moving pad in front of a nested TileWalk renumbers the kernel's scalar registers)
     int tiles_x, tiles_y, n_ot, ntiles, pad;
     unsigned m_ot, m_tx, m_ty;
 };
 
-struct Coord { int n, ty, tx, ot; };
-
 __global__ __launch_bounds__(512) void conv_f16_down_kernel(const DownP P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const ConvP& p = P.c;
+    const TileWalk walk{P.tiles_x, P.tiles_y, P.n_ot, P.ntiles, P.m_ot, P.m_tx, P.m_ty};
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, kg = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
     const int nsteps = p.I >> 4, c16n = p.I >> 4;
-
-    auto decode = [&](int tile) __attribute__((always_inline)) -> Coord {
-        Coord c;
-        unsigned r, t = shg_fastdiv((unsigned)tile, (unsigned)P.n_ot, P.m_ot, r);
-        c.ot = (int)r;
-        t = shg_fastdiv(t, (unsigned)P.tiles_x, P.m_tx, r);
-        c.tx = (int)r;
-        c.n = (int)shg_fastdiv(t, (unsigned)P.tiles_y, P.m_ty, r);
-        c.ty = (int)r;
-        return c;
-    };
 
     // ---- window requests: wave w owns pieces 5 w .. 5 w + 4 of the 40; lane l of a piece = slot 32 piece + l / 2, 16-byte half (l & 1) ^ bit 3
     // of the slot index; slot = row * 66 + (column & 1) * 33 + (column >> 1): input pixel (16 ty - pad + row, 64 tx - pad + column)
@@ -105,7 +92,7 @@ __global__ __launch_bounds__(512) void conv_f16_down_kernel(const DownP P) {
 
     const bool prm_any = p.bias || p.out_scale;
     int tile = blockIdx.x;
-    Coord cur = decode(tile);
+    Coord cur = tile_decode(tile, walk);
     tile_addresses(cur);
     int step = 0, s = 0, tpar = 0;
     {
@@ -120,10 +107,10 @@ __global__ __launch_bounds__(512) void conv_f16_down_kernel(const DownP P) {
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
         int nstep = step + 1, ntile = tile;
         if (nstep == nsteps) { nstep = 0; ntile = tile + gridDim.x; }
-        const bool has_next = ntile < P.ntiles;
+        const bool has_next = ntile < walk.ntiles;
         Coord nc = cur;
         if (!has_next) { nstep = step; ntile = tile; }
-        else if (nstep == 0) { nc = decode(ntile); tile_addresses(nc); }
+        else if (nstep == 0) { nc = tile_decode(ntile, walk); tile_addresses(nc); }
         const unsigned step_off = (unsigned)(nstep * 32), tile_off = (unsigned)((nc.ot * 4 * 9 * c16n + nstep) * 1024);
         const int stage = s & 1, nstage = stage ^ 1;
         const unsigned char* wa = lds + L_W + stage * WSTAGE + lane * 16;
@@ -171,11 +158,7 @@ __global__ __launch_bounds__(512) void conv_f16_down_kernel(const DownP P) {
                             }
                         }
                     }
-                    const u32x2 a2 = __builtin_bit_cast(u32x2, v[0]), b2 = __builtin_bit_cast(u32x2, v[1]);
-                    auto r0 = __builtin_amdgcn_permlane32_swap(a2[0], b2[0], false, false);
-                    auto r1 = __builtin_amdgcn_permlane32_swap(a2[1], b2[1], false, false);
-                    u32x4 o4;
-                    o4[0] = r0[0]; o4[1] = r1[0]; o4[2] = r0[1]; o4[3] = r1[1];
+                    const u32x4 o4 = lane_exchange(__builtin_bit_cast(u32x2, v[0]), __builtin_bit_cast(u32x2, v[1]));
                     const int o = cur.ot * 128 + m * 32 + (2 * gp + kg) * 8;
                     const unsigned voff = (ok && o < p.O) ? pix + (unsigned)(o * 2) : OOB;
                     asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" ::"v"(o4), "v"(voff), "s"(srd_y));
@@ -204,34 +187,12 @@ bool conv_down_eligible(const ConvP& p) {
     // 256 -> 512 at 129^2 136 -> 153 us and 512 -> 512 at 65^2 68 -> 72 us (the gather kernel keeps those)
     if (p.I > 128) return false;
     if ((reinterpret_cast<uintptr_t>(p.bias) | reinterpret_cast<uintptr_t>(p.out_scale)) & 15) return false;
-    return (long)p.H * p.W * p.I * 2 < (1L << 31) && (long)p.OHt * p.OWt * p.O * 2 < (1L << 31);
+    return offsets_fit_32bit(p);
 }
 
 int conv_down_launch(const ConvP& p0, int pad, hipStream_t st) {
-    down::DownP P{};
-    P.c = p0;
-    P.pad = pad;
-    P.tiles_y = shg_cdiv(p0.OHt, down::TH);
-    P.tiles_x = shg_cdiv(p0.OWt, down::TW);
-    P.n_ot = (p0.O + 127) / 128;
-    const long ntiles = (long)p0.N * P.tiles_y * P.tiles_x * P.n_ot;
-    if (ntiles > 0x7fffffffL) { shg_set_error("conv2d_f16 (stride 2): too many tiles"); return SHG_ERR_ARG; }
-    P.ntiles = (int)ntiles;
-    P.m_ot = 0xFFFFFFFFu / (unsigned)P.n_ot; P.m_tx = 0xFFFFFFFFu / (unsigned)P.tiles_x; P.m_ty = 0xFFFFFFFFu / (unsigned)P.tiles_y;
-    const int cus = shg_cu_count();
-    static ShgDeviceOnce attr_once;
-    const int dev_now = shg_current_device();
-    if (attr_once.pending(dev_now)) {
-        if (hipFuncSetAttribute((const void*)down::conv_f16_down_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, down::LDS_BYTES) != hipSuccess) {
-            shg_set_error("conv2d_f16 (stride 2): cannot reserve %d bytes of LDS", down::LDS_BYTES);
-            return SHG_ERR_LAUNCH;
-        }
-        attr_once.mark(dev_now);
-    }
-    const unsigned grid = (unsigned)(ntiles < cus ? ntiles : cus);
-    hipLaunchKernelGGL(down::conv_f16_down_kernel, dim3(grid), dim3(512), down::LDS_BYTES, st, P);
-    SHG_CHECK_LAUNCH();
-    return SHG_OK;
+    return persistent_launch<down::conv_f16_down_kernel>(p0.N, shg_cdiv(p0.OHt, down::TH), shg_cdiv(p0.OWt, down::TW), (p0.O + 127) / 128, down::LDS_BYTES, "stride 2",
+                                                         [&](const TileWalk& w) { return std::make_tuple(down::DownP{p0, w.tiles_x, w.tiles_y, w.n_ot, w.ntiles, pad, w.m_ot, w.m_tx, w.m_ty}); }, st);
 }
 
 }  // namespace f16

@@ -40,33 +40,16 @@ constexpr int L_W = 0, L_P = 2 * WSTAGE, L_PRM = L_P + 2 * PSTAGE;
 constexpr int PRM = 4096, PRM_SCALE = 1024, PRM_NOISE = 2048;      // a tile's parameter slot: bias | out_scale | noise rows -- 1 KiB apart: a DMA request
                                                                    // writes all 64 lanes' 16 bytes (zeros for the lanes out of range)
 constexpr int LDS_BYTES = L_PRM + 2 * PRM;      // 163 840: all of the CU's LDS
-constexpr unsigned OOB = 0x80000000u;           // a byte offset no descriptor range admits: the DMA writes zeros for that lane
 
-struct Coord { int n, ty, tx, ot; };
-
-struct RingDiv { unsigned n_ot, tiles_x, tiles_y, m_ot, m_tx, m_ty; };    // divisors of the tile decode and floor(2^32 / divisor)
-
-template <int NT>
-__global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const int ntiles, const RingDiv dv) {
+__global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const TileWalk walk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, kg = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
-    const int n_ot = (int)dv.n_ot;
-    const int PW = NT == 9 ? TW + 2 : p.PW;                      // (the 3x3 patch is 18 x 34: a constant divisor for the piece -> (row, column) map)
+    const int n_ot = walk.n_ot;
+    constexpr int PW = TW + 2;                                  // (the 3x3 patch is 18 x 34: a constant divisor for the piece -> (row, column) map)
     const int nchunks = p.I >> 5, c16n = p.I >> 4, npix = p.PH * PW;
     const bool resident = n_ot == 1 && nchunks <= 2;            // weight stage of step s = chunk's own slab: loaded by the first two steps only
-
-    auto decode = [&](int tile) __attribute__((always_inline)) -> Coord {
-        Coord c;
-        unsigned r, t = shg_fastdiv((unsigned)tile, dv.n_ot, dv.m_ot, r);
-        c.ot = (int)r;
-        t = shg_fastdiv(t, dv.tiles_x, dv.m_tx, r);
-        c.tx = (int)r;
-        c.n = (int)shg_fastdiv(t, dv.tiles_y, dv.m_ty, r);
-        c.ty = (int)r;
-        return c;
-    };
 
     // ---- what this lane moves in a patch DMA piece: wave w owns pieces 5w .. 5w+4 of the 40 (plane = w / 4, pixel group = 5 (w & 3) + i);
     // lane l of a piece = patch pixel 32 grp + l / 2, 16-byte half (l & 1) ^ bit 3 of the pixel index
@@ -93,10 +76,10 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
     unsigned wsoff[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
-        const int pi = i * 8 + wave, t = (pi >> 2) < NT ? (pi >> 2) : 0, ks = (pi >> 1) & 1, m = pi & 1;
+        const int pi = i * 8 + wave, t = (pi >> 2) < 9 ? (pi >> 2) : 0, ks = (pi >> 1) & 1, m = pi & 1;
         wsoff[i] = (unsigned)(((m * p.wslots + p.tw[t]) * c16n + ks) * 1024);
     }
-    const bool w4_ok = 32 + wave < NT * 4;
+    const bool w4_ok = 32 + wave < 36;
     auto dma_patch = [&](int i, int stage, unsigned chunk_off) __attribute__((always_inline)) {
         shg_dma16(lds0 + L_P + stage * PSTAGE + (ks_dma * 20 + (wave & 3) * 5 + i) * 1024, pvoff[i], srd_x, chunk_off);
     };
@@ -121,17 +104,16 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
     };
 
     // ---- B-operand addresses inside a patch stage (plane 0): lane (j, kg), tap t, pixel block q -> pixel p, half kg ^ bit 3 of p
-    // (NT = 9 is conv2d_f16_impl's 3x3 table: tap t reads patch row t / 3, column t % 3 -- q + row has four values, 12 addresses instead of 18)
-    constexpr int BR = NT == 9 ? 4 : NT * 2, BC = NT == 9 ? 3 : 1;
-    unsigned baddr_[BR][BC];
+    // (conv2d_f16_impl's 3x3 table: tap t reads patch row t / 3, column t % 3 -- q + row has four values, 12 addresses instead of 18)
+    unsigned baddr_[4][3];
 #pragma unroll
-    for (int r = 0; r < BR; ++r)
+    for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int c = 0; c < BC; ++c) {
-            const int pp = NT == 9 ? (wave * 2 + r) * PW + j + c : (wave * 2 + (r & 1) + p.tdy[r >> 1]) * PW + j + p.tdx[r >> 1];
+        for (int c = 0; c < 3; ++c) {
+            const int pp = (wave * 2 + r) * PW + j + c;
             baddr_[r][c] = (unsigned)(pp * 32 + ((kg ^ ((pp >> 3) & 1)) << 4));
         }
-    auto baddr = [&](int t, int q) __attribute__((always_inline)) -> unsigned { return NT == 9 ? baddr_[q + t / 3][t % 3] : baddr_[t * 2 + q][0]; };
+    auto baddr = [&](int t, int q) __attribute__((always_inline)) -> unsigned { return baddr_[q + t / 3][t % 3]; };
 
     f16x acc[2][2];
 #pragma unroll
@@ -161,13 +143,8 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
     };
     auto store_piece = [&](int k) __attribute__((always_inline)) {          // k = (q, m, gp)
         const int q = k >> 2, m = (k >> 1) & 1, gp = k & 1;
-        // lanes 0-31 hold channels 8g .. 8g+3 of group g, lanes 32-63 channels 8g+4 .. 8g+7: after the half exchange the lower lanes own the
-        // 16 bytes of group 2 gp, the upper lanes those of group 2 gp + 1
         u32x2 a = pk[m][q][2 * gp], b = pk[m][q][2 * gp + 1];
-        auto r0 = __builtin_amdgcn_permlane32_swap(a[0], b[0], false, false);
-        auto r1 = __builtin_amdgcn_permlane32_swap(a[1], b[1], false, false);
-        u32x4 v;
-        v[0] = r0[0]; v[1] = r1[0]; v[2] = r0[1]; v[3] = r1[1];
+        const u32x4 v = lane_exchange(a, b);
         const int o = p_ot * 64 + m * 32 + (2 * gp + kg) * 8;
         const unsigned voff = o < p.O ? pyoff[q] + (unsigned)(o * 2) : OOB;
         asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" ::"v"(v), "v"(voff), "s"(srd_y));     // (the wait state hipcc pads behind a > 8-byte store whose data registers are rewritten next: not modelled inside asm)
@@ -185,9 +162,9 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
         b[0][1] = *(const h8*)(pa + baddr(0, 1)); a[0][1] = *(const h8*)(wa + 1024);
         __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
-        for (int it = 0; it < NT * 2; ++it) {
+        for (int it = 0; it < 18; ++it) {
             const int cb = it & 1, nb = cb ^ 1;
-            if (it + 1 < NT * 2) {
+            if (it + 1 < 18) {
                 const int t = (it + 1) >> 1, ks = (it + 1) & 1;
                 a[nb][0] = *(const h8*)(wa + ((it + 1) * 2 + 0) * 1024); b[nb][0] = *(const h8*)(pa + ks * PLANE + baddr(t, 0));
                 b[nb][1] = *(const h8*)(pa + ks * PLANE + baddr(t, 1)); a[nb][1] = *(const h8*)(wa + ((it + 1) * 2 + 1) * 1024);
@@ -196,7 +173,7 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
             acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[cb][0], b[cb][1], acc[0][1], 0, 0, 0);
             acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[cb][1], b[cb][0], acc[1][0], 0, 0, 0);
             acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[cb][1], b[cb][1], acc[1][1], 0, 0, 0);
-            if (it + 1 < NT * 2) {
+            if (it + 1 < 18) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -206,23 +183,15 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
                 __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            // slots (NT = 9: 18 iterations): patch pieces behind iterations 0 4 8 12 16, weight pieces behind 2 6 10 14 17, stores behind 1 3 .. 15
-            constexpr int LAST = NT * 2 - 1;
-            if (it % 4 == 0 && it / 4 < 5 && it / 4 * 4 <= LAST) dma_patch(it / 4, nstage, chunk_off);
-            if (NT * 2 < 17 && it == LAST)
-                for (int i = LAST / 4 + 1; i < 5; ++i) dma_patch(i, nstage, chunk_off);
+            // slots: patch pieces behind iterations 0 4 8 12 16, weight pieces behind 2 6 10 14 17, stores behind 1 3 .. 15
+            if (it % 4 == 0) dma_patch(it / 4, nstage, chunk_off);
             if constexpr (WITH_W) {
-                if (it % 4 == 2 && it / 4 < 4) dma_weight(it / 4, nstage, tile_off);
-                if (it == LAST) {
-                    for (int i = (LAST >= 2 ? (LAST - 2) / 4 + 1 : 0); i < 4; ++i) dma_weight(i, nstage, tile_off);
-                    dma_weight(4, nstage, tile_off);
-                }
+                if (it % 4 == 2) dma_weight(it / 4, nstage, tile_off);
+                if (it == 17) dma_weight(4, nstage, tile_off);
             }
-            if (it == LAST && prm_next) dma_params(b_c, b_tpar);
+            if (it == 17 && prm_next) dma_params(b_c, b_tpar);
             if constexpr (PEND) {
-                if ((it & 1) && it / 2 < 8) store_piece(it / 2);
-                if (NT * 2 < 16 && it == LAST)
-                    for (int k = (LAST + 1) / 2; k < 8; ++k) store_piece(k);
+                if ((it & 1) && it < 16) store_piece(it / 2);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -231,7 +200,7 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
     using F_ = std::false_type;
 
     int tile = blockIdx.x;
-    Coord cur = decode(tile);
+    Coord cur = tile_decode(tile, walk);
     tile_addresses(cur);
     int chunk = 0, s = 0, tpar = 0;
     const bool prm_any = p.bias || p.tail, prm_per_tile = prm_any && (!resident || p.tail);
@@ -251,10 +220,10 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
         int nchunk = chunk + 1, ntile = tile;
         if (nchunk == nchunks) { nchunk = 0; ntile = tile + gridDim.x; }
-        const bool has_next = ntile < ntiles;
+        const bool has_next = ntile < walk.ntiles;
         Coord nc = cur;
         if (!has_next) { nchunk = chunk; ntile = tile; }             // (the last step requests itself once more: no special case in the body)
-        else if (nchunk == 0) { nc = decode(ntile); tile_addresses(nc); }
+        else if (nchunk == 0) { nc = tile_decode(ntile, walk); tile_addresses(nc); }
         const unsigned chunk_off = (unsigned)(nchunk * 64), tile_off = (unsigned)((nc.ot * 2 * p.wslots * c16n + nchunk * 2) * 1024);
         const bool with_w = !(resident && s + 1 >= 2);
         const bool prm_next = prm_per_tile && nchunk == 0 && has_next;
@@ -331,9 +300,11 @@ __global__ __launch_bounds__(512) void conv_f16_ring_kernel(const ConvP p, const
 
 }  // namespace ring
 
-// The ring kernel serves: patches read with stride 1 (stride-1 convolutions; span = extent of the tap offsets) of at most 18 x 34 pixels,
-// 9 taps (for now), whole 8-channel output pieces; of the fused tail everything but the input scale and the residual (those stay on
-// conv_f16_kernel), noise with whole 16-byte pieces per row.
+// The ring kernel serves: patches read with stride 1 (stride-1 convolutions; span = extent of the tap offsets) of 18 x 34 pixels under nine
+// taps in conv2d_f16_impl's 3x3 order -- the kernel's operand addresses and its request / store slots are written out for that table; the
+// 1 / 2 / 4-tap launches of the same form are the phases of the transposed convolution, which conv_f16_upring.hip serves --, whole
+// 8-channel output pieces; of the fused tail everything but the input scale and the residual (those stay on conv_f16_kernel), noise with
+// whole 16-byte pieces per row.
 static int g_f16_routes = 7;         // bit 0: stride-1 3x3 launches on the ring kernel, bit 1: transposed launches on the merged-phase kernel, bit 2: stride-2 3x3 launches on conv_f16_down.hip
 int conv_f16_routes() { return g_f16_routes; }
 
@@ -343,33 +314,17 @@ bool conv_ring_eligible(const ConvP& p, int span_y, int span_x) {
     if (p.tail && (p.s_out != 1 || p.oy0 || p.ox0)) return false;
     if (p.noise_mode && ((p.OWt & 3) || (reinterpret_cast<uintptr_t>(p.noise) & 15))) return false;
     if ((reinterpret_cast<uintptr_t>(p.bias) | reinterpret_cast<uintptr_t>(p.out_scale)) & 15) return false;
-    return span_y == 3 && span_x == 3;                             // (the kernel's 18 x 34 patch)
+    return span_y == 3 && span_x == 3 && offsets_fit_32bit(p);     // (the kernel's 18 x 34 patch)
 }
 
-int conv_ring_launch(const ConvP& p0, int span_y, int span_x, hipStream_t st) {
+int conv_ring_launch(const ConvP& p0, hipStream_t st) {
     ConvP p = p0;
-    p.PH = ring::TH - 1 + span_y;
-    p.PW = ring::TW - 1 + span_x;
+    p.PH = ring::TH + 2;
+    p.PW = ring::TW + 2;
     p.tiles_y = shg_cdiv(p.GH, ring::TH);
     p.tiles_x = shg_cdiv(p.GW, ring::TW);
-    const int n_ot = (p.O + 63) / 64;
-    const long ntiles = (long)p.N * p.tiles_y * p.tiles_x * n_ot;
-    const int cus = shg_cu_count();
-    static ShgDeviceOnce attr_once;
-    const int dev_now = shg_current_device();
-    if (attr_once.pending(dev_now)) {
-        if (hipFuncSetAttribute((const void*)ring::conv_f16_ring_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize, ring::LDS_BYTES) != hipSuccess) {
-            shg_set_error("conv2d_f16 (ring): cannot reserve %d bytes of LDS", ring::LDS_BYTES);
-            return SHG_ERR_LAUNCH;
-        }
-        attr_once.mark(dev_now);
-    }
-    const unsigned grid = (unsigned)(ntiles < cus ? ntiles : cus);
-    const ring::RingDiv dv{(unsigned)n_ot, (unsigned)p.tiles_x, (unsigned)p.tiles_y, 0xFFFFFFFFu / (unsigned)n_ot, 0xFFFFFFFFu / (unsigned)p.tiles_x,
-                           0xFFFFFFFFu / (unsigned)p.tiles_y};
-    hipLaunchKernelGGL((ring::conv_f16_ring_kernel<9>), dim3(grid), dim3(512), ring::LDS_BYTES, st, p, (int)ntiles, dv);
-    SHG_CHECK_LAUNCH();
-    return SHG_OK;
+    return persistent_launch<ring::conv_f16_ring_kernel>(p.N, p.tiles_y, p.tiles_x, (p.O + 63) / 64, ring::LDS_BYTES, "ring",
+                                                         [&](const TileWalk& w) { return std::make_tuple(p, w); }, st);
 }
 
 }  // namespace f16

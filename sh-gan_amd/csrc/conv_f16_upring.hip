@@ -24,15 +24,12 @@ namespace upring {
 constexpr int TH = 16, TW = 32, PW = TW + 1;       // grid pixels of a tile; patch = (TH + 1) x (TW + 1) input pixels
 constexpr int PPX = 640, PLANE = PPX * 32, PSTAGE = 2 * PLANE, WSTAGE = 18 * 1024;
 constexpr int L_W = 0, L_P = 2 * WSTAGE, L_S = L_P + 2 * PSTAGE, LDS_BYTES = L_S + 2 * 2048;
-constexpr unsigned OOB = 0x80000000u;
 
 struct UpP {
     ConvP c;                    // x, w, y, N, I, O, H, W, OHt, OWt, in_scale
-    int crop, tiles_x, tiles_y, n_ot, ntiles;
-    unsigned m_ot, m_tx, m_ty;  // floor((2^32 - 1) / divisor) of the tile decode
+    int crop;
+    TileWalk w;
 };
-
-struct Coord { int n, ty, tx, ot; };
 
 __global__ __launch_bounds__(512) void conv_f16_upring_kernel(const UpP P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -42,17 +39,6 @@ __global__ __launch_bounds__(512) void conv_f16_upring_kernel(const UpP P) {
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
     const int nchunks = p.I >> 5, c16n = p.I >> 4;
     const bool scaled = p.in_scale != nullptr;
-
-    auto decode = [&](int tile) __attribute__((always_inline)) -> Coord {
-        Coord c;
-        unsigned r, t = shg_fastdiv((unsigned)tile, (unsigned)P.n_ot, P.m_ot, r);
-        c.ot = (int)r;
-        t = shg_fastdiv(t, (unsigned)P.tiles_x, P.m_tx, r);
-        c.tx = (int)r;
-        c.n = (int)shg_fastdiv(t, (unsigned)P.tiles_y, P.m_ty, r);
-        c.ty = (int)r;
-        return c;
-    };
 
     // ---- patch requests: wave w owns pieces 5 (w & 3) .. + 4 of plane w >> 2; lane l of a piece = patch pixel 32 piece + l / 2, 16-byte half
     // (l & 1) ^ bit 3 of the pixel index (the swizzle of conv_f16_ring.hip); patch pixel (r, c) = input pixel (16 ty - 1 + r, 32 tx - 1 + c)
@@ -108,7 +94,7 @@ __global__ __launch_bounds__(512) void conv_f16_upring_kernel(const UpP P) {
             for (int r = 0; r < 16; ++r) acc[ph][q][r] = 0.f;
 
     int tile = blockIdx.x;
-    Coord cur = decode(tile);
+    Coord cur = tile_decode(tile, P.w);
     tile_addresses(cur);
     int chunk = 0, s = 0, tpar = 0;
     {
@@ -123,10 +109,10 @@ __global__ __launch_bounds__(512) void conv_f16_upring_kernel(const UpP P) {
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");      // step s landed (stores of the previous tile too); stage (s + 1) & 1 is free
         int nchunk = chunk + 1, ntile = tile;
         if (nchunk == nchunks) { nchunk = 0; ntile = tile + gridDim.x; }
-        const bool has_next = ntile < P.ntiles;
+        const bool has_next = ntile < P.w.ntiles;
         Coord nc = cur;
         if (!has_next) { nchunk = chunk; ntile = tile; }                   // (the last step requests itself once more)
-        else if (nchunk == 0) { nc = decode(ntile); tile_addresses(nc); }
+        else if (nchunk == 0) { nc = tile_decode(ntile, P.w); tile_addresses(nc); }
         const unsigned chunk_off = (unsigned)(nchunk * 64), tile_off = (unsigned)((nc.ot * 9 * c16n + nchunk * 2) * 1024);
         const int stage = s & 1, nstage = stage ^ 1;
         const unsigned char* wa = lds + L_W + stage * WSTAGE + lane * 16;
@@ -177,9 +163,7 @@ __global__ __launch_bounds__(512) void conv_f16_upring_kernel(const UpP P) {
         }
         if (scaled && nchunk == 0 && has_next) dma_scale(nc, tpar ^ 1);
         if (chunk == nchunks - 1) {
-            // C/D layout: column (pixel) = lane & 31, row (channel) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); lanes 0-31 hold channels 8g .. 8g+3 of
-            // group g, lanes 32-63 channels 8g+4 .. 8g+7: after the half exchange the lower lanes own the 16 bytes of group 2 gp, the upper
-            // lanes those of group 2 gp + 1
+            // C/D layout: column (pixel) = lane & 31, row (channel) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
             const i32x4 srd_y = shg_make_srd(p.y + (long)cur.n * p.OHt * p.OWt * p.O, (unsigned)(p.OHt * p.OWt * p.O * 2));
 #pragma unroll
             for (int ph = 0; ph < 4; ++ph)
@@ -195,11 +179,7 @@ __global__ __launch_bounds__(512) void conv_f16_upring_kernel(const UpP P) {
                         h4 v0, v1;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { v0[e] = (_Float16)acc[ph][q][(2 * gp) * 4 + e]; v1[e] = (_Float16)acc[ph][q][(2 * gp + 1) * 4 + e]; }
-                        const u32x2 a = __builtin_bit_cast(u32x2, v0), b2 = __builtin_bit_cast(u32x2, v1);
-                        auto r0 = __builtin_amdgcn_permlane32_swap(a[0], b2[0], false, false);
-                        auto r1 = __builtin_amdgcn_permlane32_swap(a[1], b2[1], false, false);
-                        u32x4 v;
-                        v[0] = r0[0]; v[1] = r1[0]; v[2] = r0[1]; v[3] = r1[1];
+                        const u32x4 v = lane_exchange(__builtin_bit_cast(u32x2, v0), __builtin_bit_cast(u32x2, v1));
                         const int o = cur.ot * 32 + (2 * gp + kg) * 8;
                         const unsigned voff = (ok && o < p.O) ? pix + (unsigned)(o * 2) : OOB;
                         asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" ::"v"(v), "v"(voff), "s"(srd_y));     // (the wait state hipcc pads behind a > 8-byte store whose data registers are rewritten next: not modelled inside asm)
@@ -223,34 +203,12 @@ __global__ __launch_bounds__(512) void conv_f16_upring_kernel(const UpP P) {
 bool convt_upring_eligible(const ConvP& p) {
     if (!(conv_f16_routes() & 2)) return false;
     return (p.I & 31) == 0 && (p.O & 7) == 0 && !p.bias && !p.tail && p.I <= 512 && ((reinterpret_cast<uintptr_t>(p.in_scale)) & 15) == 0 &&
-           (long)p.H * p.W * p.I * 2 < (1L << 31) && (long)p.OHt * p.OWt * p.O * 2 < (1L << 31);
+           offsets_fit_32bit(p);
 }
 
 int convt_upring_launch(const ConvP& p0, int crop, hipStream_t st) {
-    upring::UpP P{};
-    P.c = p0;
-    P.crop = crop;
-    P.tiles_y = shg_cdiv(p0.H + 1, upring::TH);
-    P.tiles_x = shg_cdiv(p0.W + 1, upring::TW);
-    P.n_ot = (p0.O + 31) / 32;
-    const long ntiles = (long)p0.N * P.tiles_y * P.tiles_x * P.n_ot;
-    if (ntiles > 0x7fffffffL) { shg_set_error("conv2d_f16 (transposed): too many tiles"); return SHG_ERR_ARG; }
-    P.ntiles = (int)ntiles;
-    P.m_ot = 0xFFFFFFFFu / (unsigned)P.n_ot; P.m_tx = 0xFFFFFFFFu / (unsigned)P.tiles_x; P.m_ty = 0xFFFFFFFFu / (unsigned)P.tiles_y;
-    const int cus = shg_cu_count();
-    static ShgDeviceOnce attr_once;
-    const int dev_now = shg_current_device();
-    if (attr_once.pending(dev_now)) {
-        if (hipFuncSetAttribute((const void*)upring::conv_f16_upring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, upring::LDS_BYTES) != hipSuccess) {
-            shg_set_error("conv2d_f16 (transposed): cannot reserve %d bytes of LDS", upring::LDS_BYTES);
-            return SHG_ERR_LAUNCH;
-        }
-        attr_once.mark(dev_now);
-    }
-    const unsigned grid = (unsigned)(ntiles < cus ? ntiles : cus);
-    hipLaunchKernelGGL(upring::conv_f16_upring_kernel, dim3(grid), dim3(512), upring::LDS_BYTES, st, P);
-    SHG_CHECK_LAUNCH();
-    return SHG_OK;
+    return persistent_launch<upring::conv_f16_upring_kernel>(p0.N, shg_cdiv(p0.H + 1, upring::TH), shg_cdiv(p0.W + 1, upring::TW), (p0.O + 31) / 32, upring::LDS_BYTES,
+                                                             "transposed", [&](const TileWalk& w) { return std::make_tuple(upring::UpP{p0, crop, w}); }, st);
 }
 
 }  // namespace f16

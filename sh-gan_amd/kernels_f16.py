@@ -1,4 +1,4 @@
-"""Host wrappers of the fp16 entry points of libshgan_hip.so (csrc/conv_f16.hip; include/shgan_hip.h "fp16 route") -- the kernels
+"""Host wrappers of the fp16 entry points of libshgan_hip.so (csrc/conv_f16*.hip, conv_wgrad_f16.hip, upfirdn2d_f16.hip, pointwise_f16.hip; include/shgan_hip.h "fp16 route") -- the kernels
 behind the reference's ``use_fp16`` branches (stylegan.py:136-138,486,660-667; comodgan.py:40-47,305).
 
 Every fp16 activation is a ``[N,C,H,W]`` torch tensor in ``torch.channels_last`` memory format (= dense NHWC in HBM): the module
@@ -284,7 +284,7 @@ def _noise_flat(L, noise, n, hw):
 
 
 def modtail(t, d=None, noise=None, bias=None, act=False, gain=1.0, alpha=0.2, act_gain=kernels.SQRT2, clamp=256.0):
-    """y = A(t * d[n,c] + noise + bias[c]) in one pass (csrc/conv_f16.hip modtail_f16_kernel)."""
+    """y = A(t * d[n,c] + noise + bias[c]) in one pass (csrc/pointwise_f16.hip modtail_f16_kernel)."""
     L = kernels._Launch()
     t = _h(L, t, 't')
     n, c, h, w = t.shape

@@ -267,7 +267,7 @@ def bias_act(x, bias=None, act=True, gain=1.0, alpha=0.2, act_gain=kernels.SQRT2
 
 class _ModTailFn(torch.autograd.Function):
     """y = A(t * d[n,c] + noise + bias[c]) in ONE kernel, and its first-order backward in ONE kernel + three tiny reductions -- float16
-    NHWC activations (csrc/conv_f16.hip modtail kernels) and float32 NCHW ones (forward: the fused bias_act kernel; backward:
+    NHWC activations (csrc/pointwise_f16.hip modtail kernels) and float32 NCHW ones (forward: the fused bias_act kernel; backward:
     modtail_backward_f32_kernel) -- instead of one tensor pass per operation and per gradient (the training-route fusion of
     stylegan.py:173,176-181,298-304).  Under ``create_graph`` (R1 / path-length regularisers) the backward is composed from the
     differentiable operators instead, so second derivatives keep working."""

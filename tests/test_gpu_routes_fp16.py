@@ -1,10 +1,10 @@
 """Route table of the float16 entry points of shgan_amd.kernels_f16 (run with -m gpu on an MI355X).
 
-The counterpart of tests/test_gpu_routes_fp32.py for csrc/conv_f16.hip, conv_f16_ring.hip, conv_f16_upring.hip and conv_f16_down.hip: each
-case names the kernel (or template instantiation) that must serve its input and the ones that must not, sits one step either side of a
+The counterpart of tests/test_gpu_routes_fp32.py for the fp16 sources (csrc/conv_f16*.hip, conv_wgrad_f16.hip, upfirdn2d_f16.hip,
+pointwise_f16.hip): each case names the kernel (or template instantiation) that must serve its input and the ones that must not, sits one step either side of a
 dispatch predicate or a loop bound (grid caps with grid-stride loops, the slice loop of the weight gradient, the trips of the tail's
 backward), and compares the result with a float64 evaluation of the same operation on the same half-rounded operands.  The last two tests
-are host-only: the table covers every hipLaunchKernelGGL site of the four sources.
+are host-only: the table covers every launch site of those sources.
 
 Bars (from the arithmetic, not from the code under test):
   * outputs rounded to half once from an fp32 accumulation (conv2d, conv_transpose2d, conv2d_wgrad, upfirdn2d):
@@ -327,7 +327,7 @@ def convT(n, i, o, h, w, pad=0, bias=False):
 # the table: id -> (builder, expect, forbid, switches); switches: routes = mask of shg_conv2d_f16_set_routes for the case, twice = run
 # again and compare the bits
 # ------------------------------------------------------------------------------------------------
-GATHER, RING, UPRING, DOWN = 'conv_f16_kernel', 'conv_f16_ring_kernel<9>', 'conv_f16_upring_kernel', 'conv_f16_down_kernel'
+GATHER, RING, UPRING, DOWN = 'conv_f16_kernel', 'conv_f16_ring_kernel', 'conv_f16_upring_kernel', 'conv_f16_down_kernel'
 WG31, WG32, WG11 = 'conv_wgrad_f16_kernel<3, 1>', 'conv_wgrad_f16_kernel<3, 2>', 'conv_wgrad_f16_kernel<1, 1>'
 RED = 'f16::wgrad_reduce_kernel'
 MT, MTB, BA, BAB = 'modtail_f16_kernel', 'modtail_backward_f16_kernel', 'bias_act_f16_kernel', 'bias_act_backward_f16_kernel'
@@ -548,8 +548,8 @@ def test_route(case):
         assert (v < bar) if strict else (v <= bar), f'{case}: {label} {v:.3e} exceeds {bar:.0e}'
 
 
-# Every kernel launched from conv_f16.hip, conv_f16_ring.hip, conv_f16_upring.hip and conv_f16_down.hip (their hipLaunchKernelGGL sites),
-# with the instantiation where the site picks one.
+# Every kernel launched from the fp16 sources (F16_SOURCES: their hipLaunchKernelGGL sites, and the persistent_launch<kernel> sites of the
+# three persistent convolutions), with the instantiation where the site picks one.
 ROUTE_KERNELS = (
     ALL_GATHER
     + [RING, UPRING, DOWN, WG31, WG32, WG11] + [f'{RED}<{g}>' for g in (1, 2, 4, 8, 16)]
@@ -565,7 +565,7 @@ NOT_ROUTED = {
                                    'its output, and test_direct_weight_pack_equals_the_staged_pack covers its transposed / rotated forms',
 }
 
-F16_SOURCES = ('conv_f16.hip', 'conv_f16_ring.hip', 'conv_f16_upring.hip', 'conv_f16_down.hip')
+F16_SOURCES = ('conv_f16.hip', 'conv_wgrad_f16.hip', 'upfirdn2d_f16.hip', 'pointwise_f16.hip', 'conv_f16_ring.hip', 'conv_f16_upring.hip', 'conv_f16_down.hip')
 
 
 def test_route_table_covers_every_kernel():
@@ -577,12 +577,12 @@ def test_route_table_covers_every_kernel():
 
 
 def test_route_table_names_every_launch_site():
-    """Every hipLaunchKernelGGL site of the four fp16 sources launches a kernel of ROUTE_KERNELS or of NOT_ROUTED, and the table names no
-    kernel those sources do not launch (host-only: reads the sources)."""
+    """Every launch site of the fp16 sources launches a kernel of ROUTE_KERNELS or of NOT_ROUTED, and the table names no kernel those
+    sources do not launch (host-only: reads the sources)."""
     sites = set()
     for name in F16_SOURCES:
         with open(os.path.join(ROOT, 'sh-gan_amd', 'csrc', name)) as fh:
-            sites |= {m.split('::')[-1] for m in re.findall(r'hipLaunchKernelGGL\(\(?\s*([\w:]+)', fh.read())}
+            sites |= {m.split('::')[-1] for m in re.findall(r'(?:hipLaunchKernelGGL\(\(?|persistent_launch<)\s*([\w:]+)', fh.read())}
     assert len(sites) >= 19, sorted(sites)
     table = {re.match(r'[\w:]+', k).group(0).split('::')[-1] for k in ROUTE_KERNELS} | set(NOT_ROUTED)
     assert sites == table, (sorted(sites - table), sorted(table - sites))

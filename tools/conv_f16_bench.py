@@ -1,4 +1,4 @@
-"""Per-shape timing of the fp16 convolution family (csrc/conv_f16.hip): forward, transposed, weight gradient.  usage: python tools/conv_f16_bench.py"""
+"""Per-shape timing of the fp16 convolution family (csrc/conv_f16*.hip, conv_wgrad_f16.hip; the tail passes of pointwise_f16.hip): forward, transposed, weight gradient.  usage: python tools/conv_f16_bench.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
