@@ -103,7 +103,8 @@ def row(name, got, want, tol, scale=None):
 
 # ------------------------------------------------------------------------------------------------
 # case builders: each returns (call, judge); the inputs are built before the probe, ``call()`` enqueues the entry point(s) and returns
-# nothing, ``judge()`` reads the outputs back and returns the records (name, measured, bound)
+# the buffers they write (whole, guard rows and pad columns included), ``judge()`` reads the outputs back and returns the records
+# (name, measured, bound)
 # ------------------------------------------------------------------------------------------------
 
 def dense_case(n, k, o, bias=True, act=False, bgain=1.0, pad_y=0, pad_x=0, gain=1.0):
@@ -118,9 +119,11 @@ def dense_case(n, k, o, bias=True, act=False, bgain=1.0, pad_y=0, pad_x=0, gain=
 
         def call():
             cabi('shg_dense_f32', ptr(xd), ptr(wd), ptr(bd), ptr(y.view), n, k, o, k + pad_x, y.ld, wgain, bgain, a, al, g, cl)
+            return [y.buf]
     else:
         def call():
             assert kk.dense(xd, wd, bd, wgain=wgain, bgain=bgain, act=act, gain=gain, out=y.view).data_ptr() == y.view.data_ptr()
+            return [y.buf]
 
     def judge():
         got, want = y.check('y'), ref.dense(x, w, b, wgain, bgain, act, gain)
@@ -140,6 +143,7 @@ def matmul_nn_case(n, m, k, scale=0.37, pad_a=0, pad_o=0):
 
     def call():
         cabi('shg_matmul_nn_f32', ptr(ad), ptr(bd), ptr(out.view), n, m, k, m + pad_a, out.ld, scale)
+        return [out.buf]
 
     def judge():
         # c: a wave adds its slice of ceil(M / 16) products, 16 wave sums meet in LDS, then the scale: ceil(M / 16) + 18 with two to spare
@@ -156,6 +160,7 @@ def matmul_tn_case(n, m, k, colsum=True, scale=-1.3, pad_a=0, pad_b=0):
 
     def call():
         cabi('shg_matmul_tn_f32', ptr(ad), ptr(bd), ptr(out.view), ptr(col.view) if colsum else None, n, m, k, m + pad_a, k + pad_b, scale, cs)
+        return [out.buf, col.buf]
 
     def judge():
         want, wcol = ref.matmul_tn(a, b, scale, cs if colsum else None)
@@ -178,6 +183,7 @@ def normalize_case(n, k, zero_row=None):
 
     def call():
         cabi('shg_normalize_2nd_moment_f32', ptr(xd), ptr(y.view), n, k, 1e-8)
+        return [y.buf]
 
     def judge():
         got = y.check('y')
@@ -198,6 +204,7 @@ def demod_case(o, i, k, prenorm, bwd='both'):
     def call():
         cabi('shg_demod_weight_f32', ptr(wd), ptr(wn.view), ptr(wsq.view), ptr(sfac.view), o, i, k, int(prenorm))
         cabi('shg_demod_weight_backward_f32', ptr(wn.view), ptr(sfac.view), ptr(gnd), ptr(gqd), ptr(gw.view), o, i, k)
+        return [wn.buf, wsq.buf, sfac.buf, gw.buf]
 
     def judge():
         rn, rq, rs = ref.demod_weight(w, prenorm)
@@ -236,6 +243,7 @@ def style_case(n, i, o, prenorm, bwd='both', want_wsq=True, ties=False, fwd_d=Tr
         if fwd_d:
             cabi('shg_style_factors_backward_f32', ptr(sn.view), ptr(d.view), ptr(wd), ptr(aux.view), ptr(gsd), ptr(gdd), ptr(gs.view),
                  ptr(gw.view) if want_wsq else None, ptr(part.view), n, i, o, int(prenorm))
+        return [sn.buf, d.buf, aux.buf, gs.buf, gw.buf, part.buf]
 
     def judge():
         rsn, rd, raux = ref.style_factors(s, wsq, prenorm)
@@ -312,6 +320,7 @@ def style_fn_case(n, i, o, half):
     def call():
         assert sg.CLOSED_STYLE_FACTORS_BACKWARD
         got[:] = _autograd_style(lambda s, w: sg._StyleFactorsFn.apply(s, w, half), torch.float32, s64, w64, *rest, DEV)
+        return list(got)
 
     def judge():
         names = ('sn', 'd', 'g_styles', 'g_wsq', '2nd:styles', '2nd:wsq', '2nd:g_sn', '2nd:g_d')
@@ -333,6 +342,7 @@ def modulation_n33_case(half):
             assert not _kk().style_factors_supported(sd, wd)
             _, sn, d = sg._modulation_factors(half, None, sd, True, wfac=(None, wd))
             got[:] = [sn.detach(), d.detach()] + list(torch.autograd.grad((sn * a.to(DEV)).sum() + (d * b.to(DEV)).sum(), [sd, wd]))
+        return list(got)
 
     def judge():
         rsn, rd, raux = ref.style_factors(s, wsq, half)
@@ -353,6 +363,7 @@ def style_prep_case(n, i, o, demod=True, pre_gain=1.0, pad=0):
     def call():
         cabi('shg_modconv_style_prep_f32', ptr(sd), i + pad, ptr(pw.wsq) if demod else None, ptr(s_out.view), ptr(d_out.view) if demod else None, n, i,
              o if demod else 0, op, int(demod), pre_gain)
+        return [s_out.buf, d_out.buf]
 
     def judge():
         table = pw.wsq.cpu().double().reshape(i, op) if demod else None
@@ -395,6 +406,7 @@ def grouped_case(n, items=33):
     def call():
         kk.dense_grouped(d_items)
         kk.modconv_style_prep_grouped(p_items)
+        return [raw.buf] + [r[8].buf for r in recs_in] + [r[9].buf for r in recs_in if r[9] is not None]
 
     def judge():
         buf = raw.buf.cpu()
