@@ -552,6 +552,33 @@ int shg_ada_apply_f32(const float* x, const float* G_inv, const float* Cm, const
 int shg_ada_apply_adjoint_f32(const float* gy, const float* G_inv, const float* Cm, const int* margins, float* gx, int N, int C, int H, int W,
                               int geom, int color_first, int color_count, void* stream);
 
+/* ---- the tail of the ADA pipe (sh-gan_amd/ada.py: FullAugmentPipe; csrc/ada_tail.hip): ADA's image-space filter, additive noise and cutout,
+ * in ADA's order, after the colour stage.  shg_ada_tail_params_f32: draws ut [N,8] (uniform in [0,1)) and gt [N,5] (standard normal), column
+ * layout in ada.py, and the probability p (ONE float in device memory) -> Hz [N,43], the per-sample taps g @ Hz_fbank (the 4 x 43 sym2 bank
+ * lives with the kernel); sigma [N]; cut [N,4] = {cx, cy, half_w, half_h} in units of the image size.  One workgroup, float64 arithmetic,
+ * no host synchronisation; cfg is HOST memory.  A sample none of whose band gates fired gets the exact unit impulse (tap 21 = 1, the rest 0);
+ * closed gates give sigma = 0 and half sizes 0.
+ * shg_ada_tail_apply_f32: x, y [N,C,H,W], x != y, z [N,color_count,H,W].  On channels [color_first, color_first + color_count):
+ * y = mask * (fir(x) + sigma z), fir = reflect-pad by 21, the 43 taps along x, then along y (correlations), fused in one launch through
+ * LDS; on the other channels y = mask * x.  mask = |(x + 0.5) / W - cx| >= half_w or |(y + 0.5) / H - cy| >= half_h, in float32.  A null Hz,
+ * z (with sigma) or cut skips that stage; all three null: SHG_ERR_ARG.  bias = 0 drops the noise term (the operator's linear part).  A
+ * sample whose taps are the exact impulse is not filtered: its bits pass.  With Hz: H, W >= 22 (reflect: pad < size), else SHG_ERR_ARG.
+ * shg_ada_tail_adjoint_f32: gx = A^T gy, A the linear part of the same call (not self-adjoint: the reflected pad folds back).  A gather,
+ * no atomics: gx is the same bits on every run and need not be cleared. */
+typedef struct {
+    float imgfilter;                 /* probability multiplier of every band gate */
+    float bands[4];                  /* ADA's imgfilter_bands: per-band factor of that probability */
+    float imgfilter_std;
+    float noise, noise_std;
+    float cutout, cutout_size;
+} shg_ada_tail_config;
+int shg_ada_tail_params_f32(const float* ut, const float* gt, const float* p, const shg_ada_tail_config* cfg, float* Hz, float* sigma,
+                            float* cut, int N, void* stream);
+int shg_ada_tail_apply_f32(const float* x, const float* Hz, const float* sigma, const float* z, const float* cut, float* y, int N, int C, int H,
+                           int W, int color_first, int color_count, int bias, void* stream);
+int shg_ada_tail_adjoint_f32(const float* gy, const float* Hz, const float* cut, float* gx, int N, int C, int H, int W, int color_first,
+                             int color_count, void* stream);
+
 /* ---- next row N3 (training-side critic, forward only): minibatch_std_layer (stylegan.py:686-704).
  * x [N,C,H,W] -> y [N,C+F,H,W]; N % G == 0, C % F == 0; stat [N/G * F] is caller-owned scratch. */
 int shg_minibatch_std_f32(const float* x, float* y, float* stat, int N, int C, int H, int W, int G, int F, void* stream);

@@ -37,6 +37,11 @@ class AdaConfig(ctypes.Structure):           # shg_ada_config
                                    'contrast_std', 'hue_max', 'saturation_std')] + [('color_count', c_i)]
 
 
+class AdaTailConfig(ctypes.Structure):       # shg_ada_tail_config
+    _fields_ = [('imgfilter', c_f), ('bands', c_f * 4), ('imgfilter_std', c_f), ('noise', c_f), ('noise_std', c_f), ('cutout', c_f),
+                ('cutout_size', c_f)]
+
+
 class IncConv(ctypes.Structure):             # shg_inc_conv_desc
     _fields_ = [('x', c_fp), ('w', c_fp), ('bias', c_fp), ('y', c_fp)] + [
         (n, c_i) for n in ('I', 'H', 'W', 'x_ctot', 'x_coff', 'O', 'kh', 'kw', 'sh', 'sw', 'ph', 'pw', 'OH', 'OW', 'y_ctot', 'y_coff', 'splitk')]
@@ -159,6 +164,9 @@ _SIGS = {
     'shg_ada_params_f32': [c_fp, c_fp, c_fp, ctypes.POINTER(AdaConfig), c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_ada_apply_f32': [c_fp] * 5 + [c_i] * 8 + [c_fp],
     'shg_ada_apply_adjoint_f32': [c_fp] * 5 + [c_i] * 7 + [c_fp],
+    'shg_ada_tail_params_f32': [c_fp, c_fp, c_fp, ctypes.POINTER(AdaTailConfig), c_fp, c_fp, c_fp, c_i, c_fp],
+    'shg_ada_tail_apply_f32': [c_fp] * 6 + [c_i] * 7 + [c_fp],
+    'shg_ada_tail_adjoint_f32': [c_fp] * 4 + [c_i] * 6 + [c_fp],
     'shg_minibatch_std_f32': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
     'shg_conv2d_f16': [c_fp, c_fp, c_fp, c_fp] + [c_i] * 12 + [c_fp],
     'shg_conv2d_f16_needs_clear': [c_i] * 5,

@@ -20,7 +20,8 @@ draws are not those of ADA's many small ``torch.rand`` calls: the distribution i
 
 Channels.  Geometry moves every channel.  Colour acts on ``color_channels = (first, count)``, count 1 or 3; the default is all channels
 for C = 1 or 3 and channels 1..3 for C = 4 -- the critic input ``cat([mask - 0.5, img])`` of ``losses.InpaintingLoss``, whose mask channel
-keeps its values.  ``imgfilter``, ``noise`` and ``cutout`` are accepted as 0 only.
+keeps its values.  ``imgfilter``, ``noise`` and ``cutout`` are accepted as 0 only by ``AugmentPipe``; ``FullAugmentPipe`` (at the end of this
+file, ``csrc/ada_tail.hip``) runs them after the colour stage.
 
 The operator is linear in the image (plus the colour offset); its backward is ``shg_ada_apply_adjoint_f32``, whose backward is the forward
 kernel again, so R1 (``create_graph=True``) differentiates through it.  The adjoint accumulates with float atomics whose order is not fixed:
@@ -280,3 +281,220 @@ class AdaController:
         p = self.pipe.p
         p.copy_((p + adjust).clamp_(min=0))
         return adjust
+
+
+# ---- the tail of ADA's pipe: image-space filter, noise, cutout (csrc/ada_tail.hip) ---------------------------------------------------------
+# ``FullAugmentPipe`` is ``AugmentPipe`` followed by ADA's remaining three categories, in ADA's order.  One more parameter launch
+# (``shg_ada_tail_params_f32``: per-sample taps g @ Hz_fbank [N,43], sigma [N], the cutout box [N,4]) and one more fused launch
+# (``shg_ada_tail_apply_f32``).  Draw layout of the tail, ``ut`` [N, 8] uniform and ``gt`` [N, 5] normal, value | gate:
+#
+#     imgfilter band i (0..3) gt_i | ut_i        noise gt4 | ut4        cutout centre ut6 (x), ut7 (y) | ut5
+#
+# and the noise field ``z`` [N, count, H, W], standard normal.  The filter and the noise act on ``color_channels`` (the colour stage's rule
+# and default: the mask channel of the C = 4 critic input is neither filtered nor given noise); the cutout multiplies every channel.  The
+# transpose (``shg_ada_tail_adjoint_f32``) is a gather without atomics: gradients through the tail are the same bits on every run.
+N_UNIFORM_TAIL, N_NORMAL_TAIL, TAIL_TAPS = 8, 5, 43
+
+_SYM2 = (-0.12940952255092145, 0.22414386804185735, 0.836516303737469, 0.48296291314469025)       # ADA's wavelets['sym2']
+_TAIL = ('imgfilter', 'noise', 'cutout')
+
+_BGCF = dict(AUGPIPE_SPECS['bgc'], imgfilter=1)
+# ADA's named sets (train.py: augpipe_specs), all of them
+AUGPIPE_SPECS_FULL = dict(
+    AUGPIPE_SPECS,
+    filter=dict(imgfilter=1),
+    noise=dict(noise=1),
+    cutout=dict(cutout=1),
+    bgcf=_BGCF,
+    bgcfn=dict(_BGCF, noise=1),
+    bgcfnc=dict(_BGCF, noise=1, cutout=1),
+)
+
+
+def hz_fbank():
+    """ADA's ``Hz_fbank``, float64 [4, 43]: the sym2 low-pass and its mirror, three rounds of zero-stuffing and convolution."""
+    lo = np.asarray(_SYM2, dtype=np.float64)
+    hi = lo * ((-1.0) ** np.arange(lo.size))
+    lo2 = np.convolve(lo, lo[::-1]) / 2
+    hi2 = np.convolve(hi, hi[::-1]) / 2
+    fb = np.eye(4, 1)
+    for i in range(1, 4):
+        fb = np.dstack([fb, np.zeros_like(fb)]).reshape(4, -1)[:, :-1]
+        fb = np.stack([np.convolve(row, lo2) for row in fb])
+        fb[i, (fb.shape[1] - hi2.size) // 2:(fb.shape[1] + hi2.size) // 2] += hi2
+    return fb
+
+
+def ada_tail_params(ut, gt, p, cfg):
+    """-> (Hz [N,43], sigma [N], cut [N,4] = cx, cy, half_w, half_h) on the device, from draws ut [N,8], gt [N,5] and the one-element tensor
+    p; ``cfg`` an ``_lib.AdaTailConfig``.  One launch, nothing read back."""
+    n = ut.shape[0]
+    if (tuple(ut.shape) != (n, N_UNIFORM_TAIL) or tuple(gt.shape) != (n, N_NORMAL_TAIL) or ut.dtype != torch.float32
+            or gt.dtype != torch.float32):
+        raise _lib.ShgError(f'ada_tail_params: draws must be float32 ut [N, {N_UNIFORM_TAIL}] and gt [N, {N_NORMAL_TAIL}] (got '
+                            f'{tuple(ut.shape)}, {tuple(gt.shape)})')
+    if not (ut.is_cuda and gt.is_cuda and p.is_cuda and p.dtype == torch.float32 and p.numel() == 1):
+        raise _lib.ShgError('ada_tail_params: ut, gt and the float32 scalar p must live on the device')
+    ut, gt = ut.contiguous(), gt.contiguous()
+    with torch.cuda.device(ut.device):
+        Hz = torch.zeros([n, TAIL_TAPS], dtype=torch.float32, device=ut.device)
+        sigma = torch.zeros([n], dtype=torch.float32, device=ut.device)
+        cut = torch.zeros([n, 4], dtype=torch.float32, device=ut.device)
+        _lib.check(_lib.get_lib().shg_ada_tail_params_f32(_ptr(ut), _ptr(gt), _ptr(p), ctypes.byref(cfg), _ptr(Hz), _ptr(sigma), _ptr(cut), n,
+                                                          _stream(ut)), 'ada_tail_params')
+    return Hz, sigma, cut
+
+
+def _tail_launch(adjoint, x, Hz, sigma, z, cut, color, bias):
+    _check_image(x, 'ada_tail_apply')
+    n, c, h, w = x.shape
+    first, count = color if color is not None else (0, 0)
+
+    def ok(t, shape):
+        return t is None or (tuple(t.shape) == shape and t.dtype == torch.float32 and t.device == x.device)
+    if not (ok(Hz, (n, TAIL_TAPS)) and ok(sigma, (n,)) and ok(z, (n, count, h, w)) and ok(cut, (n, 4))):
+        raise _lib.ShgError(f'ada_tail_apply: Hz [N,{TAIL_TAPS}], sigma [N], z [N,{count},H,W] and cut [N,4] must be float32 on the image device')
+    x = x.contiguous()
+    Hz, sigma, z, cut = (t.contiguous() if t is not None else None for t in (Hz, sigma, z, cut))
+    with torch.cuda.device(x.device):
+        # zero-filled although the kernels write every element (tests/test_gpu_ada_tail.py runs them into poisoned buffers): an
+        # uninitialised allocation of the package needs a poison-fill case in tests/test_gpu_alloc_fill.py, and the tail has none
+        y = torch.zeros_like(x)
+        lib = _lib.get_lib()
+        if adjoint:
+            rc = lib.shg_ada_tail_adjoint_f32(_ptr(x), _ptr(Hz), _ptr(cut), _ptr(y), n, c, h, w, first, count, _stream(x))
+        else:
+            rc = lib.shg_ada_tail_apply_f32(_ptr(x), _ptr(Hz), _ptr(sigma), _ptr(z), _ptr(cut), _ptr(y), n, c, h, w, first, count, int(bias),
+                                            _stream(x))
+        _lib.check(rc, 'ada_tail_adjoint' if adjoint else 'ada_tail_apply')
+    return y
+
+
+class _AdaTailApplyFn(torch.autograd.Function):
+    """y = A x (+ sigma z when ``bias``); backward: the adjoint kernel."""
+
+    @staticmethod
+    def forward(ctx, x, Hz, sigma, z, cut, color, bias):
+        ctx.save_for_backward(Hz, cut)
+        ctx.color = color
+        return _tail_launch(False, x.detach(), Hz, sigma, z, cut, color, bias)
+
+    @staticmethod
+    def backward(ctx, gy):
+        Hz, cut = ctx.saved_tensors
+        if Hz is None and cut is None:               # noise alone: the linear part is the identity
+            return gy, None, None, None, None, None, None
+        return _AdaTailAdjointFn.apply(gy, Hz, cut, ctx.color), None, None, None, None, None, None
+
+
+class _AdaTailAdjointFn(torch.autograd.Function):
+    """gx = A^T gy; backward: the forward kernel without the noise term (the operator is linear)."""
+
+    @staticmethod
+    def forward(ctx, gy, Hz, cut, color):
+        ctx.save_for_backward(Hz, cut)
+        ctx.color = color
+        return _tail_launch(True, gy.detach(), Hz, None, None, cut, color, False)
+
+    @staticmethod
+    def backward(ctx, ggx):
+        Hz, cut = ctx.saved_tensors
+        if Hz is None and cut is None:
+            return ggx, None, None, None
+        return _AdaTailApplyFn.apply(ggx, Hz, None, None, cut, ctx.color, False), None, None, None
+
+
+def _tail_color(Hz, z, color_channels, c):
+    if Hz is None and z is None:
+        return None
+    color = tuple(int(v) for v in color_channels) if color_channels is not None else default_color_channels(c)
+    _check_color(color, c)
+    return color
+
+
+def ada_tail_apply(x, Hz=None, sigma=None, z=None, cut=None, color_channels=None):
+    """The tail's image operator on given parameters (differentiable in ``x``, twice): ``mask * (fir(x) + sigma z)`` on ``color_channels =
+    (first, count)``, ``mask * x`` on the others.  The filter runs when ``Hz`` [N,43] is given, the noise when ``sigma`` [N] and ``z``
+    [N,count,H,W] are, the cutout when ``cut`` [N,4] is.  None of them: ``x`` itself."""
+    if (sigma is None) != (z is None):
+        raise ValueError('ada_tail_apply: the noise needs both sigma and z')
+    if Hz is None and z is None and cut is None:
+        return x
+    return _AdaTailApplyFn.apply(x, Hz, sigma, z, cut, _tail_color(Hz, z, color_channels, x.shape[1]), True)
+
+
+def ada_tail_apply_adjoint(gy, Hz=None, cut=None, color_channels=None):
+    """The transpose of ``ada_tail_apply``'s linear part ``mask * fir``."""
+    if Hz is None and cut is None:
+        return gy
+    return _AdaTailAdjointFn.apply(gy, Hz, cut, _tail_color(Hz, None, color_channels, gy.shape[1]))
+
+
+class FullAugmentPipe(AugmentPipe):
+    """ADA's whole pipe: ``AugmentPipe`` (blit, geometry, colour), then imgfilter, noise and cutout.  ``draws`` is ``(u, g, ut, gt)`` or
+    ``(u, g, ut, gt, z)``; without ``z`` a noise field is drawn with one ``torch.randn``.  ``(u, g)`` alone serves while the tail is off."""
+
+    def __init__(self, xflip=0, rotate90=0, xint=0, xint_max=0.125,
+                 scale=0, rotate=0, aniso=0, xfrac=0, scale_std=0.2, rotate_max=1, aniso_std=0.2, xfrac_std=0.125,
+                 brightness=0, contrast=0, lumaflip=0, hue=0, saturation=0, brightness_std=0.2, contrast_std=0.5, hue_max=1, saturation_std=1,
+                 imgfilter=0, imgfilter_bands=(1, 1, 1, 1), imgfilter_std=1, noise=0, cutout=0, noise_std=0.1, cutout_size=0.5,
+                 color_channels=None):
+        super().__init__(xflip=xflip, rotate90=rotate90, xint=xint, xint_max=xint_max, scale=scale, rotate=rotate, aniso=aniso, xfrac=xfrac,
+                         scale_std=scale_std, rotate_max=rotate_max, aniso_std=aniso_std, xfrac_std=xfrac_std, brightness=brightness,
+                         contrast=contrast, lumaflip=lumaflip, hue=hue, saturation=saturation, brightness_std=brightness_std,
+                         contrast_std=contrast_std, hue_max=hue_max, saturation_std=saturation_std, imgfilter=0, noise=0, cutout=0,
+                         color_channels=color_channels)
+        self.imgfilter, self.noise, self.cutout = float(imgfilter), float(noise), float(cutout)
+        self.imgfilter_bands = tuple(float(v) for v in imgfilter_bands)
+        if len(self.imgfilter_bands) != 4:
+            raise ValueError(f'FullAugmentPipe: imgfilter_bands must have 4 entries, one per band of Hz_fbank (got {len(self.imgfilter_bands)})')
+        self.imgfilter_std, self.noise_std, self.cutout_size = float(imgfilter_std), float(noise_std), float(cutout_size)
+        self.register_buffer('Hz_fbank', torch.as_tensor(hz_fbank(), dtype=torch.float32))     # ADA's state_dict key; the kernel holds the taps
+
+    @property
+    def tail_on(self):
+        return any(getattr(self, n) > 0 for n in _TAIL)
+
+    def _tail_config(self):
+        cfg = _lib.AdaTailConfig()
+        for name in ('imgfilter', 'imgfilter_std', 'noise', 'noise_std', 'cutout', 'cutout_size'):
+            setattr(cfg, name, getattr(self, name))
+        cfg.bands[:] = self.imgfilter_bands
+        return cfg
+
+    def draw(self, n, device=None):
+        """Fresh draws for n images: (u [n,24], g [n,8], ut [n,8], gt [n,5]) on the device; one generator call each (graph-safe)."""
+        device = self.p.device if device is None else device
+        return super().draw(n, device) + (torch.rand([n, N_UNIFORM_TAIL], device=device), torch.randn([n, N_NORMAL_TAIL], device=device))
+
+    def params(self, draws, c, h, w):
+        return super().params(tuple(draws)[:2], c, h, w)
+
+    def tail_params(self, draws):
+        """-> (Hz, sigma, cut) of the tail on the draws (u, g, ut, gt[, z])."""
+        return ada_tail_params(draws[2], draws[3], self.p.reshape(1), self._tail_config())
+
+    def forward(self, images, draws=None):
+        _check_image(images, 'FullAugmentPipe')
+        n, c, h, w = images.shape
+        color = self._color_for(c)
+        tail = self.tail_on
+        if not tail and not self.geometry_on and not self.color_on:
+            return images
+        if draws is None and (self.geometry_on or self.color_on):
+            draws = self.draw(n, images.device)
+        elif draws is None:                          # the tail alone: u and g would not be read
+            draws = (None, None, torch.rand([n, N_UNIFORM_TAIL], device=images.device), torch.randn([n, N_NORMAL_TAIL], device=images.device))
+        draws = tuple(draws)
+        if len(draws) not in ((4, 5) if tail else (2, 4, 5)):
+            raise ValueError(f'FullAugmentPipe: draws must be (u, g, ut, gt) or (u, g, ut, gt, z){"" if tail else " or (u, g)"} '
+                             f'(got {len(draws)} entries)')
+        images = super().forward(images, draws[:2])
+        if not tail:
+            return images
+        Hz, sigma, cut = self.tail_params(draws)
+        z = None
+        if self.noise > 0:
+            z = draws[4] if len(draws) == 5 else torch.randn([n, color[1], h, w], device=images.device)
+        return ada_tail_apply(images, Hz if self.imgfilter > 0 else None, sigma if z is not None else None, z,
+                              cut if self.cutout > 0 else None, color)
