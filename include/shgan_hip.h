@@ -537,7 +537,16 @@ int shg_randcrop_bicubic_planar_f32(const void* src, long src_bytes, const int* 
  * color_count = 1: channel color_first becomes x * mean_r(sum_c M[r][c]) + mean_r(t[r]); 0: no colour stage, Cm is not read.  Every other
  * channel passes the geometry alone.  geom = 0 and color_count = 0 together: SHG_ERR_ARG (the caller passes the tensor through).
  * shg_ada_apply_adjoint_f32: gx = A^T gy, A the linear part of the same call.  With geom = 1 gx must be ZERO on entry (float atomics
- * accumulate into it, staged through LDS); their order is not fixed, so gx is not bit-reproducible from run to run.  N * C <= 65535. */
+ * accumulate into it, staged through LDS); their order is not fixed, so gx is not bit-reproducible from run to run.  N * C <= 65535.
+ * shg_ada_apply_adjoint_gather_f32: the same gx in gather form, the same bits on every run.  Two launches without atomics: gs = D^T C^T gy
+ * on the sample grid [N,C,2H+10,2W+10] into the caller's workspace (shg_ada_adjoint_gather_workspace_bytes; device memory, contents
+ * irrelevant on entry), then every source pixel sums, in a fixed order and in float64, the samples whose bilinear footprint reaches the
+ * upsampled pixels it feeds (csrc/ada_geom.h: the window of a pixel is the bounding box of the inverse affine map).  gx need NOT be
+ * cleared: every element is written.  Decided per sample on the device: a sample whose window half extents |M00| + |M01|, |M10| + |M11|
+ * (M the inverse of the 2 x 2 part) are at most 24 and whose entries are finite and of sane size (|k| + |L| (2 (W + H) + 20) <= 2^24,
+ * csrc/ada_geom.h) takes the gather; any other sample (a singular, more than ~16-fold magnifying, huge or non-finite matrix) is handled
+ * by the scatter kernel launched behind it -- correct, but that sample's gradient is not bit-reproducible.  geom = 0: the colour kernel alone, workspace not read.  geom = 1 with a null or too small
+ * workspace: SHG_ERR_ARG.  shg_ada_adjoint_gather_workspace_bytes: 0 for sizes the entry point rejects. */
 typedef struct {
     float xflip, rotate90, xint, scale, rotate, aniso, xfrac;          /* probability multipliers, geometry */
     float brightness, contrast, lumaflip, hue, saturation;             /* probability multipliers, colour */
@@ -551,6 +560,10 @@ int shg_ada_apply_f32(const float* x, const float* G_inv, const float* Cm, const
                       int color_first, int color_count, int bias, void* stream);
 int shg_ada_apply_adjoint_f32(const float* gy, const float* G_inv, const float* Cm, const int* margins, float* gx, int N, int C, int H, int W,
                               int geom, int color_first, int color_count, void* stream);
+long shg_ada_adjoint_gather_workspace_bytes(int N, int C, int H, int W);
+int shg_ada_apply_adjoint_gather_f32(const float* gy, const float* G_inv, const float* Cm, const int* margins, float* gx, void* workspace,
+                                     long workspace_bytes, int N, int C, int H, int W, int geom, int color_first, int color_count,
+                                     void* stream);
 
 /* ---- the tail of the ADA pipe (sh-gan_amd/ada.py: FullAugmentPipe; csrc/ada_tail.hip): ADA's image-space filter, additive noise and cutout,
  * in ADA's order, after the colour stage.  shg_ada_tail_params_f32: draws ut [N,8] (uniform in [0,1)) and gt [N,5] (standard normal), column

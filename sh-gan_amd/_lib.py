@@ -164,6 +164,8 @@ _SIGS = {
     'shg_ada_params_f32': [c_fp, c_fp, c_fp, ctypes.POINTER(AdaConfig), c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_ada_apply_f32': [c_fp] * 5 + [c_i] * 8 + [c_fp],
     'shg_ada_apply_adjoint_f32': [c_fp] * 5 + [c_i] * 7 + [c_fp],
+    'shg_ada_adjoint_gather_workspace_bytes': [c_i] * 4,
+    'shg_ada_apply_adjoint_gather_f32': [c_fp] * 6 + [c_l] + [c_i] * 7 + [c_fp],
     'shg_ada_tail_params_f32': [c_fp, c_fp, c_fp, ctypes.POINTER(AdaTailConfig), c_fp, c_fp, c_fp, c_i, c_fp],
     'shg_ada_tail_apply_f32': [c_fp] * 6 + [c_i] * 7 + [c_fp],
     'shg_ada_tail_adjoint_f32': [c_fp] * 4 + [c_i] * 6 + [c_fp],
@@ -224,6 +226,7 @@ def get_lib():
     lib.shg_inception_conv_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_kid_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_pr_workspace_bytes.restype = ctypes.c_size_t
+    lib.shg_ada_adjoint_gather_workspace_bytes.restype = c_l
     lib.shg_inception_packed_weight_elems.restype = c_l
     lib.shg_conv2d_f16_packed_weight_elems.restype = c_l
     lib.shg_conv_wino4_weight_elems.restype = c_l

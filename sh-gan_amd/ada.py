@@ -25,7 +25,14 @@ file, ``csrc/ada_tail.hip``) runs them after the colour stage.
 
 The operator is linear in the image (plus the colour offset); its backward is ``shg_ada_apply_adjoint_f32``, whose backward is the forward
 kernel again, so R1 (``create_graph=True``) differentiates through it.  The adjoint accumulates with float atomics whose order is not fixed:
-gradients through the pipe are not bit-reproducible from run to run."""
+gradients through the pipe are not bit-reproducible from run to run.
+
+``deterministic=True`` (``ada_apply``, ``ada_apply_adjoint``, ``AugmentPipe``, ``FullAugmentPipe``; off by default) takes the gather form of
+the adjoint instead, ``shg_ada_apply_adjoint_gather_f32``: two launches without atomics and a workspace of the sample grid's size; the
+gradient is the same bits on every run and for every batch a sample is part of (given the margins).  The forward is the same launch either
+way.  The one exception is decided per sample on the device: a singular matrix, one that magnifies more than about 16-fold or one with a
+non-finite or huge (2^24) entry is left to the scatter kernel -- that sample's gradient is correct but not bit-reproducible (the parameter kernel
+cannot produce such a matrix from finite draws)."""
 import ctypes
 
 import numpy as np
@@ -86,7 +93,7 @@ def ada_params(u, g, p, cfg, H, W):
     return G, Cm, margins
 
 
-def _launch(adjoint, x, G, Cm, margins, geom, color, bias):
+def _launch(adjoint, x, G, Cm, margins, geom, color, bias, deterministic=False):
     _check_image(x, 'ada_apply')
     n, c, h, w = x.shape
     first, count = color if color is not None else (0, 0)
@@ -100,10 +107,16 @@ def _launch(adjoint, x, G, Cm, margins, geom, color, bias):
     Cm = Cm.contiguous() if count else None
     margins = margins.contiguous() if geom else None
     with torch.cuda.device(x.device):
-        # the adjoint accumulates into its output with atomics
-        y = torch.zeros_like(x) if adjoint and geom else torch.empty_like(x)
         lib = _lib.get_lib()
-        if adjoint:
+        gather = bool(adjoint and deterministic)
+        # the scatter adjoint accumulates into its output with atomics; the gather form writes every element
+        y = torch.zeros_like(x) if adjoint and geom and not gather else torch.empty_like(x)
+        if gather:
+            nbytes = int(lib.shg_ada_adjoint_gather_workspace_bytes(n, c, h, w)) if geom else 0
+            ws = torch.empty([nbytes // 4], dtype=torch.float32, device=x.device) if nbytes else None
+            rc = lib.shg_ada_apply_adjoint_gather_f32(_ptr(x), _ptr(G), _ptr(Cm), _ptr(margins), _ptr(y), _ptr(ws), nbytes, n, c, h, w, int(geom),
+                                                      first, count, _stream(x))
+        elif adjoint:
             rc = lib.shg_ada_apply_adjoint_f32(_ptr(x), _ptr(G), _ptr(Cm), _ptr(margins), _ptr(y), n, c, h, w, int(geom), first, count, _stream(x))
         else:
             rc = lib.shg_ada_apply_f32(_ptr(x), _ptr(G), _ptr(Cm), _ptr(margins), _ptr(y), n, c, h, w, int(geom), first, count, int(bias),
@@ -116,53 +129,54 @@ class _AdaApplyFn(torch.autograd.Function):
     """y = A x (+ the colour offset when ``bias``); backward: the adjoint kernel."""
 
     @staticmethod
-    def forward(ctx, x, G, Cm, margins, geom, color, bias):
+    def forward(ctx, x, G, Cm, margins, geom, color, bias, deterministic=False):
         ctx.save_for_backward(G, Cm, margins)
-        ctx.cfg = (geom, color)
+        ctx.cfg = (geom, color, bool(deterministic))
         return _launch(False, x.detach(), G, Cm, margins, geom, color, bias)
 
     @staticmethod
     def backward(ctx, gy):
         G, Cm, margins = ctx.saved_tensors
-        geom, color = ctx.cfg
-        return _AdaAdjointFn.apply(gy, G, Cm, margins, geom, color), None, None, None, None, None, None
+        geom, color, deterministic = ctx.cfg
+        return _AdaAdjointFn.apply(gy, G, Cm, margins, geom, color, deterministic), None, None, None, None, None, None, None
 
 
 class _AdaAdjointFn(torch.autograd.Function):
     """gx = A^T gy; backward: the forward kernel without the offset (the operator is linear)."""
 
     @staticmethod
-    def forward(ctx, gy, G, Cm, margins, geom, color):
+    def forward(ctx, gy, G, Cm, margins, geom, color, deterministic=False):
         ctx.save_for_backward(G, Cm, margins)
-        ctx.cfg = (geom, color)
-        return _launch(True, gy.detach(), G, Cm, margins, geom, color, False)
+        ctx.cfg = (geom, color, bool(deterministic))
+        return _launch(True, gy.detach(), G, Cm, margins, geom, color, False, deterministic)
 
     @staticmethod
     def backward(ctx, ggx):
         G, Cm, margins = ctx.saved_tensors
-        geom, color = ctx.cfg
-        return _AdaApplyFn.apply(ggx, G, Cm, margins, geom, color, False), None, None, None, None, None
+        geom, color, deterministic = ctx.cfg
+        return _AdaApplyFn.apply(ggx, G, Cm, margins, geom, color, False, deterministic), None, None, None, None, None, None
 
 
-def ada_apply(x, G_inv=None, Cm=None, margins=None, color_channels=None):
+def ada_apply(x, G_inv=None, Cm=None, margins=None, color_channels=None, deterministic=False):
     """The pipe's image operator on given parameters (differentiable in ``x``, twice): geometry when ``G_inv`` [N,3,3] and ``margins``
-    int32 [4] are given, colour on ``color_channels = (first, count)`` when ``Cm`` [N,3,4] is.  Neither: ``x`` itself."""
+    int32 [4] are given, colour on ``color_channels = (first, count)`` when ``Cm`` [N,3,4] is.  Neither: ``x`` itself.
+    ``deterministic``: the gradient takes the gather form of the adjoint (same bits on every run); the forward is the same launch."""
     geom, color = G_inv is not None, (tuple(int(v) for v in color_channels) if Cm is not None else None)
     if not geom and color is None:
         return x
     if color is not None:
         _check_color(color, x.shape[1])
-    return _AdaApplyFn.apply(x, G_inv, Cm, margins, geom, color, True)
+    return _AdaApplyFn.apply(x, G_inv, Cm, margins, geom, color, True, bool(deterministic))
 
 
-def ada_apply_adjoint(gy, G_inv=None, Cm=None, margins=None, color_channels=None):
-    """The transpose of ``ada_apply``'s linear part."""
+def ada_apply_adjoint(gy, G_inv=None, Cm=None, margins=None, color_channels=None, deterministic=False):
+    """The transpose of ``ada_apply``'s linear part; ``deterministic``: in gather form, without atomics."""
     geom, color = G_inv is not None, (tuple(int(v) for v in color_channels) if Cm is not None else None)
     if not geom and color is None:
         return gy
     if color is not None:
         _check_color(color, gy.shape[1])
-    return _AdaAdjointFn.apply(gy, G_inv, Cm, margins, geom, color)
+    return _AdaAdjointFn.apply(gy, G_inv, Cm, margins, geom, color, bool(deterministic))
 
 
 def _check_color(color, c):
@@ -184,8 +198,9 @@ class AugmentPipe(torch.nn.Module):
                  scale=0, rotate=0, aniso=0, xfrac=0, scale_std=0.2, rotate_max=1, aniso_std=0.2, xfrac_std=0.125,
                  brightness=0, contrast=0, lumaflip=0, hue=0, saturation=0, brightness_std=0.2, contrast_std=0.5, hue_max=1, saturation_std=1,
                  imgfilter=0, imgfilter_bands=(1, 1, 1, 1), imgfilter_std=1, noise=0, cutout=0, noise_std=0.1, cutout_size=0.5,
-                 color_channels=None):
+                 color_channels=None, deterministic=False):
         super().__init__()
+        self.deterministic = bool(deterministic)     # gradients through the geometry in gather form (a plain attribute, not a buffer)
         for name, value in (('imgfilter', imgfilter), ('noise', noise), ('cutout', cutout)):
             if float(value) != 0:
                 raise NotImplementedError(f'AugmentPipe: {name} is not part of the HIP path (only {name}=0 is accepted)')
@@ -245,7 +260,7 @@ class AugmentPipe(torch.nn.Module):
         if draws is None:
             draws = self.draw(n, images.device)
         G, Cm, margins, _ = self.params(draws, c, h, w)
-        return ada_apply(images, G if geom else None, Cm if col else None, margins if geom else None, color)
+        return ada_apply(images, G if geom else None, Cm if col else None, margins if geom else None, color, deterministic=self.deterministic)
 
 
 class AdaController:
@@ -438,12 +453,12 @@ class FullAugmentPipe(AugmentPipe):
                  scale=0, rotate=0, aniso=0, xfrac=0, scale_std=0.2, rotate_max=1, aniso_std=0.2, xfrac_std=0.125,
                  brightness=0, contrast=0, lumaflip=0, hue=0, saturation=0, brightness_std=0.2, contrast_std=0.5, hue_max=1, saturation_std=1,
                  imgfilter=0, imgfilter_bands=(1, 1, 1, 1), imgfilter_std=1, noise=0, cutout=0, noise_std=0.1, cutout_size=0.5,
-                 color_channels=None):
+                 color_channels=None, deterministic=False):
         super().__init__(xflip=xflip, rotate90=rotate90, xint=xint, xint_max=xint_max, scale=scale, rotate=rotate, aniso=aniso, xfrac=xfrac,
                          scale_std=scale_std, rotate_max=rotate_max, aniso_std=aniso_std, xfrac_std=xfrac_std, brightness=brightness,
                          contrast=contrast, lumaflip=lumaflip, hue=hue, saturation=saturation, brightness_std=brightness_std,
                          contrast_std=contrast_std, hue_max=hue_max, saturation_std=saturation_std, imgfilter=0, noise=0, cutout=0,
-                         color_channels=color_channels)
+                         color_channels=color_channels, deterministic=deterministic)
         self.imgfilter, self.noise, self.cutout = float(imgfilter), float(noise), float(cutout)
         self.imgfilter_bands = tuple(float(v) for v in imgfilter_bands)
         if len(self.imgfilter_bands) != 4:

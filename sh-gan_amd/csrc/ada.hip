@@ -25,8 +25,17 @@
 //     global memory directly.  gx must be zero on entry.  The order of float atomics is not fixed: the gradient is not bit-reproducible.
 // Source indices are clamped into the image and the margins (device data) into [0, size - 1]: no access is out of bounds whatever the
 // matrices hold (NaN included).
+//   * ada_cot_kernel + ada_gather_kernel (shg_ada_apply_adjoint_gather_f32, ada.py: deterministic=True): the same transpose in gather
+//     form, without atomics.  The forward is y = C D S U P x (reflect pad, x2 upsampling, bilinear sampling, x2 decimation, colour);
+//     launch 1 stores gs = D^T C^T gy on the sample grid into a workspace, launch 2 gives every 16 x 16 source tile its (at most 3 x 3)
+//     reflect images in turn: gather the upsampled cotangents gU = S^T gs on the 42 x 42 pixels the image reads, from the candidate
+//     window of ada_geom.h, apply U^T from LDS, fold into registers, store once.  Float64 sums in a fixed order: the same bits on every
+//     run, and gx need not be cleared.  A sample whose window is not bounded (ada_gather_inverse: singular, non-finite or magnifying
+//     beyond ADA_GATHER_HMAX) gets zeros there and is handled by ada_adjoint_kernel<true> behind it: correct, not bit-reproducible.
+// The coordinate arithmetic every kernel shares (ada_coord, ada_axis, ada_reflect, ada_geo, the window) lives in ada_geom.h.
 #include "shg_common.h"
 #include "../../include/shgan_hip.h"
+#include "ada_geom.h"
 
 namespace {
 
@@ -38,19 +47,6 @@ constexpr int ADA_CH = 4;                      // channels per pass of the forwa
 constexpr int ADA_FBOX = 2304;                 // entries per channel of the forward's source-window LDS tile
 constexpr int ADA_BOX = 4096;                  // entries (doubles) of the adjoint's source-space LDS tile
 constexpr int ADA_NU = 24, ADA_NG = 8;         // draw columns
-
-// sym6 low-pass (an orthonormal wavelet filter: the taps sum to sqrt 2), normalised to sum 1 as ada.py's Hz_geom
-constexpr double ADA_SYM6[12] = {0.015404109327027373,  0.0034907120842174702, -0.11799011114819057,  -0.048311742585633,
-                                 0.4910559419267466,    0.787641141030194,     0.3379294217276218,    -0.07263752278646252,
-                                 -0.021060292512300564, 0.04472490177066578,   0.0017677118642428036, -0.007800708325034148};
-constexpr double ada_sym6_sum() {
-    double s = 0.0;
-    for (int i = 0; i < 12; ++i) s += ADA_SYM6[i];
-    return s;
-}
-#define ADA_TAP(i) (float)(ADA_SYM6[i] / ada_sym6_sum())
-__device__ constexpr float ADA_F[12] = {ADA_TAP(0), ADA_TAP(1), ADA_TAP(2), ADA_TAP(3), ADA_TAP(4),  ADA_TAP(5),
-                                        ADA_TAP(6), ADA_TAP(7), ADA_TAP(8), ADA_TAP(9), ADA_TAP(10), ADA_TAP(11)};
 
 // ------------------------------------------------------------------------------------------------ parameters
 struct M3 {
@@ -212,63 +208,6 @@ __global__ __launch_bounds__(ADA_THREADS) void ada_params_kernel(const float* __
     }
 }
 
-// ------------------------------------------------------------------------------------------------ the resampling weights of one axis
-struct AdaAxis {
-    int lo;          // first padded index
-    int idx[7];      // source index of padded index lo + k (reflected, clamped into the image)
-    float w[7];
-};
-
-__device__ __forceinline__ int ada_reflect(int i, int m0, int n) {
-    int r = i - m0;
-    r = r < 0 ? -r : r;
-    r = r > n - 1 ? 2 * (n - 1) - r : r;
-    return min(max(r, 0), n - 1);
-}
-
-// upsampled-pixel coordinate of sample index j (the other axis' index is jo): a, b = the row of G_inv for this axis (own, other), t its
-// translation, n / no the sizes of this and the other axis, m0 / m1 this axis' margins
-__device__ __forceinline__ double ada_coord(int j, int jo, float a, float b, float t, int n, int no, int m0, int m1) {
-    const double uo = 0.5 * (double)(j - n - 5), uu = 0.5 * (double)(jo - no - 5);
-    const double np = (double)(n + m0 + m1);
-    double c = 2.0 * ((double)a * uo + (double)b * uu + (double)t) + (double)(m0 - m1) + np - 1.0;
-    return fmin(fmax(c, -4.0), 2.0 * np + 4.0);           // (a NaN ends at -4: every weight zero)
-}
-
-__device__ __forceinline__ void ada_axis(double c, int n, int m0, int m1, AdaAxis& ax) {
-    constexpr float A[7] = {ADA_F[11], ADA_F[9], ADA_F[7], ADA_F[5], ADA_F[3], ADA_F[1], 0.f};      // f[11 - 2k]
-    constexpr float B[7] = {ADA_F[10], ADA_F[8], ADA_F[6], ADA_F[4], ADA_F[2], ADA_F[0], 0.f};      // f[10 - 2k]
-    constexpr float BS[7] = {0.f, ADA_F[10], ADA_F[8], ADA_F[6], ADA_F[4], ADA_F[2], ADA_F[0]};     // f[12 - 2k]
-    const int np = n + m0 + m1, nu = 2 * np;
-    const double fl = floor(c);
-    const float t = (float)(c - fl);
-    const int x0 = (int)fl;
-    const float b0 = (x0 >= 0 && x0 < nu) ? 2.f * (1.f - t) : 0.f;
-    const float b1 = (x0 + 1 >= 0 && x0 + 1 < nu) ? 2.f * t : 0.f;
-    const bool odd = (x0 & 1) != 0;
-    ax.lo = (x0 - 5) >> 1;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        const int i = ax.lo + k;
-        const float w = b0 * (odd ? B[k] : A[k]) + b1 * (odd ? A[k] : BS[k]);
-        ax.w[k] = (i >= 0 && i < np) ? w : 0.f;
-        ax.idx[k] = ada_reflect(i, m0, n);
-    }
-}
-
-struct AdaGeo {
-    float g[6];
-    int mx0, my0, mx1, my1;
-};
-__device__ __forceinline__ AdaGeo ada_geo(const float* __restrict__ G, const int* __restrict__ margins, int n, int H, int W) {
-    AdaGeo q;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) q.g[i] = G[(long)n * 9 + i];
-    q.mx0 = min(max(margins[0], 0), W - 1), q.my0 = min(max(margins[1], 0), H - 1);
-    q.mx1 = min(max(margins[2], 0), W - 1), q.my1 = min(max(margins[3], 0), H - 1);
-    return q;
-}
-
 // The bounding box, in padded-image indices, of everything the samples of a tile read: the coordinate is affine in the sample index, so the
 // tile's corner samples bound it.  One index of slack on each side, clipped to the padded image (weights are zero outside it); a box of
 // more than `cap` entries is returned empty.
@@ -409,6 +348,8 @@ __global__ __launch_bounds__(ADA_THREADS) void ada_apply_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------------------------------------ adjoint
+// REST: launched behind the gather route, for the samples it left alone (it wrote zeros there); a workgroup of any other sample returns.
+template <bool REST>
 __global__ __launch_bounds__(ADA_THREADS) void ada_adjoint_kernel(const float* __restrict__ gy, const float* __restrict__ G,
                                                                   const float* __restrict__ Cm, const int* __restrict__ margins,
                                                                   float* __restrict__ gx, int C, int H, int W, int cf, int cc) {
@@ -419,6 +360,7 @@ __global__ __launch_bounds__(ADA_THREADS) void ada_adjoint_kernel(const float* _
     const int n = (int)blockIdx.z / C, ch = (int)blockIdx.z - n * C;
     const int ty0 = (int)blockIdx.y * ADA_T, tx0 = (int)blockIdx.x * ADA_T, tid = threadIdx.x;
     const AdaGeo q = ada_geo(G, margins, n, H, W);
+    if (REST && ada_gather_inverse(q, H, W).ok) return;
     const long plane = (long)H * W;
     {   // the cotangent tile of this source channel, colour matrix transposed
         const int oy = tid / ADA_T, ox = tid - oy * ADA_T;
@@ -502,6 +444,187 @@ __global__ __launch_bounds__(ADA_THREADS) void ada_adjoint_kernel(const float* _
     }
 }
 
+// ------------------------------------------------------------------------------------------------ adjoint, gather form (no atomics)
+constexpr int ADA_GT = 32;                     // samples per axis of one workgroup of the cotangent kernel
+constexpr int ADA_GO = ADA_GT / 2 + 5;         // outputs per axis that feed them
+
+// Launch 1: gs = D^T C^T gy on the sample grid, ws [N, C, 2H + 10, 2W + 10] (element [j - 1] is sample index j): the colour matrix
+// transposed while the cotangent is read, then gs[j] = sum_t f[t] gy[(j - 1 - t) / 2] over the t of the parity of j - 1, along x, then y.
+// A workgroup owns 32 x 32 samples of one (sample, channel) and stores each once.  Samples the gather does not take are skipped.
+__global__ __launch_bounds__(ADA_THREADS) void ada_cot_kernel(const float* __restrict__ gy, const float* __restrict__ G,
+                                                              const float* __restrict__ Cm, const int* __restrict__ margins,
+                                                              float* __restrict__ ws, int C, int H, int W, int cf, int cc) {
+    __shared__ float gt[ADA_GO][ADA_GO + 1];
+    __shared__ float ht[ADA_GO][ADA_GT + 1];
+    const int n = (int)blockIdx.z / C, ch = (int)blockIdx.z - n * C, tid = threadIdx.x;
+    if (!ada_gather_inverse(ada_geo(G, margins, n, H, W), H, W).ok) return;
+    const int oy0 = (int)blockIdx.y * (ADA_GT / 2) - 5, ox0 = (int)blockIdx.x * (ADA_GT / 2) - 5;
+    const long plane = (long)H * W;
+    for (int e = tid; e < ADA_GO * ADA_GO; e += ADA_THREADS) {
+        const int ly = e / ADA_GO, lx = e - ly * ADA_GO;
+        const int oy = oy0 + ly, ox = ox0 + lx;
+        float v = 0.f;
+        if (oy >= 0 && oy < H && ox >= 0 && ox < W) {
+            const long at = (long)oy * W + ox;
+            const float* M = Cm + (long)n * 12;
+            if (cc == 3 && ch >= cf && ch < cf + 3) {
+                const float* b = gy + ((long)n * C + cf) * plane + at;
+                const int j = ch - cf;
+                v = M[j] * b[0] + M[4 + j] * b[plane] + M[8 + j] * b[2 * plane];
+            } else if (cc == 1 && ch == cf) {
+                const float sc = (M[0] + M[1] + M[2] + M[4] + M[5] + M[6] + M[8] + M[9] + M[10]) * (1.f / 3.f);
+                v = sc * gy[((long)n * C + ch) * plane + at];
+            } else {
+                v = gy[((long)n * C + ch) * plane + at];
+            }
+        }
+        gt[ly][lx] = v;
+    }
+    __syncthreads();
+    for (int e = tid; e < ADA_GO * ADA_GT; e += ADA_THREADS) {         // along x: output (s - t) / 2 is local (s - t) / 2 + 5
+        const int ly = e / ADA_GT, sx = e - ly * ADA_GT;
+        float s = 0.f;
+#pragma unroll
+        for (int h = 0; h < 6; ++h) {
+            const int t = (sx & 1) + 2 * h;
+            s = __builtin_fmaf(ADA_F[t], gt[ly][((sx - t) >> 1) + 5], s);
+        }
+        ht[ly][sx] = s;
+    }
+    __syncthreads();
+    const int SH = 2 * H + 10, SW = 2 * W + 10;
+    float* out = ws + ((long)n * C + ch) * ((long)SH * SW);
+    for (int e = tid; e < ADA_GT * ADA_GT; e += ADA_THREADS) {         // along y
+        const int sy = e / ADA_GT, sx = e - sy * ADA_GT;
+        float s = 0.f;
+#pragma unroll
+        for (int h = 0; h < 6; ++h) {
+            const int t = (sy & 1) + 2 * h;
+            s = __builtin_fmaf(ADA_F[t], ht[((sy - t) >> 1) + 5][sx], s);
+        }
+        const int gy_ = (int)blockIdx.y * ADA_GT + sy, gx_ = (int)blockIdx.x * ADA_GT + sx;
+        if (gy_ < SH && gx_ < SW) out[(long)gy_ * SW + gx_] = s;
+    }
+}
+
+// One axis of one reflect image of a 16-wide source tile.  Source index y has the padded preimages m0 + y (img 0), m0 - y for y >= 1
+// (img 1) and m0 + 2 (n - 1) - y for y <= n - 2 (img 2), each where it lies inside [0, n + m0 + m1).
+struct AdaImage {
+    int base, sgn;       // padded index of local l: base + sgn * l
+    int imin;            // padded index of row 0 of the LDS tile (the smallest of the 16)
+    int p0, p1;          // the padded indices that are preimages, [p0, p1]; p0 > p1: none
+};
+__device__ __forceinline__ bool ada_image_valid(int img, int y, int pi, int n, int np) {
+    return y < n && (img == 0 || (img == 1 && y >= 1 && pi >= 0) || (img == 2 && y <= n - 2 && pi < np));
+}
+__device__ __forceinline__ AdaImage ada_image(int img, int t0, int m0, int n, int np) {
+    AdaImage a;
+    a.sgn = img == 0 ? 1 : -1;
+    a.base = (img == 2 ? m0 + 2 * (n - 1) : m0) + a.sgn * t0;
+    a.imin = a.sgn > 0 ? a.base : a.base - (ADA_T - 1);
+    a.p0 = 1 << 30, a.p1 = -(1 << 30);
+    for (int l = 0; l < ADA_T; ++l) {
+        const int pi = a.base + a.sgn * l;
+        if (ada_image_valid(img, t0 + l, pi, n, np)) a.p0 = min(a.p0, pi), a.p1 = max(a.p1, pi);
+    }
+    return a;
+}
+
+// Launch 2: gx = P^T U^T S^T gs.  A workgroup owns a 16 x 16 tile of the source image of one sample and up to ADA_CH channels.  For each
+// of the (at most 3 x 3) reflect images of the tile, in a fixed order: gather gU on the 42 x 42 upsampled pixels the image's padded pixels
+// read (every candidate sample of the pixel's window, in index order, evaluated with the forward's ada_coord: it contributes 2 (1 - t) or
+// 2 t per axis according to floor(c) = v or v - 1), U^T along y, then along x, from LDS, and the fold into per-thread accumulators.  One
+// store; every sum is float64 in a fixed order.  A sample the gather does not take (ada_gather_inverse) gets zeros.
+__global__ __launch_bounds__(ADA_THREADS) void ada_gather_kernel(const float* __restrict__ ws, const float* __restrict__ G,
+                                                                 const int* __restrict__ margins, float* __restrict__ gx, int C, int H,
+                                                                 int W) {
+    __shared__ double gu[ADA_CH][ADA_S][ADA_SP];
+    __shared__ double mid[ADA_CH][ADA_T][ADA_SP];
+    const int groups = (C + ADA_CH - 1) / ADA_CH;
+    const int n = (int)blockIdx.z / groups, c0 = ((int)blockIdx.z - n * groups) * ADA_CH, nch = min(ADA_CH, C - c0);
+    const int ty0 = (int)blockIdx.y * ADA_T, tx0 = (int)blockIdx.x * ADA_T, tid = threadIdx.x;
+    const int yl = tid / ADA_T, xl = tid - yl * ADA_T;
+    const AdaGeo q = ada_geo(G, margins, n, H, W);
+    const AdaInv m = ada_gather_inverse(q, H, W);
+    double acc[ADA_CH] = {0.0, 0.0, 0.0, 0.0};
+    if (m.ok) {
+        const int hp = H + q.my0 + q.my1, wp = W + q.mx0 + q.mx1, SW = 2 * W + 10;
+        const long splane = (long)(2 * H + 10) * SW;
+        const float* src[ADA_CH];
+#pragma unroll
+        for (int k = 0; k < ADA_CH; ++k) src[k] = ws + ((long)n * C + c0 + min(k, nch - 1)) * splane;
+        for (int iy = 0; iy < 3; ++iy) {
+            const AdaImage ay = ada_image(iy, ty0, q.my0, H, hp);
+            if (ay.p0 > ay.p1) continue;
+            for (int ix = 0; ix < 3; ++ix) {
+                const AdaImage ax = ada_image(ix, tx0, q.mx0, W, wp);
+                if (ax.p0 > ax.p1) continue;
+                for (int e = tid; e < ADA_S * ADA_S; e += ADA_THREADS) {
+                    const int uy = e / ADA_S, ux = e - uy * ADA_S;
+                    const int vy = 2 * ay.imin - 5 + uy, vx = 2 * ax.imin - 5 + ux;
+                    double a[ADA_CH] = {0.0, 0.0, 0.0, 0.0};
+                    if (vy >= max(0, 2 * ay.p0 - 5) && vy <= min(2 * hp - 1, 2 * ay.p1 + 6) && vx >= max(0, 2 * ax.p0 - 5) &&
+                        vx <= min(2 * wp - 1, 2 * ax.p1 + 6)) {
+                        int jx0, jx1, jy0, jy1;
+                        ada_gather_window(m, vx, vy, H, W, jx0, jx1, jy0, jy1);
+                        for (int jy = jy0; jy <= jy1; ++jy) {
+                            for (int jx = jx0; jx <= jx1; ++jx) {
+                                const double cx = ada_coord(jx, jy, q.g[0], q.g[1], q.g[2], W, H, q.mx0, q.mx1);
+                                const double fx = floor(cx);
+                                const int dx = vx - (int)fx;
+                                if (dx != 0 && dx != 1) continue;
+                                const double cy = ada_coord(jy, jx, q.g[4], q.g[3], q.g[5], H, W, q.my0, q.my1);
+                                const double fy = floor(cy);
+                                const int dy = vy - (int)fy;
+                                if (dy != 0 && dy != 1) continue;
+                                const float tx = (float)(cx - fx), ty = (float)(cy - fy);          // the forward's weights
+                                const float wx = dx == 0 ? 2.f * (1.f - tx) : 2.f * tx, wy = dy == 0 ? 2.f * (1.f - ty) : 2.f * ty;
+                                const double w = (double)wx * (double)wy;
+                                const long at = (long)(jy - 1) * SW + (jx - 1);
+#pragma unroll
+                                for (int k = 0; k < ADA_CH; ++k)
+                                    if (k < nch) a[k] += w * (double)src[k][at];
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int k = 0; k < ADA_CH; ++k) gu[k][uy][ux] = a[k];
+                }
+                __syncthreads();
+                for (int e = tid; e < ADA_T * ADA_S; e += ADA_THREADS) {       // U^T along y: gP[i] = sum_o gU[o] f[o - 2 i + 5]
+                    const int ly = e / ADA_S, ux = e - ly * ADA_S;
+#pragma unroll
+                    for (int k = 0; k < ADA_CH; ++k) {
+                        double s = 0.0;
+#pragma unroll
+                        for (int t = 0; t < 12; ++t) s += gu[k][2 * ly + t][ux] * (double)ADA_F[t];
+                        mid[k][ly][ux] = s;
+                    }
+                }
+                __syncthreads();
+                {   // along x, for this thread's source pixel, and the fold
+                    const int ly = ay.sgn > 0 ? yl : ADA_T - 1 - yl, lx = ax.sgn > 0 ? xl : ADA_T - 1 - xl;
+                    if (ada_image_valid(iy, ty0 + yl, ay.base + ay.sgn * yl, H, hp) && ada_image_valid(ix, tx0 + xl, ax.base + ax.sgn * xl, W, wp)) {
+#pragma unroll
+                        for (int k = 0; k < ADA_CH; ++k) {
+                            double s = 0.0;
+#pragma unroll
+                            for (int t = 0; t < 12; ++t) s += mid[k][ly][2 * lx + t] * (double)ADA_F[t];
+                            acc[k] += s;
+                        }
+                    }
+                }
+                // (the next image's gather writes gu, which nobody reads any more; mid is written again only behind that gather's barrier)
+            }
+        }
+    }
+    if (ty0 + yl < H && tx0 + xl < W) {
+#pragma unroll
+        for (int k = 0; k < ADA_CH; ++k)
+            if (k < nch) gx[(((long)n * C + c0 + k) * H + ty0 + yl) * W + tx0 + xl] = (float)acc[k];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ colour alone (geometry off)
 template <bool ADJ>
 __global__ __launch_bounds__(ADA_THREADS) void ada_color_kernel(const float* __restrict__ x, const float* __restrict__ Cm,
@@ -579,8 +702,42 @@ extern "C" int shg_ada_apply_adjoint_f32(const float* gy, const float* G_inv, co
     const int cf = color_count ? color_first : 0;
     if (geom) {
         const dim3 grid(shg_cdiv(W, ADA_T), shg_cdiv(H, ADA_T), N * C);
-        hipLaunchKernelGGL(ada_adjoint_kernel, grid, dim3(ADA_THREADS), 0, (hipStream_t)stream, gy, G_inv, Cm, margins, gx, C, H, W, cf,
+        hipLaunchKernelGGL(ada_adjoint_kernel<false>, grid, dim3(ADA_THREADS), 0, (hipStream_t)stream, gy, G_inv, Cm, margins, gx, C, H, W, cf,
                            color_count);
+    } else {
+        const long plane = (long)H * W;
+        hipLaunchKernelGGL(ada_color_kernel<true>, dim3(shg_cdiv(plane, ADA_THREADS), N), dim3(ADA_THREADS), 0, (hipStream_t)stream, gy, Cm, gx,
+                           C, plane, cf, color_count, 0);
+    }
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}
+
+extern "C" long shg_ada_adjoint_gather_workspace_bytes(int N, int C, int H, int W) {
+    if (N < 1 || C < 1 || H < 1 || W < 1 || H > 16384 || W > 16384 || (long)N * C > 65535) return 0;
+    return (long)N * C * (2 * H + 10) * (2 * W + 10) * (long)sizeof(float);
+}
+
+extern "C" int shg_ada_apply_adjoint_gather_f32(const float* gy, const float* G_inv, const float* Cm, const int* margins, float* gx,
+                                                void* workspace, long workspace_bytes, int N, int C, int H, int W, int geom, int color_first,
+                                                int color_count, void* stream) {
+    const int rc = ada_check("ada_apply_adjoint_gather_f32", gy, G_inv, Cm, margins, gx, N, C, H, W, geom, color_first, color_count);
+    if (rc != SHG_OK) return rc;
+    const int cf = color_count ? color_first : 0;
+    if (geom) {
+        const long need = shg_ada_adjoint_gather_workspace_bytes(N, C, H, W);
+        SHG_CHECK_ARG(workspace && workspace_bytes >= need, "ada_apply_adjoint_gather_f32: the workspace must hold %ld bytes (got %s, %ld)", need,
+                      workspace ? "a pointer" : "null", workspace_bytes);
+        SHG_CHECK_ARG(workspace != (const void*)gy && workspace != (void*)gx, "ada_apply_adjoint_gather_f32: the workspace aliases an image");
+        const hipStream_t s = (hipStream_t)stream;
+        float* ws = (float*)workspace;
+        const dim3 cot(shg_cdiv(2 * W + 10, ADA_GT), shg_cdiv(2 * H + 10, ADA_GT), N * C);
+        hipLaunchKernelGGL(ada_cot_kernel, cot, dim3(ADA_THREADS), 0, s, gy, G_inv, Cm, margins, ws, C, H, W, cf, color_count);
+        const dim3 tiles(shg_cdiv(W, ADA_T), shg_cdiv(H, ADA_T), N * shg_cdiv(C, ADA_CH));
+        hipLaunchKernelGGL(ada_gather_kernel, tiles, dim3(ADA_THREADS), 0, s, (const float*)ws, G_inv, margins, gx, C, H, W);
+        // the samples the gather left alone (it wrote zeros): the scatter kernel, whose other workgroups return at once
+        const dim3 grid(shg_cdiv(W, ADA_T), shg_cdiv(H, ADA_T), N * C);
+        hipLaunchKernelGGL(ada_adjoint_kernel<true>, grid, dim3(ADA_THREADS), 0, s, gy, G_inv, Cm, margins, gx, C, H, W, cf, color_count);
     } else {
         const long plane = (long)H * W;
         hipLaunchKernelGGL(ada_color_kernel<true>, dim3(shg_cdiv(plane, ADA_THREADS), N), dim3(ADA_THREADS), 0, (hipStream_t)stream, gy, Cm, gx,

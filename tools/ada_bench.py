@@ -1,8 +1,11 @@
 """Times the ADA pipe (shgan_amd.ada) on the GPU: the fused forward and the adjoint against ADA's literal sequence written with torch's own
 operators in float32 on the same device (reflect pad -> zero insertion + conv2d -> affine_grid + grid_sample -> conv2d + stride -> colour
-matmul; its backward by torch autograd), and -- with ``--step`` -- Gmain + Dmain of BASELINE config 5 with and without the ``bgc`` pipe.
+matmul; its backward by torch autograd), and -- with ``--step`` -- Gmain + Dmain of BASELINE config 5 without a pipe, with the ``bgc`` pipe
+and with the ``bgc`` pipe on the deterministic (gather-form) adjoint.  The two adjoint routes are timed alternately, ``--rounds`` times
+each, in the same process and on the same draws: the scatter kernel with the zero fill of its output, the gather route as all of its
+launches (its workspace comes from the caching allocator, as in training).
 
-    python tools/ada_bench.py [--shapes 16x4x512x512,8x4x512x512] [--reps 20] [--warmup 5] [--step] [--train-batch 8] [--out FILE]
+    python tools/ada_bench.py [--shapes 16x4x512x512,8x4x512x512] [--reps 20] [--warmup 5] [--rounds 5] [--step] [--train-batch 8] [--out FILE]
 
 Both sides get the same matrices and the same margins (the yardstick is handed the integers: ADA's host read-back that sizes the pad is NOT
 in its time).  HIP events around ``reps`` back-to-back launches after ``warmup`` untimed ones; one JSON line per measurement."""
@@ -66,7 +69,7 @@ def torch_sequence(x, G_inv, Cm, margins, f, color):
     return torch.cat([x[:, :first], img.reshape(n, count, h, w), x[:, first + count:]], dim=1)
 
 
-def bench_ops(shape, reps, warmup, emit):
+def bench_ops(shape, reps, warmup, emit, rounds=5):
     from shgan_amd import ada
     n, c, h, w = shape
     dev = 'cuda:0'
@@ -92,6 +95,20 @@ def bench_ops(shape, reps, warmup, emit):
         t_ref_bwd = timed(lambda: torch.autograd.grad(yr, xr, wgt, retain_graph=True), max(reps // 4, 2), 2)
         (gref,) = torch.autograd.grad(yr, xr, wgt)
     gerr = float((ada.ada_apply_adjoint(wgt, G, Cm, margins, color) - gref).abs().max())
+    with torch.no_grad():
+        det = ada.ada_apply_adjoint(wgt, G, Cm, margins, color, deterministic=True)
+        det_err = float((det - gref).abs().max())
+        same_bits = bool(torch.equal(det, ada.ada_apply_adjoint(wgt, G, Cm, margins, color, deterministic=True)))
+        scatter, gather = [], []
+        for _ in range(rounds):
+            scatter.append(round(timed(lambda: ada.ada_apply_adjoint(wgt, G, Cm, margins, color), reps, warmup), 1))
+            gather.append(round(timed(lambda: ada.ada_apply_adjoint(wgt, G, Cm, margins, color, deterministic=True), reps, warmup), 1))
+    from shgan_amd import _lib
+    emit(dict(what='ada_adjoint_routes', shape=list(shape), margins=m, scatter_us=scatter, gather_us=gather,
+              scatter_median_us=sorted(scatter)[rounds // 2], gather_median_us=sorted(gather)[rounds // 2],
+              gather_over_scatter=round(sorted(gather)[rounds // 2] / sorted(scatter)[rounds // 2], 3),
+              workspace_bytes=int(_lib.get_lib().shg_ada_adjoint_gather_workspace_bytes(n, c, h, w)), max_abs_diff_gather=det_err,
+              gather_same_bits_twice=same_bits, readings=f'{rounds} x {reps} launches, alternating'))
     floor_bytes = 2 * n * c * h * w * 4
     emit(dict(what='ada_ops', shape=list(shape), margins=m, params_us=round(t_params, 1), forward_us=round(t_fwd, 1), adjoint_us=round(t_adj, 1),
               adjoint_includes='zero fill of gx', torch_forward_us=round(t_ref, 1), torch_backward_us=round(t_ref_bwd, 1),
@@ -104,14 +121,14 @@ def bench_step(batch, reps, warmup, emit):
     from shgan_amd import ada, configs, losses, train_stage as ts
     from shgan_amd.model_zoo import stylegan
     dev = 'cuda:0'
-    for spec in (None, 'bgc'):
+    for spec, det in ((None, False), ('bgc', False), ('bgc', True)):
         torch.manual_seed(1234)
         G = configs.seeded_init_(configs.build_generator(512), seed=0).to(dev).train().requires_grad_(False)
         D = stylegan.Discriminator(resolution=512, ic_n=4, ch_base=32768, ch_max=512, mbstd_group_size=4, mbstd_c_n=1).to(dev).train().requires_grad_(False)
         real = torch.rand(batch, 3, 512, 512, device=dev) * 2 - 1
         mask = (torch.rand(batch, 1, 512, 512, device=dev) < 0.7).float()
         real4 = torch.cat([mask - 0.5, real], dim=1)
-        pipe = ada.AugmentPipe(**ada.AUGPIPE_SPECS[spec]).to(dev) if spec else None
+        pipe = ada.AugmentPipe(**ada.AUGPIPE_SPECS[spec], deterministic=det).to(dev) if spec else None
         L = losses.InpaintingLoss(dev, G, D, composite_fake=True, noise_mode='random', style_mixing_prob=0.9, augment_pipe=pipe)
         kw = dict(lr=0.002, betas=(0.0, 0.99), eps=1e-8, capturable=True, fused=True)
         phases = [ph for ph in ts.make_phases(G, D, kw, kw, g_reg_interval=4, d_reg_interval=16) if ph.name in ('Gmain', 'Dmain')]
@@ -119,7 +136,7 @@ def bench_step(batch, reps, warmup, emit):
         for i in range(3):                                   # two eager runs per phase, then capture + first replay
             pg.run(real4, i)
         t = timed(lambda: pg.run(real4, 1), reps, warmup)
-        emit(dict(what='config5_Gmain+Dmain', batch=batch, pipe=spec, ms_per_step=round(t / 1e3, 2), graphs=sorted(pg.graphs), readings='single'))
+        emit(dict(what='config5_Gmain+Dmain', batch=batch, pipe=spec, deterministic=det, ms_per_step=round(t / 1e3, 2), graphs=sorted(pg.graphs), readings='single'))
         for ph in phases:
             if ph.sync is not None:
                 ph.sync.remove()
@@ -132,6 +149,7 @@ def main():
     ap.add_argument('--shapes', default='16x4x512x512,8x4x512x512')
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--step', action='store_true')
     ap.add_argument('--train-batch', type=int, default=8)
     ap.add_argument('--out', default=None)
@@ -146,7 +164,7 @@ def main():
             with open(a.out, 'w') as fh:
                 fh.write('\n'.join(lines) + '\n')
     for s in [v for v in a.shapes.split(',') if v]:
-        bench_ops(tuple(int(v) for v in s.split('x')), a.reps, a.warmup, emit)
+        bench_ops(tuple(int(v) for v in s.split('x')), a.reps, a.warmup, emit, a.rounds)
     if a.step:
         bench_step(a.train_batch, max(a.reps // 2, 3), 2, emit)
 
