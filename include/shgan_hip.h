@@ -11,6 +11,13 @@
  *   - return value 0 = ok, <0 = error (SHG_ERR_*); shg_last_error() gives the message
  *     (the reference raises RuntimeError from TORCH_CHECK / AT_CUDA_CHECK, upfirdn2d.cpp:19-36,92);
  *   - thread-safe for distinct streams; the error string is thread-local.
+ *
+ * Extents.  No entry point reads or writes a byte outside the extents stated for its arguments: a tensor
+ * argument is exactly the elements of the shape and strides given for it, a packed operand exactly what its
+ * `*_elems` / `*_bytes` function returns, and a workspace `ws` is touched only within
+ * [ws, ws + *_workspace_bytes(...)).  This holds for buffers without any allocator slack before or behind
+ * them: ragged last tiles, vector accesses, plane pitches, channel padding and split-K slices stay inside.
+ * tests/test_gpu_alloc_guard.py runs every entry point on buffers housed between poisoned guard bands.
  */
 #ifndef SHGAN_HIP_H
 #define SHGAN_HIP_H
