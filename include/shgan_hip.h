@@ -311,6 +311,21 @@ int shg_shu_split_adjoint_n_f32(const float* const* g, const long* g_batch_strid
 /* ---- A24: eval composite (lib/experiments/shgan_default.py:257-262): x4 [N,4,H,W], img [N,3,H,W] -> u8 [N,3,H,W]. */
 int shg_composite_u8(const float* x4, const float* img, uint8_t* out, int N, int H, int W, void* stream);
 
+/* ---- Pluralistic sampling: K completions per masked input (model_zoo/comodgan.py Generator.sample_many; csrc/plural.hip).
+ * Expansion: one launch writes dst[n*K + k] = src[n] (n < N, k < K) for every level of a table in DEVICE memory -- x_global and the
+ *   encoder's skip features, so that synthesis row n*K + k reads input n.  src holds N images of `bytes` bytes each, dst N*K of them;
+ *   any element type: a level moves in the widest unit of 16 / 8 / 4 / 2 / 1 bytes that divides `bytes` and both addresses.  A level
+ *   with a null pointer or bytes <= 0 is skipped.  max_bytes_per_image (>= the largest level) sizes the grid only.  K = 1 is a copy.
+ * Composite: x4 [N,4,H,W], img [N*K,3,H,W] -> u8 [N*K,3,H,W], shg_composite_u8's arithmetic and shape domain; row r takes the mask and
+ *   the known pixels of input r / K. */
+typedef struct {
+    const void* src;
+    void* dst;
+    long bytes; /* per image */
+} shg_expand_level;
+int shg_plural_expand(const shg_expand_level* levels, int n_levels, int N, int K, long max_bytes_per_image, void* stream);
+int shg_plural_composite_u8(const float* x4, const float* img, uint8_t* out, int N, int K, int H, int W, void* stream);
+
 /* ---- input hand-off of the eval loop (lib/experiments/shgan_default.py:267-274): x = cat([mask-0.5, real*mask]).
  * real [N,3,H,W] in [-1,1], mask [N,H,W] in {0,1} -> x [N,4,H,W]. */
 int shg_assemble_input_f32(const float* real, const float* mask, float* x, int N, int H, int W, void* stream);
@@ -442,6 +457,15 @@ int shg_lpips_conv1_f32(const void* x, const float* lut, float scale, float bias
 size_t shg_lpips_head_scratch_bytes(int B, int h, int w);
 int shg_lpips_head_f32(const float* fp, const float* fg, const float* w, int B, int C, int h, int wd, void* scratch, size_t scratch_bytes,
                        double* out, void* stream);
+/* Pair form of the head (sh-gan_amd/diversity.py): f [M,C,h,w], device tables ia, ib int32 [P], w [C] -> out[p] += the head's value for
+ *   the pair (f[ia[p]], f[ib[p]]), out float64 [P]; P <= 65535.  The arithmetic, the fixed summation order and the scratch layout are
+ *   shg_lpips_head_f32's: a pair's bits equal that entry point's on the two rows and depend neither on P nor on the pair's place in the
+ *   table; ia[p] == ib[p] adds exactly 0.  ia_host / ib_host: optional HOST copies of the tables (both or neither); with them an index
+ *   outside [0, M) is SHG_ERR_ARG and nothing is launched.  Without them (tables that exist on the device only) the kernel clamps such
+ *   an index into [0, M) and stores 1 into *err (device int, may be null; the caller zeroes it): no read leaves f in either case. */
+size_t shg_lpips_head_pairs_scratch_bytes(int P, int h, int w);
+int shg_lpips_head_pairs_f32(const float* f, const int* ia, const int* ib, const int* ia_host, const int* ib_host, const float* w, int M, int P,
+                             int C, int h, int wd, void* scratch, size_t scratch_bytes, double* out, int* err, void* stream);
 
 /* The scaling layer as a pass of its own, for a backbone whose first convolution is not conv1 above (net = 'vgg', sh-gan_amd/lpips.py):
  * x [B,3,H,W] uint8 (lut [256]) or float32 -> y [B,3,H,W] float32 = s(v), v and s as in conv1 (same float32 steps, same host arrays). */

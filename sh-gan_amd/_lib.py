@@ -42,6 +42,10 @@ class AdaTailConfig(ctypes.Structure):       # shg_ada_tail_config
                 ('cutout_size', c_f)]
 
 
+class ExpandLevel(ctypes.Structure):         # shg_expand_level
+    _fields_ = [('src', c_fp), ('dst', c_fp), ('bytes', c_l)]
+
+
 class IncConv(ctypes.Structure):             # shg_inc_conv_desc
     _fields_ = [('x', c_fp), ('w', c_fp), ('bias', c_fp), ('y', c_fp)] + [
         (n, c_i) for n in ('I', 'H', 'W', 'x_ctot', 'x_coff', 'O', 'kh', 'kw', 'sh', 'sw', 'ph', 'pw', 'OH', 'OW', 'y_ctot', 'y_coff', 'splitk')]
@@ -111,6 +115,8 @@ _SIGS = {
     'shg_shu_split_irfft2_n_f32': [c_fp, c_fp, c_pp, c_pp, ctypes.POINTER(c_l), c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_i), c_i, c_fp],
     'shg_shu_split_adjoint_n_f32': [c_pp, ctypes.POINTER(c_l), c_pp, c_fp, c_i, c_i, c_i, ctypes.POINTER(c_i), c_i, c_fp],
     'shg_composite_u8': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
+    'shg_plural_expand': [c_fp, c_i, c_i, c_i, c_l, c_fp],
+    'shg_plural_composite_u8': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
     'shg_assemble_input_f32': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_assemble_input_u8': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_conv_weight_prep_up_poly_f32': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp],
@@ -150,6 +156,9 @@ _SIGS = {
     'shg_lpips_conv1_f32': [c_fp, c_fp, c_f, c_f, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_lpips_head_scratch_bytes': [c_i] * 3,
     'shg_lpips_head_f32': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, ctypes.c_size_t, c_fp, c_fp],
+    'shg_lpips_head_pairs_scratch_bytes': [c_i] * 3,
+    'shg_lpips_head_pairs_f32': [c_fp, c_fp, c_fp, ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, ctypes.c_size_t, c_fp, c_fp,
+                                 c_fp],
     'shg_lpips_scaling_f32': [c_fp, c_fp, c_f, c_f, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp, c_i, c_i, c_i, c_fp],
     'shg_ppl_frontend_f32': [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp],
     'shg_adam_tick': [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp],
@@ -223,6 +232,7 @@ def get_lib():
     lib.shg_conv2d_wgrad_f16_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_image_metrics_scratch_bytes.restype = ctypes.c_size_t
     lib.shg_lpips_head_scratch_bytes.restype = ctypes.c_size_t
+    lib.shg_lpips_head_pairs_scratch_bytes.restype = ctypes.c_size_t
     lib.shg_inception_conv_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_kid_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_pr_workspace_bytes.restype = ctypes.c_size_t

@@ -18,17 +18,21 @@ NUM_WS = {256: 14, 512: 16, 1024: 18}                    # comodgan.py:367-372
 
 SHU_KEYS = ('shu_channels', 'shu_df_freedom', 'shu_df_type', 'shu_input_res', 'shu_lowest_res', 'shu_tail_sigma_mult',
             'shu_gaussian_at_input_res')                  # the shu_* keys of configs/model/shgan.yaml
+SYNTHESIS_TYPES = ('comodgan_synthesis', 'comodgan_synthesis_plur')
 
 
 def model_cfg(name='shgan_g512', ch_base=32768, ch_max=512, w_dim=512, z_dim=512, w0_dim=1024, use_fp16_before_res=None,
-              use_fp16_after_res=None, shu=None):
+              use_fp16_after_res=None, shu=None, synthesis='comodgan_synthesis'):
     """Registry config (``type`` / ``args``) of a shipped generator; the width arguments exist for reduced-size tests.  The shipped
     configs are float32 (``use_fp16_*: null``, comodgan.yaml:27,46); ``use_fp16_before_res`` (encoder blocks above that resolution) /
     ``use_fp16_after_res`` (synthesis blocks above it) switch the reference's half-precision blocks on (BASELINE config 5).
     ``shu`` = dict of ``shu_*`` encoder arguments (the key names of shgan.yaml) that replace the shipped SHU geometry, e.g.
-    ``dict(shu_input_res=32, shu_lowest_res=8)``; the SHU constructor says which geometries the kernels take."""
+    ``dict(shu_input_res=32, shu_lowest_res=8)``; the SHU constructor says which geometries the kernels take.  ``synthesis`` =
+    'comodgan_synthesis' (shipped) or 'comodgan_synthesis_plur' (pluralistic inpainting: same arguments and state_dict)."""
     if name not in ('shgan_g256', 'shgan_g512', 'shgan_g1024'):            # configs/model/shgan.yaml:51-124
         raise KeyError(f'unknown model config {name!r} (shipped: shgan_g256, shgan_g512, shgan_g1024)')
+    if synthesis not in SYNTHESIS_TYPES:
+        raise KeyError(f'unknown synthesis network {synthesis!r} (known: {", ".join(SYNTHESIS_TYPES)})')
     res = int(name.split('_g')[1])
     mapping = dict(type='comodgan_mapping', args=dict(
         z_dim=z_dim, c_dim=0, w_dim=w_dim, num_ws=NUM_WS[res], num_layers=8, embed_features=None, layer_features=None,
@@ -44,7 +48,7 @@ def model_cfg(name='shgan_g512', ch_base=32768, ch_max=512, w_dim=512, z_dim=512
         if unknown:
             raise KeyError(f'unknown SHU config key(s) {unknown} (known: {", ".join(SHU_KEYS)})')
         encoder['args'].update(shu)
-    synthesis = dict(type='comodgan_synthesis', args=dict(
+    synthesis = dict(type=synthesis, args=dict(
         w_dim=w_dim, w0_dim=w0_dim, resolution=res, rgb_n=3, ch_base=ch_base, ch_max=ch_max, use_fp16_after_res=use_fp16_after_res,
         resample_filter=[1, 3, 3, 1], activation=ACT))
     return dict(type='comodgan_generator', args=dict(mapping=mapping, encoder=encoder, synthesis=synthesis))

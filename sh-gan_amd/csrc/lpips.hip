@@ -15,6 +15,9 @@
 //   cache: each map comes from memory once); a wave's 64 values are added in float64 by a fixed butterfly -> scratch[b][tile]; a second
 //   launch adds an image's tiles in a fixed order (float64) and adds the spatial mean to out[b].  No atomics: the same bits run to run
 //   and in any batch.  A pixel whose features are all zero gives 0 / (0 + 1e-10) = 0.
+// shg_lpips_head_pairs_f32: the same head for a table of P pairs (ia[p], ib[p]) of rows of ONE feature tensor f [M,C,h,w] -- the same
+//   per-tile function, the same butterfly, the same finish: a pair's bits are those of shg_lpips_head_f32 on (f[ia], f[ib]) and depend
+//   neither on P nor on the pair's place in the table.
 #include "shg_device.h"
 #include "../../include/shgan_hip.h"
 
@@ -150,13 +153,12 @@ __global__ __launch_bounds__(256) void lp_conv1_prep_kernel(const float* w, cons
     wp[e] = v;
 }
 
-__global__ __launch_bounds__(64) void lp_head_tile_kernel(const float* fp, const float* fg, const float* w, int C, int HW, double* part) {
-    const int lane = threadIdx.x, tile = blockIdx.x, b = blockIdx.y;
-    const int pix = tile * 64 + lane;
+// one 64-pixel tile of one (pred, gt) pair of maps: the wave's float64 sum of d over its pixels (the same value in every lane)
+__device__ __forceinline__ double lp_head_tile(const float* p, const float* g, const float* w, int C, int HW, int pix) {
     float d = 0.f;
     if (pix < HW) {
-        const float* p = fp + (long)b * C * HW + pix;
-        const float* g = fg + (long)b * C * HW + pix;
+        p += pix;
+        g += pix;
         float sp = 0.f, sg = 0.f;
         for (int c = 0; c < C; ++c) {
             const float u = p[(long)c * HW], v = g[(long)c * HW];
@@ -172,7 +174,28 @@ __global__ __launch_bounds__(64) void lp_head_tile_kernel(const float* fp, const
     double s = (double)d;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    return s;
+}
+
+__global__ __launch_bounds__(64) void lp_head_tile_kernel(const float* fp, const float* fg, const float* w, int C, int HW, double* part) {
+    const int lane = threadIdx.x, tile = blockIdx.x, b = blockIdx.y;
+    const double s = lp_head_tile(fp + (long)b * C * HW, fg + (long)b * C * HW, w, C, HW, tile * 64 + lane);
     if (lane == 0) part[(long)b * gridDim.x + tile] = s;
+}
+
+// the same tile for pair p of a table: both maps are rows of ONE feature tensor f [M,C,h,w].  An index outside [0, M) is clamped into
+// it (no read leaves f) and reported through *err (every reporter stores the same 1).
+__global__ __launch_bounds__(64) void lp_head_pairs_tile_kernel(const float* f, const int* ia, const int* ib, const float* w, int M, int C, int HW,
+                                                                double* part, int* err) {
+    const int lane = threadIdx.x, tile = blockIdx.x, p = blockIdx.y;
+    int a = ia[p], b = ib[p];
+    if (a < 0 || a >= M || b < 0 || b >= M) {
+        a = min(max(a, 0), M - 1);
+        b = min(max(b, 0), M - 1);
+        if (err && lane == 0 && tile == 0) *err = 1;
+    }
+    const double s = lp_head_tile(f + (long)a * C * HW, f + (long)b * C * HW, w, C, HW, tile * 64 + lane);
+    if (lane == 0) part[(long)p * gridDim.x + tile] = s;
 }
 
 __global__ __launch_bounds__(LP_HEAD_THREADS) void lp_head_finish_kernel(const double* part, int tiles, double inv_hw, double* out) {
@@ -241,6 +264,31 @@ extern "C" int shg_lpips_head_f32(const float* fp, const float* fg, const float*
     hipLaunchKernelGGL(lp_head_tile_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(64), 0, (hipStream_t)stream, fp, fg, w, C, (int)HW, part);
     SHG_CHECK_LAUNCH();
     hipLaunchKernelGGL(lp_head_finish_kernel, dim3(B), dim3(LP_HEAD_THREADS), 0, (hipStream_t)stream, part, (int)tiles, 1.0 / (double)HW, out);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}
+
+// Pair form of the head (diversity.py: the K(K-1)/2 pairs among the K samples of one input after ONE trunk pass over all of them).
+extern "C" size_t shg_lpips_head_pairs_scratch_bytes(int P, int h, int w) { return shg_lpips_head_scratch_bytes(P, h, w); }
+
+extern "C" int shg_lpips_head_pairs_f32(const float* f, const int* ia, const int* ib, const int* ia_host, const int* ib_host, const float* w, int M, int P,
+                                        int C, int h, int wd, void* scratch, size_t scratch_bytes, double* out, int* err, void* stream) {
+    SHG_CHECK_ARG(f && ia && ib && w && scratch && out, "lpips_head_pairs: null pointer");
+    SHG_CHECK_ARG((ia_host == nullptr) == (ib_host == nullptr), "lpips_head_pairs: pass both host tables or neither");
+    SHG_CHECK_ARG(M >= 1 && P >= 1 && C >= 1 && h >= 1 && wd >= 1, "lpips_head_pairs: M, P, C, h, w must be >= 1");
+    const long HW = (long)h * wd, tiles = (HW + 63) / 64;
+    SHG_CHECK_ARG(HW < (1L << 31) && P <= 65535, "lpips_head_pairs: feature map or pair table too large");
+    SHG_CHECK_ARG(scratch_bytes >= shg_lpips_head_pairs_scratch_bytes(P, h, wd), "lpips_head_pairs: scratch of %zu bytes is too small (%zu needed)",
+                  scratch_bytes, shg_lpips_head_pairs_scratch_bytes(P, h, wd));
+    if (ia_host)
+        for (int p = 0; p < P; ++p)
+            SHG_CHECK_ARG(ia_host[p] >= 0 && ia_host[p] < M && ib_host[p] >= 0 && ib_host[p] < M, "lpips_head_pairs: pair %d = (%d, %d) is outside [0, %d)", p,
+                          ia_host[p], ib_host[p], M);
+    double* part = reinterpret_cast<double*>(scratch);
+    hipLaunchKernelGGL(lp_head_pairs_tile_kernel, dim3((unsigned)tiles, (unsigned)P), dim3(64), 0, (hipStream_t)stream, f, ia, ib, w, M, C, (int)HW, part,
+                       err);
+    SHG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(lp_head_finish_kernel, dim3(P), dim3(LP_HEAD_THREADS), 0, (hipStream_t)stream, part, (int)tiles, 1.0 / (double)HW, out);
     SHG_CHECK_LAUNCH();
     return SHG_OK;
 }

