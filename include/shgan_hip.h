@@ -410,6 +410,21 @@ int shg_kid_sums_f64(const void* fake, const void* real, int is_f64, int n_f, in
                      void* workspace, size_t ws_bytes, double* out, void* stream);
 int shg_is_accumulate_f64(const float* probs, const int* split, double* acc, int B, int C, int num_splits, void* stream);
 
+/* ---- The streaming pass of the linear SVM behind U-IDS / P-IDS (CoModGAN's inception discriminative scores; sh-gan_amd/ids_score.py
+ * drives it; csrc/svm.hip).  q = X~^T phi(X~ v) with X~ = [X, 1] over the rows of x0 [n0,D] (label y0) and, optionally, x1 [n1,D]
+ * (label y1; null with n1 = 0): float32 rows at a pitch of ld0 / ld1 >= D floats, 1 <= D <= 4096, fewer than 2^31 rows, read ONCE, every
+ * product and sum in float64.  v [D+1] float64 (the intercept's entry last).  Per row t_i = x~_i . v, then
+ *   mode 0 (grad): z [n0+n1] float64 = t_i and a [n0+n1] bytes = [1 - y_i t_i > 0] are written; s_i = -2 C y_i a_i (1 - y_i t_i);
+ *   mode 1 (hv):   a is read; s_i = 2 C a_i t_i; z = t_i is written unless z is null.
+ * q [D+2] float64 = sum_i s_i x~_i (D+1 entries), then the loss sum_i a_i (1 - y_i t_i)^2 (mode 0; 0 in mode 1).  One partial of D+2
+ *   doubles per workgroup in `workspace` (shg_svm_pass_workspace_bytes; 0 for invalid sizes), added in a fixed order by a second launch:
+ *   no atomics, and the partition of the rows depends on (n0+n1, D) only -- the same bits on every run.  16-byte loads when D and both
+ *   pitches are multiples of 4 and both bases 16-byte aligned, dword loads otherwise; no load reaches past column D of a row.  Rows
+ *   4-byte, float64 operands 8-byte aligned.  C must be positive and finite, y0 and y1 finite (any values: +1 / -1 for the SVM). */
+size_t shg_svm_pass_workspace_bytes(long n0, long n1, int D);
+int shg_svm_pass_f64(const float* x0, long n0, long ld0, double y0, const float* x1, long n1, long ld1, double y1, int D, int mode, double C,
+                     const double* v, double* z, unsigned char* a, double* q, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- Improved precision / recall, `pr50k3_full` (lib/evaluator/stylegan_metrics/precision_recall.py:19-60; sh-gan_amd/
  * precision_recall.py drives them; csrc/pr.hip).  Rows are fp16 [n,D], 16-byte aligned, D >= 64 a multiple of 8.  d16(i,j) = the
  *   Euclidean distance as sqrt(max(0, |a|^2 + |b|^2 - 2 a.b)) -- a.b on the fp16 MFMA (exact products, fp32 sums), fp32 row norms --

@@ -16,6 +16,7 @@ c_fp = ctypes.c_void_p      # device pointers travel as void*
 c_i = ctypes.c_int
 c_f = ctypes.c_float
 c_l = ctypes.c_long
+c_d = ctypes.c_double
 c_pp = ctypes.POINTER(ctypes.c_void_p)
 
 
@@ -147,6 +148,8 @@ _SIGS = {
     'shg_kid_workspace_bytes': [c_i, c_i],
     'shg_kid_sums_f64': [c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_fp, ctypes.c_size_t, c_fp, c_fp],
     'shg_is_accumulate_f64': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
+    'shg_svm_pass_workspace_bytes': [c_l, c_l, c_i],
+    'shg_svm_pass_f64': [c_fp, c_l, c_l, c_d, c_fp, c_l, c_l, c_d, c_i, c_i, c_d, c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_size_t, c_fp],
     'shg_pr_workspace_bytes': [c_i, c_i, c_i],
     'shg_pr_radii_f16': [c_fp, c_i, c_i, c_i, c_fp, ctypes.c_size_t, c_fp, c_fp],
     'shg_pr_inside_f16': [c_fp, c_i, c_fp, c_i, c_i, c_fp, c_fp, ctypes.c_size_t, c_fp, c_fp],
@@ -236,6 +239,7 @@ def get_lib():
     lib.shg_inception_conv_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_kid_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_pr_workspace_bytes.restype = ctypes.c_size_t
+    lib.shg_svm_pass_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_ada_adjoint_gather_workspace_bytes.restype = c_l
     lib.shg_inception_packed_weight_elems.restype = c_l
     lib.shg_conv2d_f16_packed_weight_elems.restype = c_l

@@ -378,8 +378,8 @@ class EvalLoop:
     ``mask_kind`` = 'lama_thin' | 'lama_medium' | 'lama_thick' draws the LaMa masks of ``LamaMaskFormatter`` instead (masks.lama_masks: no
     hole-count read, so the host never waits for the device; ``hole_range`` is ignored).
 
-    The options are documented with their evaluators (evaluators.py): ``feature_fn`` / ``fid_real`` / ``kid`` / ``inception_score`` ->
-    DetectorStats, ``metrics`` / ``lpips`` -> PerImageColumns, ``pr`` -> PrecisionRecall.  ``evaluators`` maps 'detector' / 'columns' / 'pr'
+    The options are documented with their evaluators (evaluators.py): ``feature_fn`` / ``fid_real`` / ``kid`` / ``inception_score`` / ``pids_uids``
+    -> DetectorStats, ``metrics`` / ``lpips`` -> PerImageColumns, ``pr`` -> PrecisionRecall.  ``evaluators`` maps 'detector' / 'columns' / 'pr'
     to those whose options are present, in batch order; an absent option means no object, buffer or launch and None for its results.
 
     ``samples_per_input=K`` > 1 draws K completions per input (``G.sample_many``: one encoder pass per input).  Sample 0 uses the loop's usual z
@@ -395,7 +395,7 @@ class EvalLoop:
                  fid_dim=2048, latent_fn=None, device_masks=True, hole_range=(0, 1), keep_images=True, on_batch=None, step_fn=None,
                  fid_accumulate_fn=None, feeder_stream=False, timing=False, metrics=None, ssim_window=11, metrics_fn=None, fid_real=False,
                  lpips=None, kid=None, inception_score=None, pr=None, mask_kind='freeform', samples_per_input=1, diversity=None,
-                 keep_samples=False):
+                 keep_samples=False, pids_uids=None):
         from .datasets import DeviceFeeder
         self.timing, self.batch_done_events = timing, []      # timing: one timing event per finished batch (bench: steady-state rate)
         self.G, self.device, self.res = G, torch.device(device), int(resolution)
@@ -410,8 +410,8 @@ class EvalLoop:
         self.seen = 0
         self._extra_rng = None
         self.evaluators = {}
-        if feature_fn is not None or fid_real or kid or inception_score:
-            self.evaluators['detector'] = DetectorStats(self, feature_fn, fid_dim, fid_accumulate_fn, fid_real, kid, inception_score)
+        if feature_fn is not None or fid_real or kid or inception_score or pids_uids:
+            self.evaluators['detector'] = DetectorStats(self, feature_fn, fid_dim, fid_accumulate_fn, fid_real, kid, inception_score, pids_uids)
         if metrics or lpips is not None:
             self.evaluators['columns'] = PerImageColumns(self, metrics, ssim_window, metrics_fn, lpips)
         if pr:
@@ -508,9 +508,9 @@ class EvalLoop:
 
     def gather(self):
         """-> (uint8 images [n_items,3,R,R] in dataset order on the device, FidStats summed over the ranks | None), and every evaluator's result.
-        One collective per result that is on: images all-gather, fake and real moments all-reduce, metrics columns all-gather, KID fake / real and
-        precision / recall fake / real all-gathers, Inception Score all-reduce, diversity all-gather, in this order on every rank (each must have run its
-        whole shard)."""
+        One collective per result that is on: images all-gather, fake and real moments all-reduce, metrics columns all-gather, KID fake / real (the
+        rows P-IDS / U-IDS use too) and precision / recall fake / real all-gathers, Inception Score all-reduce, diversity all-gather, in this order
+        on every rank (each must have run its whole shard)."""
         if self.seen != len(self.ids):
             raise ValueError(f'EvalLoop.gather: {self.seen} of {len(self.ids)} items of this rank\'s shard were processed')
         collect = Collective(self.device, self.n_items, self.world)
@@ -535,6 +535,7 @@ class EvalLoop:
     fid_value = _value_of('detector', 'fid_value', 'fid_real=True, a feature_fn')
     kid_value = _value_of('detector', 'kid_value', 'kid=True (or its options)')
     is_value = _value_of('detector', 'is_value', 'inception_score=dict(...)')          # -> (mean, std)
+    ids_value = _value_of('detector', 'ids_value', 'pids_uids=True (or its options), fid_real=True')      # -> (U-IDS, P-IDS)
     pr_value = _value_of('pr', 'pr_value', 'pr=dict(detector=...)')                    # -> (precision, recall)
     diversity_value = _value_of('diversity', 'diversity_value', 'samples_per_input=K > 1, diversity=net')
 

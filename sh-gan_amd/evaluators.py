@@ -3,6 +3,7 @@ real, k0)`` on the batch's stream (``out``: uint8 composite of this rank's items
 import torch
 
 from .fid_stats import FidStats, fid_from_stats
+from .ids_score import ids_from_features
 from .image_metrics import MetricsAccumulator, finish_metrics
 from .inception_score import is_accumulate, is_from_accumulator, new_accumulator, split_of
 from .kid import kid_from_features
@@ -88,15 +89,20 @@ class DetectorStats:
     ``[num_splits, C + 2]`` accumulator (inception_score.py here; an image's split follows its dataset position, padded duplicates are skipped).
     ``C`` is ``feature_fn.num_classes`` or the dict's ``num_classes``; ``no_output_bias`` (default True, as the reference) is passed on when given;
     ``accumulate_fn(acc, probs, splits)`` replaces the kernel (CPU tests).  ``finish_is`` all-reduces the streams' sum once (``is_parts.sum``);
-    ``is_value()`` -> (mean, std) over the splits.  A ``*_value()`` is None until its option is on and finished."""
+    ``is_value()`` -> (mean, std) over the splits.  ``pids_uids=True`` or ``pids_uids=dict(C=1.0, tol=1e-9, max_newton=100)`` adds CoModGAN's
+    inception discriminative scores (ids_score.py; needs ``fid_real=True``: fake i is the completion of real i).  It keeps the feature rows in the
+    two per-rank buffers KID keeps -- one pair of buffers and one pair of all-gathers (``finish_kid``) whether one or both options are on, so
+    ``kid_features`` is set by either, while ``kid_value()`` stays None without ``kid`` -- and ``ids_value()`` -> (U-IDS, P-IDS) fits the linear
+    SVM on this device from the gathered rows (like ``pr_value()``, not sharded over the ranks; ``pass_fn`` in the dict replaces the kernel: CPU
+    tests).  A ``*_value()`` is None until its option is on and finished."""
 
-    def __init__(self, shard, feature_fn, fid_dim=2048, accumulate_fn=None, fid_real=False, kid=None, inception_score=None):
+    def __init__(self, shard, feature_fn, fid_dim=2048, accumulate_fn=None, fid_real=False, kid=None, inception_score=None, pids_uids=None):
         if fid_real and feature_fn is None:
             raise ValueError('EvalLoop: fid_real needs a feature_fn (the detector)')
         self.shard, self.feature_fn, self.needs_real, n_local = shard, feature_fn, bool(fid_real), len(shard.ids)
         self.fake, self.real = (PerStream((lambda: FidStats(fid_dim, device=shard.device, accumulate_fn=accumulate_fn)) if on else None,
                                           shard.device, add=lambda into, part: into.S.add_(part.S)) for on in (True, fid_real))
-        self.kid_opts = self.kid_local = self.kid_features = self.is_opts = self.is_splits = None
+        self.kid_opts = self.kid_local = self.kid_features = self.is_opts = self.is_splits = self.ids_opts = None
         if kid:
             if feature_fn is None or not fid_real:
                 raise ValueError('EvalLoop: kid needs a feature_fn (the detector) and fid_real=True (the real side\'s features)')
@@ -104,6 +110,14 @@ class DetectorStats:
             unknown = set(self.kid_opts) - {'num_subsets', 'max_subset_size', 'seed', 'sums_fn'}
             if unknown:
                 raise ValueError(f'EvalLoop: unknown kid option(s) {sorted(unknown)}')
+        if pids_uids:
+            if feature_fn is None or not fid_real:
+                raise ValueError('EvalLoop: pids_uids needs a feature_fn (the detector) and fid_real=True (the real side\'s features)')
+            self.ids_opts = dict(pids_uids) if isinstance(pids_uids, dict) else {}
+            unknown = set(self.ids_opts) - {'C', 'tol', 'max_newton', 'pass_fn'}
+            if unknown:
+                raise ValueError(f'EvalLoop: unknown pids_uids option(s) {sorted(unknown)}')
+        if kid or pids_uids:                # one pair of row buffers serves both
             self.kid_local = tuple(torch.zeros((n_local, fid_dim), dtype=torch.float32, device=shard.device) for _ in range(2))
         self.is_parts = PerStream((lambda: new_accumulator(self.is_opts['num_splits'], self.is_opts['num_classes'], shard.device))
                                   if inception_score else None, shard.device)
@@ -160,7 +174,15 @@ class DetectorStats:
         return fid_from_stats(*fake.mean_cov()[1:], *real.mean_cov()[1:]) if fake is not None and real is not None else None
 
     def kid_value(self):
-        return kid_from_features(*(t.contiguous() for t in self.kid_features), **self.kid_opts) if self.kid_features is not None else None
+        on = self.kid_opts is not None and self.kid_features is not None
+        return kid_from_features(*(t.contiguous() for t in self.kid_features), **self.kid_opts) if on else None
+
+    def ids_value(self):
+        if self.ids_opts is None or self.kid_features is None:
+            return None
+        fake, real = (t.contiguous() for t in self.kid_features)
+        res = ids_from_features(real, fake, **self.ids_opts)
+        return res['uids'], res['pids']
 
     def is_value(self):
         return is_from_accumulator(self.is_parts.sum) if self.is_parts.sum is not None else None
