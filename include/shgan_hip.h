@@ -425,6 +425,20 @@ size_t shg_svm_pass_workspace_bytes(long n0, long n1, int D);
 int shg_svm_pass_f64(const float* x0, long n0, long ld0, double y0, const float* x1, long n1, long ld1, double y1, int D, int mode, double C,
                      const double* v, double* z, unsigned char* a, double* q, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- Square float64 GEMM on the fp64 MFMA, the device tail of FID (sh-gan_amd/fid_stats.py drives it; csrc/gemm_f64.hip).
+ * shg_gemm_f64: C[b] = alpha A[b] B[b] + beta_diag I for b < batch (1..65535): n x n float64 (1 <= n <= 46336), row-major at pitches
+ *   lda, ldb, ldc >= n doubles; entry b of an operand starts stride_x * b doubles after entry 0 (any sign, 0 shares an input; stride_c
+ *   != 0 when batch > 1).  C must not overlap A or B.  128 x 128 tiles of C, K staged through LDS in chunks of 16; any n: loads outside
+ *   the matrices read as 0, nothing beside C[:n,:n] is written.  16-byte loads when A, B are 16-byte aligned and lda, ldb and (batch > 1)
+ *   stride_a, stride_b are even, 8-byte loads otherwise: the same bits either way.  Operands 8-byte aligned.
+ *   partials: NULL, or [batch][2][shg_gemm_f64_tiles(n)] doubles: per tile (row-major over the tile grid) the sum of the diagonal
+ *   entries and the sum of the squared entries of C as stored; adding a row in a fixed order gives tr C[b] and |C[b]|_F^2.  No atomics:
+ *   the same bits on every run.
+ * shg_gemm_f64_tiles(n): ceil(n / 128)^2; 0 for an n that is not served. */
+int shg_gemm_f64_tiles(int n);
+int shg_gemm_f64(const double* A, const double* B, double* C, int n, long lda, long ldb, long ldc, double alpha, double beta_diag, int batch,
+                 long stride_a, long stride_b, long stride_c, double* partials, void* stream);
+
 /* ---- Improved precision / recall, `pr50k3_full` (lib/evaluator/stylegan_metrics/precision_recall.py:19-60; sh-gan_amd/
  * precision_recall.py drives them; csrc/pr.hip).  Rows are fp16 [n,D], 16-byte aligned, D >= 64 a multiple of 8.  d16(i,j) = the
  *   Euclidean distance as sqrt(max(0, |a|^2 + |b|^2 - 2 a.b)) -- a.b on the fp16 MFMA (exact products, fp32 sums), fp32 row norms --

@@ -150,6 +150,8 @@ _SIGS = {
     'shg_is_accumulate_f64': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
     'shg_svm_pass_workspace_bytes': [c_l, c_l, c_i],
     'shg_svm_pass_f64': [c_fp, c_l, c_l, c_d, c_fp, c_l, c_l, c_d, c_i, c_i, c_d, c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_size_t, c_fp],
+    'shg_gemm_f64_tiles': [c_i],
+    'shg_gemm_f64': [c_fp, c_fp, c_fp, c_i, c_l, c_l, c_l, c_d, c_d, c_i, c_l, c_l, c_l, c_fp, c_fp],
     'shg_pr_workspace_bytes': [c_i, c_i, c_i],
     'shg_pr_radii_f16': [c_fp, c_i, c_i, c_i, c_fp, ctypes.c_size_t, c_fp, c_fp],
     'shg_pr_inside_f16': [c_fp, c_i, c_fp, c_i, c_i, c_fp, c_fp, ctypes.c_size_t, c_fp, c_fp],

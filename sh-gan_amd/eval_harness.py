@@ -10,7 +10,7 @@ import torch
 
 from . import kernels
 from .data import DistributedSampler, RandomMask, zipzap_arrange
-from .evaluators import Collective, DetectorStats, Diversity, PerImageColumns, PrecisionRecall, zipzap_device  # noqa: F401 (zipzap_device: re-exported)
+from .evaluators import Collective, DetectorStats, Diversity, PerImageColumns, PrecisionRecall, check_fid_tail, zipzap_device  # noqa: F401 (zipzap_device: re-exported)
 
 
 def assemble_input(real, mask):
@@ -379,7 +379,7 @@ class EvalLoop:
     hole-count read, so the host never waits for the device; ``hole_range`` is ignored).
 
     The options are documented with their evaluators (evaluators.py): ``feature_fn`` / ``fid_real`` / ``kid`` / ``inception_score`` / ``pids_uids``
-    -> DetectorStats, ``metrics`` / ``lpips`` -> PerImageColumns, ``pr`` -> PrecisionRecall.  ``evaluators`` maps 'detector' / 'columns' / 'pr'
+    / ``fid_tail`` -> DetectorStats, ``metrics`` / ``lpips`` -> PerImageColumns, ``pr`` -> PrecisionRecall.  ``evaluators`` maps 'detector' / 'columns' / 'pr'
     to those whose options are present, in batch order; an absent option means no object, buffer or launch and None for its results.
 
     ``samples_per_input=K`` > 1 draws K completions per input (``G.sample_many``: one encoder pass per input).  Sample 0 uses the loop's usual z
@@ -395,8 +395,9 @@ class EvalLoop:
                  fid_dim=2048, latent_fn=None, device_masks=True, hole_range=(0, 1), keep_images=True, on_batch=None, step_fn=None,
                  fid_accumulate_fn=None, feeder_stream=False, timing=False, metrics=None, ssim_window=11, metrics_fn=None, fid_real=False,
                  lpips=None, kid=None, inception_score=None, pr=None, mask_kind='freeform', samples_per_input=1, diversity=None,
-                 keep_samples=False, pids_uids=None):
+                 keep_samples=False, pids_uids=None, fid_tail='host'):
         from .datasets import DeviceFeeder
+        check_fid_tail(fid_tail)            # (checked with or without a detector)
         self.timing, self.batch_done_events = timing, []      # timing: one timing event per finished batch (bench: steady-state rate)
         self.G, self.device, self.res = G, torch.device(device), int(resolution)
         self.n_items, self.rank, self.world = int(n_items), int(rank), int(world)
@@ -411,7 +412,8 @@ class EvalLoop:
         self._extra_rng = None
         self.evaluators = {}
         if feature_fn is not None or fid_real or kid or inception_score or pids_uids:
-            self.evaluators['detector'] = DetectorStats(self, feature_fn, fid_dim, fid_accumulate_fn, fid_real, kid, inception_score, pids_uids)
+            self.evaluators['detector'] = DetectorStats(self, feature_fn, fid_dim, fid_accumulate_fn, fid_real, kid, inception_score, pids_uids,
+                                                         fid_tail)
         if metrics or lpips is not None:
             self.evaluators['columns'] = PerImageColumns(self, metrics, ssim_window, metrics_fn, lpips)
         if pr:
@@ -441,6 +443,7 @@ class EvalLoop:
             return cols
         return {**(cols or {}), 'diversity': float(div.mean()), 'diversity_per_image': div}
     kid_features, is_acc = _of('detector', 'kid_features'), _of('detector', 'is_parts.sum')
+    fid_tail_info = _of('detector', 'fid_tail_info')      # the dict of the last fid_value() with fid_tail='device'
     pr_opts, pr_features = _of('pr', 'pr_opts'), _of('pr', 'pr_features')
 
     def run(self, loader):

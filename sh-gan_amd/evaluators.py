@@ -2,7 +2,7 @@
 real, k0)`` on the batch's stream (``out``: uint8 composite of this rank's items k0 .. k0+B-1), ``finish(collect)`` from ``gather`` and value."""
 import torch
 
-from .fid_stats import FidStats, fid_from_stats
+from .fid_stats import FidStats, fid_from_stats, frechet_device
 from .ids_score import ids_from_features
 from .image_metrics import MetricsAccumulator, finish_metrics
 from .inception_score import is_accumulate, is_from_accumulator, new_accumulator, split_of
@@ -74,6 +74,18 @@ class PerStream:
         return self.sum
 
 
+def check_fid_tail(fid_tail):
+    """'host' | 'device' | dict(tol=, max_iter=, matmul_fn=) (= 'device' with options) -> (mode, options); anything else is a ValueError."""
+    if isinstance(fid_tail, dict):
+        unknown = set(fid_tail) - {'tol', 'max_iter', 'matmul_fn'}
+        if unknown:
+            raise ValueError(f'EvalLoop: unknown fid_tail option(s) {sorted(unknown)}')
+        return 'device', dict(fid_tail)
+    if fid_tail not in ('host', 'device'):
+        raise ValueError(f"EvalLoop: fid_tail must be 'host' or 'device' (or a dict of frechet_device options), got {fid_tail!r}")
+    return fid_tail, {}
+
+
 class DetectorStats:
     """Everything that hangs off ``feature_fn``, the detector hand-off of eva_fid.py:194-206 (``shard``: the EvalLoop), one detector run per side per
     batch.  Per batch ``feature_fn(images)`` -> fp64 moments on the device (fid_stats.FidStats; padded duplicates weigh 0).  The moment kernel
@@ -94,11 +106,17 @@ class DetectorStats:
     two per-rank buffers KID keeps -- one pair of buffers and one pair of all-gathers (``finish_kid``) whether one or both options are on, so
     ``kid_features`` is set by either, while ``kid_value()`` stays None without ``kid`` -- and ``ids_value()`` -> (U-IDS, P-IDS) fits the linear
     SVM on this device from the gathered rows (like ``pr_value()``, not sharded over the ranks; ``pass_fn`` in the dict replaces the kernel: CPU
-    tests).  A ``*_value()`` is None until its option is on and finished."""
+    tests).  ``fid_tail='device'`` (default 'host': ``fid_from_stats``, scipy's ``sqrtm`` on the host) makes ``fid_value()`` the ``fid`` of
+    fid_stats.frechet_device on both ``mean_cov_device`` -- the moments never leave the device, the trace of the matrix square root comes from
+    Newton-Schulz products on the fp64-MFMA GEMM -- and keeps that call's dict (trace, step count, stop reason) as ``fid_tail_info``;
+    ``fid_tail=dict(tol=1e-10, max_iter=100)`` is 'device' with those options (``matmul_fn`` in the dict replaces the kernel: CPU tests).  Like
+    ``pr_value()`` it runs on the caller's rank from the reduced moments.  A ``*_value()`` is None until its option is on and finished."""
 
-    def __init__(self, shard, feature_fn, fid_dim=2048, accumulate_fn=None, fid_real=False, kid=None, inception_score=None, pids_uids=None):
+    def __init__(self, shard, feature_fn, fid_dim=2048, accumulate_fn=None, fid_real=False, kid=None, inception_score=None, pids_uids=None,
+                 fid_tail='host'):
         if fid_real and feature_fn is None:
             raise ValueError('EvalLoop: fid_real needs a feature_fn (the detector)')
+        self.fid_tail, self.fid_tail_opts, self.fid_tail_info = check_fid_tail(fid_tail) + (None,)
         self.shard, self.feature_fn, self.needs_real, n_local = shard, feature_fn, bool(fid_real), len(shard.ids)
         self.fake, self.real = (PerStream((lambda: FidStats(fid_dim, device=shard.device, accumulate_fn=accumulate_fn)) if on else None,
                                           shard.device, add=lambda into, part: into.S.add_(part.S)) for on in (True, fid_real))
@@ -171,6 +189,9 @@ class DetectorStats:
 
     def fid_value(self):
         fake, real = self.fake.sum, self.real.sum            # FidStats: this rank's after total(), all ranks' after finish()
+        if self.fid_tail == 'device' and fake is not None and real is not None:
+            self.fid_tail_info = frechet_device(*fake.mean_cov_device()[1:], *real.mean_cov_device()[1:], **self.fid_tail_opts)
+            return self.fid_tail_info['fid']
         return fid_from_stats(*fake.mean_cov()[1:], *real.mean_cov()[1:]) if fake is not None and real is not None else None
 
     def kid_value(self):
