@@ -572,6 +572,29 @@ int shg_resize_bicubic_u8(const void* src, long src_bytes, const int* table, lon
 int shg_resize_fit_pad_u8(const void* src, long src_bytes, const int* table, long table_elems, void* dst, int B, int R, int chunks, int bands,
                           int lds_bytes, void* stream);
 
+/* ---- Inpainting photographs of any size (sh-gan_amd/inpaint.py drives both; csrc/inpaint.hip).  src: src_bytes bytes holding B HWC RGB
+ * uint8 images back to back; mask: mask_bytes bytes holding their HW uint8 masks back to back (non-zero = known, 0 = hole).  table:
+ * device int32 [table_elems] = B descriptors of 16 ints {h, w, image byte offset, mask byte offset, window y0, x0, ch, cw, h-bounds,
+ * h-coefs, KH, v-bounds, v-coefs, KV, band rows, column chunk} followed by the per-axis tables they point at: bounds [n][2] = (first tap,
+ * taps) and coefficients [n][K] (builders: inpaint.build_gather_table / build_paste_table).  A descriptor, window or tap range outside
+ * src / mask / table / fake leaves that image's bytes unwritten (never an out-of-bounds access).
+ * shg_inpaint_gather_u8: dst uint8 [B,3,R,R] = Pillow's crop(window).resize((R, R), BICUBIC) of every image, bit-exact (fixed-point
+ *   tables of (cw -> R) / (ch -> R), 22 fractional bits, n = R; the source is read in place at the image's row pitch); mask_dst float32
+ *   [B,1,R,R]: pixel (i, j) is 1 iff every native pixel of rows [i ch / R, max(ceil((i + 1) ch / R), lo + 1)) x the same columns is known.
+ *   Grid chunks x bands x B over the R x R output; lds_bytes (<= 49152) >= 3 x (window rows of a band) x (column chunk rounded up to 4).
+ * shg_inpaint_paste_u8: out uint8 [K][img_bytes], every row a copy of src on entry; fake float32 [B*K,3,R,R], row n K + k = sample k of
+ *   image n.  Per window pixel p, F = feather + 1 (feather in 0..32): A = max(0, F - Chebyshev distance to the nearest hole pixel inside
+ *   the window); v = fake resampled R x R -> ch x cw at p with the float32 tap tables (bit patterns in the int32 table, n = cw / ch;
+ *   horizontal pass, then vertical, fused multiply-adds in tap order from 0); g = clamp(v * 127.5 + 127.5, 0, 255);
+ *   out = (uint8)(int)((A g + (F - A) out) / F), every operation rounded on its own; A = 0 stores nothing.  alpha: NULL, or uint8
+ *   [mask_bytes], zeroed by the caller, that receives A.  Grid chunks x bands x B over the largest window; lds_bytes (<= 49152) >=
+ *   16 + align16(TB CW) + max(align16((TB + 2 feather) roundup4(CW + 2 feather)) + align16((TB + 2 feather) CW), 12 (rows of fake under a
+ *   band) CW).  No atomics: an image's bytes are the same alone, in any batch and on every run. */
+int shg_inpaint_gather_u8(const void* src, long src_bytes, const void* mask, long mask_bytes, const int* table, long table_elems, void* dst,
+                          float* mask_dst, int B, int R, int chunks, int bands, int lds_bytes, void* stream);
+int shg_inpaint_paste_u8(void* out, long img_bytes, const void* mask, long mask_bytes, const int* table, long table_elems, const float* fake,
+                         void* alpha, int B, int K, int R, int feather, int chunks, int bands, int lds_bytes, void* stream);
+
 /* ---- Training input of Places2, OpenImages and DTD: the "random scale, random crop" formatter (AdvInpaintingFormatter,
  * ds_places2.py:183-207, ds_openimages.py:117-141; InpaintingFormatter, ds_texture.py:121-149).  dst float32 [B,3,s,s]: per image the
  * window [ch:ch+s, cw:cw+s] of torch's bicubic resample (upsample_bicubic2d, align_corners = false, A = -0.75, 4 x 4 clamped taps,

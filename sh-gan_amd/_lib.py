@@ -173,6 +173,8 @@ _SIGS = {
     'shg_image_metrics': [c_fp, c_fp, c_f, c_f, c_fp, c_fp, c_f, c_f] + [c_i] * 6 + [c_fp, ctypes.c_size_t, c_fp, c_fp, c_fp],
     'shg_resize_bicubic_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
     'shg_resize_fit_pad_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'shg_inpaint_gather_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'shg_inpaint_paste_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
     'shg_randcrop_bicubic_ragged_f32': [c_fp, c_l, ctypes.POINTER(c_i), c_fp, c_fp, c_fp, c_i, c_i, c_fp],
     'shg_randcrop_bicubic_planar_f32': [c_fp, c_l, ctypes.POINTER(c_i), c_fp, c_fp, c_fp, c_i, c_i, c_fp],
     'shg_ada_params_f32': [c_fp, c_fp, c_fp, ctypes.POINTER(AdaConfig), c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],

@@ -1,0 +1,371 @@
+// Inpainting photographs of any size (sh-gan_amd/inpaint.py drives both kernels): a window of each image around its hole is resized to the
+// generator's R x R input (gather_windows), and the generator's output is resampled back to the window and blended into the original bytes
+// with a feathered weight (paste_back).  Images are decoded uint8 HWC RGB packed back to back (resize.pack_images), masks uint8 HW packed
+// the same way (1 / non-zero = known, 0 = hole), each image with a window {y0, x0, ch, cw} that lies inside it.
+//
+// gather_windows.  Image: the bytes of Pillow's Image.crop(box).resize((R, R), BICUBIC) -- the integer arithmetic of resize.hip on the
+// fixed-point tables of (cw -> R) and (ch -> R), the source read at the image's own row pitch from the window origin (nothing is copied
+// first).  Mask: output pixel (i, j) is known iff every native pixel of rows [i ch / R, max(ceil((i + 1) ch / R), lo + 1)) x the same
+// columns is known (integers; conservative: no hole pixel lies outside the low-resolution hole).  One workgroup = (image, band of TB
+// output rows, chunk of CW output columns), as in resize.hip.
+//
+// paste_back, for a pixel p of the window, F = feather + 1:
+//   d(p) = Chebyshev distance to the nearest hole pixel inside the window,  A(p) = max(0, F - d(p))              (an integer 0..F)
+//   v    = separable resample of fake (R x R -> ch x cw) at p: float32 tap tables from the host (Pillow's bicubic, a = -0.5, normalised),
+//          horizontal pass first (into LDS), then vertical, each a chain of fused multiply-adds in tap order starting from 0
+//   g    = clamp(v * 127.5 + 127.5, 0, 255)                     (each operation rounded on its own, as composite_u8_kernel writes it)
+//   out  = (uint8)(int)((A g + (F - A) orig) / F)               (truncation; A = 0 stores nothing, A = F gives (uint8)(int)g)
+// `out` holds K copies of the packed originals (row k = sample k) when the launch starts; the launch covers the windows only.
+// One workgroup = (image, band of TB window rows, chunk of CW window columns):
+//   1. the mask tile with a halo of `feather` pixels is staged in LDS as hole flags (outside the window: not a hole).  A(p) > 0 iff a
+//      hole lies within `feather` of p, so a staged tile without a hole has A = 0 everywhere: the workgroup returns on that
+//      workgroup-uniform test, before anything else is read.  Most of a window is such tiles.
+//   2. row pass (distance to the nearest hole in the row, capped at F), column pass (min over dy of max(|dy|, rowdist)) -> A, bytes in LDS;
+//   3. per sample k: the band's rows of fake are resampled horizontally into float LDS (pixel-interleaved, [row][3 col + channel], which
+//      is the byte order of the HWC destination), then one lane = one aligned 4-byte word of a destination row: the vertical pass of its
+//      four bytes, the blend with the word read from `out`, one 4-byte store (bytes at the ragged ends of the chunk's row and where the
+//      word would cross them).  A word belongs to one lane of one workgroup, and a word whose four A are 0 is not stored.
+// Dynamic LDS only, every carve 16-byte aligned; the staging of step 3 reuses the bytes of steps 1-2.  No atomics, no inter-workgroup
+// communication: an image's bytes do not depend on its neighbours in the batch or on the run.
+//
+// table (int32; the float32 weights of paste_back travel as their bit patterns): B descriptors of IP_DESC ints {h, w, image byte offset,
+// mask byte offset, y0, x0, ch, cw, h-bounds, h-coefs, KH, v-bounds, v-coefs, KV, TB, CW}, then per axis bounds [n][2] = (first tap, taps)
+// and coefficients [n][K] at the offsets the descriptors name (n = R for gather_windows, cw / ch for paste_back).  The kernels check every
+// descriptor and tap range against the buffer sizes they are given: a malformed table leaves bytes unwritten, it never reads or writes
+// out of bounds.
+#include "shg_common.h"
+
+namespace {
+
+constexpr int IP_THREADS = 256;
+constexpr int IP_LDS_BYTES = 49152;      // inpaint.py LDS_BYTES: the most a launch may ask for
+constexpr int IP_DESC = 16;              // inpaint.py DESC_INTS
+constexpr int IP_BITS = 22;
+constexpr int IP_MAX_FEATHER = 32;
+
+__device__ __forceinline__ uint32_t ip_clip8(int s) {
+    s >>= IP_BITS;
+    return (uint32_t)min(max(s, 0), 255);
+}
+
+__device__ __forceinline__ int ip_align16(int n) { return (n + 15) & ~15; }
+
+struct IpDesc {
+    int h, w, off, moff, wy0, wx0, ch, cw, hb, hk, KH, vb, vk, KV, TB, CW;
+};
+
+// The descriptor of image b, or false when anything in it points outside the buffers (n_h / n_v: entries of the horizontal / vertical table).
+__device__ __forceinline__ bool ip_load_desc(const int* tab, long tab_elems, int b, long img_bytes, long msk_bytes, bool out_is_r, int R, IpDesc& d) {
+    const int* p = tab + (long)b * IP_DESC;
+    d.h = p[0], d.w = p[1], d.off = p[2], d.moff = p[3], d.wy0 = p[4], d.wx0 = p[5], d.ch = p[6], d.cw = p[7];
+    d.hb = p[8], d.hk = p[9], d.KH = p[10], d.vb = p[11], d.vk = p[12], d.KV = p[13], d.TB = p[14], d.CW = p[15];
+    if (d.h < 1 || d.w < 1 || d.off < 0 || d.moff < 0 || (long)d.off + (long)d.h * d.w * 3 > img_bytes || (long)d.moff + (long)d.h * d.w > msk_bytes)
+        return false;
+    if (d.wy0 < 0 || d.wx0 < 0 || d.ch < 1 || d.cw < 1 || (long)d.wy0 + d.ch > d.h || (long)d.wx0 + d.cw > d.w) return false;
+    if (d.TB < 1 || d.CW < 1 || d.TB > 4096 || d.CW > 4096 || d.KH < 1 || d.KV < 1) return false;      // (tile products stay inside int)
+    const long nh = out_is_r ? R : d.cw, nv = out_is_r ? R : d.ch;
+    if (d.hb < 0 || d.hk < 0 || d.vb < 0 || d.vk < 0 || (long)d.hb + 2 * nh > tab_elems || (long)d.hk + nh * d.KH > tab_elems ||
+        (long)d.vb + 2 * nv > tab_elems || (long)d.vk + nv * d.KV > tab_elems)
+        return false;
+    return true;
+}
+
+__global__ __launch_bounds__(IP_THREADS) void gather_windows_kernel(const uint8_t* __restrict__ src, long src_bytes,
+                                                                    const uint8_t* __restrict__ msk, long msk_bytes,
+                                                                    const int* __restrict__ tab, long tab_elems, uint8_t* __restrict__ dst,
+                                                                    float* __restrict__ mdst, int R, int lds_bytes) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t ip_lds[];
+    uint8_t* mid = ip_lds;
+    const int b = blockIdx.z;
+    IpDesc d;
+    if (!ip_load_desc(tab, tab_elems, b, src_bytes, msk_bytes, true, R, d)) return;
+    const int y0 = (int)blockIdx.y * d.TB, c0 = (int)blockIdx.x * d.CW;
+    if (y0 >= R || c0 >= R) return;
+    const int y1 = min(y0 + d.TB, R), cn = min(d.CW, R - c0);
+    const int cwp = (cn + 3) & ~3;                                  // LDS row pitch: 4-byte reads in the vertical pass
+    const int sy0 = max(tab[d.vb + 2 * y0], 0);
+    const int sy1 = (int)min((long)tab[d.vb + 2 * (y1 - 1)] + tab[d.vb + 2 * (y1 - 1) + 1], (long)d.ch);
+    const int span = sy1 - sy0;                                     // window rows of the band
+    if (span < 1 || 3L * span * cwp > lds_bytes) return;
+
+    // horizontal pass: one lane = one (window row, output column), three channels
+    const long pitch = (long)d.w * 3;
+    const uint8_t* win = src + d.off + (long)d.wy0 * pitch + (long)d.wx0 * 3;
+    for (int e = threadIdx.x; e < span * cn; e += IP_THREADS) {
+        const int r = e / cn, c = e - r * cn, x = c0 + c;
+        int xmin = tab[d.hb + 2 * x], n = tab[d.hb + 2 * x + 1];
+        if (xmin < 0 || n < 0 || n > d.KH || (long)xmin + n > d.cw) xmin = 0, n = 0;
+        const uint8_t* p = win + (long)(sy0 + r) * pitch + xmin * 3;
+        const int* k = tab + d.hk + (long)x * d.KH;
+        int s0 = 1 << (IP_BITS - 1), s1 = s0, s2 = s0;
+        for (int j = 0; j < n; ++j) {
+            const int kj = k[j];
+            s0 += (int)p[3 * j] * kj;
+            s1 += (int)p[3 * j + 1] * kj;
+            s2 += (int)p[3 * j + 2] * kj;
+        }
+        mid[(0 * span + r) * cwp + c] = (uint8_t)ip_clip8(s0);
+        mid[(1 * span + r) * cwp + c] = (uint8_t)ip_clip8(s1);
+        mid[(2 * span + r) * cwp + c] = (uint8_t)ip_clip8(s2);
+    }
+    __syncthreads();
+
+    // vertical pass: one lane = 4 consecutive output columns of one (channel, output row)
+    const int groups = cwp >> 2, rows = y1 - y0;
+    for (int e = threadIdx.x; e < 3 * rows * groups; e += IP_THREADS) {
+        const int g = e % groups, t = e / groups;
+        const int oy = y0 + t % rows, ch = t / rows;
+        int rel = tab[d.vb + 2 * oy] - sy0, n = tab[d.vb + 2 * oy + 1];
+        if (rel < 0 || n < 0 || n > d.KV || (long)rel + n > span) rel = 0, n = 0;
+        const uint8_t* m = mid + (ch * span + rel) * cwp + 4 * g;
+        const int* k = tab + d.vk + (long)oy * d.KV;
+        int a0 = 1 << (IP_BITS - 1), a1 = a0, a2 = a0, a3 = a0;
+        for (int j = 0; j < n; ++j) {
+            const uint32_t v = *reinterpret_cast<const uint32_t*>(m + j * cwp);
+            const int kj = k[j];
+            a0 += (int)(v & 255u) * kj;
+            a1 += (int)((v >> 8) & 255u) * kj;
+            a2 += (int)((v >> 16) & 255u) * kj;
+            a3 += (int)(v >> 24) * kj;
+        }
+        const uint32_t o0 = ip_clip8(a0), o1 = ip_clip8(a1), o2 = ip_clip8(a2), o3 = ip_clip8(a3);
+        const int c = c0 + 4 * g;                                   // first output column of the group (c0 % 4 == 0 on the host's tiling)
+        uint8_t* orow = dst + (((long)b * 3 + ch) * R + oy) * R;
+        const int nv = min(4, c0 + cn - c);
+        if (nv == 4 && (R & 3) == 0 && (c & 3) == 0) {
+            *reinterpret_cast<uint32_t*>(orow + c) = o0 | o1 << 8 | o2 << 16 | o3 << 24;
+        } else {
+            const uint32_t o[4] = {o0, o1, o2, o3};
+            for (int q = 0; q < nv; ++q) orow[c + q] = (uint8_t)o[q];
+        }
+    }
+
+    // mask: one lane = one output pixel, known iff its whole native footprint is known
+    const uint8_t* mwin = msk + d.moff + (long)d.wy0 * d.w + d.wx0;
+    for (int e = threadIdx.x; e < rows * cn; e += IP_THREADS) {
+        const int t = e / cn, oy = y0 + t, ox = c0 + (e - t * cn);
+        const int rlo = (int)((long)oy * d.ch / R), rhi = max((int)(((long)(oy + 1) * d.ch + R - 1) / R), rlo + 1);
+        const int clo = (int)((long)ox * d.cw / R), chi = max((int)(((long)(ox + 1) * d.cw + R - 1) / R), clo + 1);
+        bool known = true;
+        for (int y = rlo; y < rhi; ++y) {
+            const uint8_t* mr = mwin + (long)y * d.w;
+            for (int x = clo; x < chi; ++x) known = known && mr[x] != 0;
+        }
+        mdst[((long)b * R + oy) * R + ox] = known ? 1.f : 0.f;
+    }
+}
+
+// g = clamp(v * 127.5 + 127.5, 0, 255), then (A g + (F - A) orig) / F truncated: every product, sum and the quotient rounded on its own.
+__device__ __forceinline__ uint32_t ip_blend(float v, float a, float fa, float orig, float f) {
+#pragma clang fp contract(off)
+    v = v * 127.5f;
+    v = v + 127.5f;
+    v = fminf(fmaxf(v, 0.f), 255.f);
+    const float t1 = a * v;
+    const float t2 = fa * orig;
+    float s = t1 + t2;
+    s = s / f;
+    return (uint32_t)(uint8_t)(int)s;
+}
+
+__global__ __launch_bounds__(IP_THREADS) void paste_back_kernel(uint8_t* __restrict__ out, long img_bytes, const uint8_t* __restrict__ msk,
+                                                                long msk_bytes, const int* __restrict__ tab, long tab_elems,
+                                                                const float* __restrict__ fake, uint8_t* __restrict__ alpha, int R, int K,
+                                                                int feather, int lds_bytes) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t ip_lds[];
+    const int b = blockIdx.z;
+    IpDesc d;
+    if (!ip_load_desc(tab, tab_elems, b, img_bytes, msk_bytes, false, R, d)) return;
+    const int y0 = (int)blockIdx.y * d.TB, c0 = (int)blockIdx.x * d.CW;
+    if (y0 >= d.ch || c0 >= d.cw) return;
+    const int y1 = min(y0 + d.TB, d.ch), rows = y1 - y0, cn = min(d.CW, d.cw - c0);
+    const int F = feather + 1, HALO = feather;
+    const int th = rows + 2 * HALO, tw = cn + 2 * HALO, twp = (tw + 3) & ~3;
+    const int sy0 = max(tab[d.vb + 2 * y0], 0);
+    const int sy1 = (int)min((long)tab[d.vb + 2 * (y1 - 1)] + tab[d.vb + 2 * (y1 - 1) + 1], (long)R);
+    const int span = sy1 - sy0;                                     // rows of fake under the band
+    // carves: flag (16 bytes), A [rows][cn]  |  hole flags [th][twp], row distances [th][cn]   (steps 1-2)
+    //                                        |  horizontally resampled rows, float [span][3 cn] (step 3, over the same bytes)
+    const int a_bytes = 16 + ip_align16(rows * cn), t_bytes = ip_align16(th * twp), r_bytes = ip_align16(th * cn);
+    if (span < 1 || (long)a_bytes + max((long)t_bytes + r_bytes, 12L * span * cn) > lds_bytes) return;
+    int* flag = reinterpret_cast<int*>(ip_lds);
+    uint8_t* A = ip_lds + 16;
+    uint8_t* tile = ip_lds + a_bytes;
+    uint8_t* rowd = tile + t_bytes;
+    float* mid = reinterpret_cast<float*>(ip_lds + a_bytes);
+
+    // 1. hole flags of the tile and its halo
+    for (int e = threadIdx.x; e < t_bytes >> 2; e += IP_THREADS) reinterpret_cast<uint32_t*>(tile)[e] = 0u;
+    if (threadIdx.x == 0) *flag = 0;
+    __syncthreads();
+    const uint8_t* mwin = msk + d.moff + (long)d.wy0 * d.w + d.wx0;
+    const int ca = max(c0 - HALO, 0), cb = min(c0 + cn + HALO, d.cw), nbm = cb - ca;       // window columns staged
+    const int um = (tw + 6) >> 2;                                                           // aligned words a staged row can touch
+    int found = 0;
+    for (int e = threadIdx.x; e < th * um; e += IP_THREADS) {
+        const int tr = e / um, u = e - tr * um, wr = y0 - HALO + tr;
+        if (wr < 0 || wr >= d.ch) continue;
+        const uint8_t* p = mwin + (long)wr * d.w + ca;
+        const int lo = 4 * u - (int)(reinterpret_cast<uintptr_t>(p) & 3);
+        if (lo >= nbm || lo + 4 <= 0) continue;
+        uint8_t* trow = tile + tr * twp + (ca - (c0 - HALO));
+        if (lo >= 0 && lo + 4 <= nbm) {
+            const uint32_t v = *reinterpret_cast<const uint32_t*>(p + lo);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int hole = ((v >> (8 * q)) & 255u) == 0u;
+                trow[lo + q] = (uint8_t)hole;
+                found |= hole;
+            }
+        } else {
+            for (int q = max(lo, 0); q < min(lo + 4, nbm); ++q) {
+                const int hole = p[q] == 0;
+                trow[q] = (uint8_t)hole;
+                found |= hole;
+            }
+        }
+    }
+    if (found) *flag = 1;                                           // (every writer stores the same value)
+    __syncthreads();
+    if (*flag == 0) return;                                         // no hole within `feather` of the tile: A = 0, nothing to store
+
+    // 2. row pass, column pass
+    for (int e = threadIdx.x; e < th * cn; e += IP_THREADS) {
+        const int tr = e / cn, c = e - tr * cn;
+        const uint8_t* t = tile + tr * twp + c + HALO;
+        int rd = F;
+        for (int dd = 0; dd <= HALO; ++dd)
+            if (t[-dd] | t[dd]) {
+                rd = dd;
+                break;
+            }
+        rowd[tr * cn + c] = (uint8_t)rd;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < rows * cn; e += IP_THREADS) {
+        const int r = e / cn, c = e - r * cn;
+        const uint8_t* q = rowd + (r + HALO) * cn + c;
+        int best = q[0];
+        for (int dd = 1; dd < best && dd <= HALO; ++dd) best = min(best, max(dd, min((int)q[-dd * cn], (int)q[dd * cn])));
+        A[e] = (uint8_t)(F - best);
+    }
+    __syncthreads();                                                // A complete; the flags and row distances are dead from here on
+
+    const int uo = (3 * cn + 6) >> 2;                               // aligned words a destination row of the chunk can touch
+    if (alpha) {
+        const int ua = (cn + 6) >> 2;
+        for (int e = threadIdx.x; e < rows * ua; e += IP_THREADS) {
+            const int r = e / ua, u = e - r * ua;
+            uint8_t* p = alpha + d.moff + (long)(d.wy0 + y0 + r) * d.w + d.wx0 + c0;
+            const int lo = 4 * u - (int)(reinterpret_cast<uintptr_t>(p) & 3);
+            if (lo >= cn || lo + 4 <= 0) continue;
+            const uint8_t* ar = A + r * cn;
+            if (lo >= 0 && lo + 4 <= cn) {
+                *reinterpret_cast<uint32_t*>(p + lo) = (uint32_t)ar[lo] | (uint32_t)ar[lo + 1] << 8 | (uint32_t)ar[lo + 2] << 16 | (uint32_t)ar[lo + 3] << 24;
+            } else {
+                for (int q = max(lo, 0); q < min(lo + 4, cn); ++q) p[q] = ar[q];
+            }
+        }
+    }
+
+    // 3. per sample: horizontal pass into LDS, then vertical pass + blend, one lane per destination word
+    const long RR = (long)R * R;
+    const float ff = (float)F;
+    for (int k = 0; k < K; ++k) {
+        const float* fk = fake + ((long)b * K + k) * 3 * RR;
+        for (int e = threadIdx.x; e < span * cn; e += IP_THREADS) {
+            const int r = e / cn, c = e - r * cn, x = c0 + c;
+            int xmin = tab[d.hb + 2 * x], n = tab[d.hb + 2 * x + 1];
+            if (xmin < 0 || n < 0 || n > d.KH || (long)xmin + n > R) xmin = 0, n = 0;
+            const float* p = fk + (long)(sy0 + r) * R + xmin;
+            const int* wk = tab + d.hk + (long)x * d.KH;
+            float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+            for (int j = 0; j < n; ++j) {
+                const float wj = __int_as_float(wk[j]);
+                s0 = fmaf(wj, p[j], s0);
+                s1 = fmaf(wj, p[RR + j], s1);
+                s2 = fmaf(wj, p[2 * RR + j], s2);
+            }
+            float* m = mid + (r * cn + c) * 3;
+            m[0] = s0, m[1] = s1, m[2] = s2;
+        }
+        __syncthreads();
+        uint8_t* outk = out + (long)k * img_bytes + d.off;
+        for (int e = threadIdx.x; e < rows * uo; e += IP_THREADS) {
+            const int r = e / uo, u = e - r * uo, oy = y0 + r, nb = 3 * cn;
+            const int rel = tab[d.vb + 2 * oy] - sy0, n = tab[d.vb + 2 * oy + 1];
+            if (rel < 0 || n < 0 || n > d.KV || (long)rel + n > span) continue;
+            uint8_t* p = outk + ((long)(d.wy0 + oy) * d.w + d.wx0 + c0) * 3;
+            const int lo = 4 * u - (int)(reinterpret_cast<uintptr_t>(p) & 3);
+            if (lo >= nb || lo + 4 <= 0) continue;
+            const int q0 = max(lo, 0), q1 = min(lo + 4, nb);
+            const uint8_t* ar = A + r * cn;
+            int any = 0;
+            for (int q = q0; q < q1; ++q) any |= ar[q / 3];
+            if (!any) continue;
+            const bool whole = q1 - q0 == 4;
+            uint32_t word = 0u;
+            if (whole) word = *reinterpret_cast<const uint32_t*>(p + lo);
+            const int* wk = tab + d.vk + (long)oy * d.KV;
+            const float* m = mid + (long)rel * nb;
+            for (int q = q0; q < q1; ++q) {
+                const int a = ar[q / 3];
+                if (!a) continue;
+                float v = 0.f;
+                for (int j = 0; j < n; ++j) v = fmaf(__int_as_float(wk[j]), m[j * nb + q], v);
+                const int sh = 8 * (q - lo);
+                const float orig = whole ? (float)((word >> sh) & 255u) : (float)p[q];
+                const uint32_t o = ip_blend(v, (float)a, (float)(F - a), orig, ff);
+                if (whole) word = (word & ~(255u << sh)) | o << sh;
+                else p[q] = (uint8_t)o;
+            }
+            if (whole) *reinterpret_cast<uint32_t*>(p + lo) = word;
+        }
+        __syncthreads();                                            // the next sample overwrites mid
+    }
+}
+
+}  // namespace
+
+// gather_windows: src / mask as above, dst uint8 [B,3,R,R], mask_dst float32 [B,1,R,R] (1 = known).  table: B descriptors of 16 ints and
+// the fixed-point tables of resize.py's bicubic_coeffs(cw, R) / (ch, R).  Grid chunks x bands x B; lds_bytes as shg_resize_bicubic_u8.
+extern "C" int shg_inpaint_gather_u8(const void* src, long src_bytes, const void* mask, long mask_bytes, const int* table, long table_elems,
+                                     void* dst, float* mask_dst, int B, int R, int chunks, int bands, int lds_bytes, void* stream) {
+    SHG_CHECK_ARG(src && mask && table && dst && mask_dst, "inpaint_gather: null pointer");
+    SHG_CHECK_ARG(B >= 1 && B <= 65535, "inpaint_gather: B must lie in [1, 65535] (got %d)", B);
+    SHG_CHECK_ARG(R >= 1 && R <= 16384, "inpaint_gather: R must lie in [1, 16384] (got %d)", R);
+    SHG_CHECK_ARG(src_bytes >= 3 && src_bytes <= 0x7fffffffL, "inpaint_gather: src_bytes must lie in [3, 2^31) (int32 offsets)");
+    SHG_CHECK_ARG(mask_bytes >= 1 && mask_bytes <= 0x7fffffffL, "inpaint_gather: mask_bytes must lie in [1, 2^31) (int32 offsets)");
+    SHG_CHECK_ARG(table_elems >= (long)B * IP_DESC, "inpaint_gather: the table holds fewer than B descriptors of %d ints", IP_DESC);
+    SHG_CHECK_ARG(chunks >= 1 && chunks <= R && bands >= 1 && bands <= R && bands <= 65535,
+                  "inpaint_gather: chunks and bands must lie in [1, R] (got %d, %d)", chunks, bands);
+    SHG_CHECK_ARG(lds_bytes >= 12 && lds_bytes <= IP_LDS_BYTES, "inpaint_gather: lds_bytes must lie in [12, %d] (got %d)", IP_LDS_BYTES, lds_bytes);
+    hipLaunchKernelGGL(gather_windows_kernel, dim3(chunks, bands, B), dim3(IP_THREADS), (size_t)lds_bytes, (hipStream_t)stream,
+                       (const uint8_t*)src, src_bytes, (const uint8_t*)mask, mask_bytes, table, table_elems, (uint8_t*)dst, mask_dst, R, lds_bytes);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}
+
+// paste_back: out uint8 [K][img_bytes], every row a copy of the packed originals on entry; fake float32 [B*K,3,R,R] (row n K + k: sample k
+// of image n); alpha: NULL, or uint8 [mask_bytes] that receives A inside the windows' tiles that hold a non-zero A (the caller zeroes it
+// first).  table: B descriptors of 16 ints and the float32 tables (bit patterns) of (R -> cw) / (R -> ch).  Grid chunks x bands x B.
+extern "C" int shg_inpaint_paste_u8(void* out, long img_bytes, const void* mask, long mask_bytes, const int* table, long table_elems,
+                                    const float* fake, void* alpha, int B, int K, int R, int feather, int chunks, int bands, int lds_bytes,
+                                    void* stream) {
+    SHG_CHECK_ARG(out && mask && table && fake, "inpaint_paste: null pointer");
+    SHG_CHECK_ARG(B >= 1 && B <= 65535, "inpaint_paste: B must lie in [1, 65535] (got %d)", B);
+    SHG_CHECK_ARG(K >= 1 && K <= 65535, "inpaint_paste: K must lie in [1, 65535] (got %d)", K);
+    SHG_CHECK_ARG(R >= 1 && R <= 16384, "inpaint_paste: R must lie in [1, 16384] (got %d)", R);
+    SHG_CHECK_ARG(feather >= 0 && feather <= IP_MAX_FEATHER, "inpaint_paste: feather must lie in [0, %d] (got %d)", IP_MAX_FEATHER, feather);
+    SHG_CHECK_ARG(img_bytes >= 3 && img_bytes <= 0x7fffffffL, "inpaint_paste: img_bytes must lie in [3, 2^31) (int32 offsets)");
+    SHG_CHECK_ARG(mask_bytes >= 1 && mask_bytes <= 0x7fffffffL, "inpaint_paste: mask_bytes must lie in [1, 2^31) (int32 offsets)");
+    SHG_CHECK_ARG(table_elems >= (long)B * IP_DESC, "inpaint_paste: the table holds fewer than B descriptors of %d ints", IP_DESC);
+    SHG_CHECK_ARG(chunks >= 1 && chunks <= 65535 && bands >= 1 && bands <= 65535, "inpaint_paste: chunks and bands must lie in [1, 65535] (got %d, %d)",
+                  chunks, bands);
+    SHG_CHECK_ARG(lds_bytes >= 32 && lds_bytes <= IP_LDS_BYTES, "inpaint_paste: lds_bytes must lie in [32, %d] (got %d)", IP_LDS_BYTES, lds_bytes);
+    SHG_CHECK_ARG((reinterpret_cast<uintptr_t>(fake) & 3) == 0, "inpaint_paste: fake must be 4-byte aligned");
+    hipLaunchKernelGGL(paste_back_kernel, dim3(chunks, bands, B), dim3(IP_THREADS), (size_t)lds_bytes, (hipStream_t)stream, (uint8_t*)out,
+                       img_bytes, (const uint8_t*)mask, mask_bytes, table, table_elems, fake, (uint8_t*)alpha, R, K, feather, lds_bytes);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}

@@ -44,6 +44,28 @@ def _bicubic(x):
                     np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
 
 
+def bicubic_taps(n_in, n_out):
+    """-> (xmin int64 [out], n int64 [out], w float64 [out, K]): Pillow's tap range and normalised bicubic weights along one axis, in double
+    precision before any rounding (n_in != n_out; weights past a row's n taps are 0)."""
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ss = 1.0 / fs
+    ksize = int(np.ceil(support)) * 2 + 1
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(np.trunc(center - support + 0.5), 0).astype(np.int64)
+    xmax = np.minimum(np.trunc(center + support + 0.5), n_in).astype(np.int64)
+    n = xmax - xmin
+    pre = np.zeros((n_out, ksize), np.float64)
+    ww = np.zeros(n_out, np.float64)
+    for j in range(ksize):                              # sequential sum over taps, as Pillow's loop
+        w = np.where(j < n, _bicubic(((j + xmin) - center + 0.5) * ss), 0.0)
+        pre[:, j] = w
+        ww = ww + w
+    pre = np.where(ww[:, None] != 0.0, pre / np.where(ww == 0.0, 1.0, ww)[:, None], pre)
+    return xmin, n, pre
+
+
 def bicubic_coeffs(in_size, out_size):
     """-> (bounds int32 [out, 2] = (xmin, n), k int32 [out, K]) of Pillow's 8-bit bicubic resample along one axis; cached."""
     key = (int(in_size), int(out_size))
@@ -57,22 +79,7 @@ def bicubic_coeffs(in_size, out_size):
         bounds = np.stack([np.arange(n_out), np.ones(n_out, np.int64)], axis=1).astype(np.int32)
         k = np.full((n_out, 1), 1 << PRECISION_BITS, np.int32)
     else:
-        scale = n_in / n_out
-        fs = max(scale, 1.0)
-        support = 2.0 * fs
-        ss = 1.0 / fs
-        ksize = int(np.ceil(support)) * 2 + 1
-        center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
-        xmin = np.maximum(np.trunc(center - support + 0.5), 0).astype(np.int64)
-        xmax = np.minimum(np.trunc(center + support + 0.5), n_in).astype(np.int64)
-        n = xmax - xmin
-        pre = np.zeros((n_out, ksize), np.float64)
-        ww = np.zeros(n_out, np.float64)
-        for j in range(ksize):                              # sequential sum over taps, as Pillow's loop
-            w = np.where(j < n, _bicubic(((j + xmin) - center + 0.5) * ss), 0.0)
-            pre[:, j] = w
-            ww = ww + w
-        pre = np.where(ww[:, None] != 0.0, pre / np.where(ww == 0.0, 1.0, ww)[:, None], pre)
+        xmin, n, pre = bicubic_taps(n_in, n_out)
         fx = pre * float(1 << PRECISION_BITS)
         k = np.where(pre < 0, np.trunc(-0.5 + fx), np.trunc(0.5 + fx)).astype(np.int32)
         bounds = np.stack([xmin, n], axis=1).astype(np.int32)
