@@ -595,6 +595,37 @@ int shg_inpaint_gather_u8(const void* src, long src_bytes, const void* mask, lon
 int shg_inpaint_paste_u8(void* out, long img_bytes, const void* mask, long mask_bytes, const int* table, long table_elems, const float* fake,
                          void* alpha, int B, int K, int R, int feather, int chunks, int bands, int lds_bytes, void* stream);
 
+/* ---- Gradient-domain (Poisson) paste-back (sh-gan_amd/inpaint.py paste_back_membrane; csrc/membrane.hip).  With A, g and orig of
+ * shg_inpaint_paste_u8: Omega = {A > 0}; the membrane c solves 4 c(p) - sum_{q in N4(p)} c(q) = 0 in Omega with c = d = orig - g on the
+ * window pixels with A = 0 and c = 0 outside the window; out = (uint8)(int)((A clamp(g + c, 0, 255) + (F - A) out) / F).
+ * grids: device int32 [B][6] = {gy0, gx0, gh, gw, float offset, byte offset}: per image the solve grid (a box of the window, in window
+ *   coordinates, that holds Omega's bounding box and one more ring where the window allows), the offset of its K planes [K][gh][gw][3]
+ *   in g / field, and the offset of its Omega bytes [gh][gw].  A grid outside its window or its buffers leaves the image alone.
+ * shg_inpaint_membrane_setup_f32: src = the packed originals; writes, inside the grids, g (the bits shg_inpaint_paste_u8 computes),
+ *   field (d where A = 0, 0 in Omega) and omega (A > 0; the K samples of an image share it).  table, fake, chunks, bands, lds_bytes as
+ *   shg_inpaint_paste_u8.
+ * shg_membrane_solve_f32: P problems, table device int32 [P][4] = {h, w, float offset into field, byte offset into omega}, h <= max_h,
+ *   w <= max_w, slices of field disjoint: field float32 [h][w][3], omega uint8 [h][w], neighbours outside the h x w grid count as 0.  On
+ *   return the field holds c in Omega and is untouched elsewhere.  Multigrid V-cycles (csrc/membrane.hip) until the residual's max norm
+ *   over Omega and the three channels is <= res_tol[p] (device float32 [P]): info (device int32 [P][3]) = {cycles run, bits of the last
+ *   norm, state}, state 1 = certified, 2 = stalled (a cycle did not lower the norm: the float32 floor), 0 = out of max_cycles (0..1024).
+ *   A fixed sequence of launches, no host synchronisation; no atomics: a problem's bits do not depend on the batch or the run.
+ *   ws: ws_bytes >= shg_membrane_workspace_bytes(P, max_h, max_w) (16-byte aligned, as field); its old contents are irrelevant.
+ *   A problem whose descriptor breaks a rule above is left alone with info = {0, +inf, 0}.
+ * shg_inpaint_membrane_paste_u8: out, alpha, table, chunks, bands, lds_bytes as shg_inpaint_paste_u8; g and field (= c) as above.
+ * shg_membrane_tile / shg_membrane_coarsest: the smoother's tile side and the largest side of a coarsest level. */
+int shg_membrane_tile(void);
+int shg_membrane_coarsest(void);
+size_t shg_membrane_workspace_bytes(int P, int max_h, int max_w);
+int shg_inpaint_membrane_setup_f32(const void* src, long img_bytes, const void* mask, long mask_bytes, const int* table, long table_elems,
+                                   const int* grids, const float* fake, float* g, float* field, long g_elems, void* omega, long omega_bytes,
+                                   int B, int K, int R, int feather, int chunks, int bands, int lds_bytes, void* stream);
+int shg_membrane_solve_f32(float* field, long field_elems, const void* omega, long omega_bytes, const int* table, int P, const float* res_tol,
+                           int max_cycles, int max_h, int max_w, void* ws, size_t ws_bytes, int* info, void* stream);
+int shg_inpaint_membrane_paste_u8(void* out, long img_bytes, const void* mask, long mask_bytes, const int* table, long table_elems,
+                                  const int* grids, const float* g, const float* field, long g_elems, void* alpha, int B, int K, int R,
+                                  int feather, int chunks, int bands, int lds_bytes, void* stream);
+
 /* ---- Training input of Places2, OpenImages and DTD: the "random scale, random crop" formatter (AdvInpaintingFormatter,
  * ds_places2.py:183-207, ds_openimages.py:117-141; InpaintingFormatter, ds_texture.py:121-149).  dst float32 [B,3,s,s]: per image the
  * window [ch:ch+s, cw:cw+s] of torch's bicubic resample (upsample_bicubic2d, align_corners = false, A = -0.75, 4 x 4 clamped taps,

@@ -175,6 +175,12 @@ _SIGS = {
     'shg_resize_fit_pad_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
     'shg_inpaint_gather_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
     'shg_inpaint_paste_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'shg_membrane_tile': [],
+    'shg_membrane_coarsest': [],
+    'shg_membrane_workspace_bytes': [c_i, c_i, c_i],
+    'shg_inpaint_membrane_setup_f32': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'shg_membrane_solve_f32': [c_fp, c_l, c_fp, c_l, c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, ctypes.c_size_t, c_fp, c_fp],
+    'shg_inpaint_membrane_paste_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
     'shg_randcrop_bicubic_ragged_f32': [c_fp, c_l, ctypes.POINTER(c_i), c_fp, c_fp, c_fp, c_i, c_i, c_fp],
     'shg_randcrop_bicubic_planar_f32': [c_fp, c_l, ctypes.POINTER(c_i), c_fp, c_fp, c_fp, c_i, c_i, c_fp],
     'shg_ada_params_f32': [c_fp, c_fp, c_fp, ctypes.POINTER(AdaConfig), c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
@@ -244,6 +250,7 @@ def get_lib():
     lib.shg_kid_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_pr_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_svm_pass_workspace_bytes.restype = ctypes.c_size_t
+    lib.shg_membrane_workspace_bytes.restype = ctypes.c_size_t
     lib.shg_ada_adjoint_gather_workspace_bytes.restype = c_l
     lib.shg_inception_packed_weight_elems.restype = c_l
     lib.shg_conv2d_f16_packed_weight_elems.restype = c_l

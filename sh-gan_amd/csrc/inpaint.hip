@@ -33,41 +33,13 @@
 // and coefficients [n][K] at the offsets the descriptors name (n = R for gather_windows, cw / ch for paste_back).  The kernels check every
 // descriptor and tap range against the buffer sizes they are given: a malformed table leaves bytes unwritten, it never reads or writes
 // out of bounds.
-#include "shg_common.h"
+#include "inpaint_common.h"
 
 namespace {
-
-constexpr int IP_THREADS = 256;
-constexpr int IP_LDS_BYTES = 49152;      // inpaint.py LDS_BYTES: the most a launch may ask for
-constexpr int IP_DESC = 16;              // inpaint.py DESC_INTS
-constexpr int IP_BITS = 22;
-constexpr int IP_MAX_FEATHER = 32;
 
 __device__ __forceinline__ uint32_t ip_clip8(int s) {
     s >>= IP_BITS;
     return (uint32_t)min(max(s, 0), 255);
-}
-
-__device__ __forceinline__ int ip_align16(int n) { return (n + 15) & ~15; }
-
-struct IpDesc {
-    int h, w, off, moff, wy0, wx0, ch, cw, hb, hk, KH, vb, vk, KV, TB, CW;
-};
-
-// The descriptor of image b, or false when anything in it points outside the buffers (n_h / n_v: entries of the horizontal / vertical table).
-__device__ __forceinline__ bool ip_load_desc(const int* tab, long tab_elems, int b, long img_bytes, long msk_bytes, bool out_is_r, int R, IpDesc& d) {
-    const int* p = tab + (long)b * IP_DESC;
-    d.h = p[0], d.w = p[1], d.off = p[2], d.moff = p[3], d.wy0 = p[4], d.wx0 = p[5], d.ch = p[6], d.cw = p[7];
-    d.hb = p[8], d.hk = p[9], d.KH = p[10], d.vb = p[11], d.vk = p[12], d.KV = p[13], d.TB = p[14], d.CW = p[15];
-    if (d.h < 1 || d.w < 1 || d.off < 0 || d.moff < 0 || (long)d.off + (long)d.h * d.w * 3 > img_bytes || (long)d.moff + (long)d.h * d.w > msk_bytes)
-        return false;
-    if (d.wy0 < 0 || d.wx0 < 0 || d.ch < 1 || d.cw < 1 || (long)d.wy0 + d.ch > d.h || (long)d.wx0 + d.cw > d.w) return false;
-    if (d.TB < 1 || d.CW < 1 || d.TB > 4096 || d.CW > 4096 || d.KH < 1 || d.KV < 1) return false;      // (tile products stay inside int)
-    const long nh = out_is_r ? R : d.cw, nv = out_is_r ? R : d.ch;
-    if (d.hb < 0 || d.hk < 0 || d.vb < 0 || d.vk < 0 || (long)d.hb + 2 * nh > tab_elems || (long)d.hk + nh * d.KH > tab_elems ||
-        (long)d.vb + 2 * nv > tab_elems || (long)d.vk + nv * d.KV > tab_elems)
-        return false;
-    return true;
 }
 
 __global__ __launch_bounds__(IP_THREADS) void gather_windows_kernel(const uint8_t* __restrict__ src, long src_bytes,
@@ -155,19 +127,6 @@ __global__ __launch_bounds__(IP_THREADS) void gather_windows_kernel(const uint8_
     }
 }
 
-// g = clamp(v * 127.5 + 127.5, 0, 255), then (A g + (F - A) orig) / F truncated: every product, sum and the quotient rounded on its own.
-__device__ __forceinline__ uint32_t ip_blend(float v, float a, float fa, float orig, float f) {
-#pragma clang fp contract(off)
-    v = v * 127.5f;
-    v = v + 127.5f;
-    v = fminf(fmaxf(v, 0.f), 255.f);
-    const float t1 = a * v;
-    const float t2 = fa * orig;
-    float s = t1 + t2;
-    s = s / f;
-    return (uint32_t)(uint8_t)(int)s;
-}
-
 __global__ __launch_bounds__(IP_THREADS) void paste_back_kernel(uint8_t* __restrict__ out, long img_bytes, const uint8_t* __restrict__ msk,
                                                                 long msk_bytes, const int* __restrict__ tab, long tab_elems,
                                                                 const float* __restrict__ fake, uint8_t* __restrict__ alpha, int R, int K,
@@ -179,116 +138,27 @@ __global__ __launch_bounds__(IP_THREADS) void paste_back_kernel(uint8_t* __restr
     const int y0 = (int)blockIdx.y * d.TB, c0 = (int)blockIdx.x * d.CW;
     if (y0 >= d.ch || c0 >= d.cw) return;
     const int y1 = min(y0 + d.TB, d.ch), rows = y1 - y0, cn = min(d.CW, d.cw - c0);
-    const int F = feather + 1, HALO = feather;
-    const int th = rows + 2 * HALO, tw = cn + 2 * HALO, twp = (tw + 3) & ~3;
+    const int F = feather + 1;
     const int sy0 = max(tab[d.vb + 2 * y0], 0);
     const int sy1 = (int)min((long)tab[d.vb + 2 * (y1 - 1)] + tab[d.vb + 2 * (y1 - 1) + 1], (long)R);
     const int span = sy1 - sy0;                                     // rows of fake under the band
-    // carves: flag (16 bytes), A [rows][cn]  |  hole flags [th][twp], row distances [th][cn]   (steps 1-2)
-    //                                        |  horizontally resampled rows, float [span][3 cn] (step 3, over the same bytes)
-    const int a_bytes = 16 + ip_align16(rows * cn), t_bytes = ip_align16(th * twp), r_bytes = ip_align16(th * cn);
-    if (span < 1 || (long)a_bytes + max((long)t_bytes + r_bytes, 12L * span * cn) > lds_bytes) return;
-    int* flag = reinterpret_cast<int*>(ip_lds);
-    uint8_t* A = ip_lds + 16;
-    uint8_t* tile = ip_lds + a_bytes;
-    uint8_t* rowd = tile + t_bytes;
-    float* mid = reinterpret_cast<float*>(ip_lds + a_bytes);
-
-    // 1. hole flags of the tile and its halo
-    for (int e = threadIdx.x; e < t_bytes >> 2; e += IP_THREADS) reinterpret_cast<uint32_t*>(tile)[e] = 0u;
-    if (threadIdx.x == 0) *flag = 0;
-    __syncthreads();
-    const uint8_t* mwin = msk + d.moff + (long)d.wy0 * d.w + d.wx0;
-    const int ca = max(c0 - HALO, 0), cb = min(c0 + cn + HALO, d.cw), nbm = cb - ca;       // window columns staged
-    const int um = (tw + 6) >> 2;                                                           // aligned words a staged row can touch
-    int found = 0;
-    for (int e = threadIdx.x; e < th * um; e += IP_THREADS) {
-        const int tr = e / um, u = e - tr * um, wr = y0 - HALO + tr;
-        if (wr < 0 || wr >= d.ch) continue;
-        const uint8_t* p = mwin + (long)wr * d.w + ca;
-        const int lo = 4 * u - (int)(reinterpret_cast<uintptr_t>(p) & 3);
-        if (lo >= nbm || lo + 4 <= 0) continue;
-        uint8_t* trow = tile + tr * twp + (ca - (c0 - HALO));
-        if (lo >= 0 && lo + 4 <= nbm) {
-            const uint32_t v = *reinterpret_cast<const uint32_t*>(p + lo);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int hole = ((v >> (8 * q)) & 255u) == 0u;
-                trow[lo + q] = (uint8_t)hole;
-                found |= hole;
-            }
-        } else {
-            for (int q = max(lo, 0); q < min(lo + 4, nbm); ++q) {
-                const int hole = p[q] == 0;
-                trow[q] = (uint8_t)hole;
-                found |= hole;
-            }
-        }
-    }
-    if (found) *flag = 1;                                           // (every writer stores the same value)
-    __syncthreads();
-    if (*flag == 0) return;                                         // no hole within `feather` of the tile: A = 0, nothing to store
-
-    // 2. row pass, column pass
-    for (int e = threadIdx.x; e < th * cn; e += IP_THREADS) {
-        const int tr = e / cn, c = e - tr * cn;
-        const uint8_t* t = tile + tr * twp + c + HALO;
-        int rd = F;
-        for (int dd = 0; dd <= HALO; ++dd)
-            if (t[-dd] | t[dd]) {
-                rd = dd;
-                break;
-            }
-        rowd[tr * cn + c] = (uint8_t)rd;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < rows * cn; e += IP_THREADS) {
-        const int r = e / cn, c = e - r * cn;
-        const uint8_t* q = rowd + (r + HALO) * cn + c;
-        int best = q[0];
-        for (int dd = 1; dd < best && dd <= HALO; ++dd) best = min(best, max(dd, min((int)q[-dd * cn], (int)q[dd * cn])));
-        A[e] = (uint8_t)(F - best);
-    }
-    __syncthreads();                                                // A complete; the flags and row distances are dead from here on
+    IpTile t;
+    ip_tile_make(t, ip_lds, y0, c0, rows, cn, feather);
+    if (span < 1 || (long)t.a_bytes + max((long)t.t_bytes + t.r_bytes, 12L * span * cn) > lds_bytes) return;
+    // 1.-2. the feather weight; a tile without a hole within `feather` has A = 0 everywhere: nothing to store
+    if (!ip_feather_tile(t, msk, d, feather)) return;
+    const uint8_t* A = t.A;
+    float* mid = t.mid;
 
     const int uo = (3 * cn + 6) >> 2;                               // aligned words a destination row of the chunk can touch
-    if (alpha) {
-        const int ua = (cn + 6) >> 2;
-        for (int e = threadIdx.x; e < rows * ua; e += IP_THREADS) {
-            const int r = e / ua, u = e - r * ua;
-            uint8_t* p = alpha + d.moff + (long)(d.wy0 + y0 + r) * d.w + d.wx0 + c0;
-            const int lo = 4 * u - (int)(reinterpret_cast<uintptr_t>(p) & 3);
-            if (lo >= cn || lo + 4 <= 0) continue;
-            const uint8_t* ar = A + r * cn;
-            if (lo >= 0 && lo + 4 <= cn) {
-                *reinterpret_cast<uint32_t*>(p + lo) = (uint32_t)ar[lo] | (uint32_t)ar[lo + 1] << 8 | (uint32_t)ar[lo + 2] << 16 | (uint32_t)ar[lo + 3] << 24;
-            } else {
-                for (int q = max(lo, 0); q < min(lo + 4, cn); ++q) p[q] = ar[q];
-            }
-        }
-    }
+    if (alpha) ip_store_alpha(t, alpha, d);
 
     // 3. per sample: horizontal pass into LDS, then vertical pass + blend, one lane per destination word
     const long RR = (long)R * R;
     const float ff = (float)F;
     for (int k = 0; k < K; ++k) {
         const float* fk = fake + ((long)b * K + k) * 3 * RR;
-        for (int e = threadIdx.x; e < span * cn; e += IP_THREADS) {
-            const int r = e / cn, c = e - r * cn, x = c0 + c;
-            int xmin = tab[d.hb + 2 * x], n = tab[d.hb + 2 * x + 1];
-            if (xmin < 0 || n < 0 || n > d.KH || (long)xmin + n > R) xmin = 0, n = 0;
-            const float* p = fk + (long)(sy0 + r) * R + xmin;
-            const int* wk = tab + d.hk + (long)x * d.KH;
-            float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-            for (int j = 0; j < n; ++j) {
-                const float wj = __int_as_float(wk[j]);
-                s0 = fmaf(wj, p[j], s0);
-                s1 = fmaf(wj, p[RR + j], s1);
-                s2 = fmaf(wj, p[2 * RR + j], s2);
-            }
-            float* m = mid + (r * cn + c) * 3;
-            m[0] = s0, m[1] = s1, m[2] = s2;
-        }
+        ip_resample_rows(t, tab, d, fk, R, sy0, span);
         __syncthreads();
         uint8_t* outk = out + (long)k * img_bytes + d.off;
         for (int e = threadIdx.x; e < rows * uo; e += IP_THREADS) {
@@ -311,11 +181,10 @@ __global__ __launch_bounds__(IP_THREADS) void paste_back_kernel(uint8_t* __restr
             for (int q = q0; q < q1; ++q) {
                 const int a = ar[q / 3];
                 if (!a) continue;
-                float v = 0.f;
-                for (int j = 0; j < n; ++j) v = fmaf(__int_as_float(wk[j]), m[j * nb + q], v);
+                const float v = ip_resample_col(wk, m, n, nb, q);
                 const int sh = 8 * (q - lo);
                 const float orig = whole ? (float)((word >> sh) & 255u) : (float)p[q];
-                const uint32_t o = ip_blend(v, (float)a, (float)(F - a), orig, ff);
+                const uint32_t o = ip_mix(ip_scale(v), (float)a, (float)(F - a), orig, ff);
                 if (whole) word = (word & ~(255u << sh)) | o << sh;
                 else p[q] = (uint8_t)o;
             }

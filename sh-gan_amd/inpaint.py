@@ -11,7 +11,13 @@ of ``pack_images`` -- the masks then lie back to back in the same order -- or [B
     The image bytes are Pillow's ``crop(box).resize((R, R), BICUBIC)``; a low-resolution pixel is known iff its whole native footprint is.
   * ``paste_back``: one launch over the windows of K copies of the originals: feather weight A from the native mask (Chebyshev distance,
     an integer 0 .. feather + 1), float32 bicubic resample of the generator's output to the window, scale, blend, truncation.
-  * ``Inpainter``: plan, pack, gather -> assemble -> G -> paste, one device-to-host copy per chunk.
+  * ``paste_back_membrane``: the gradient-domain paste-back (csrc/membrane.hip): ``membrane_setup`` -> ``membrane_solve`` ->
+    ``membrane_paste``.  The generated window keeps its gradients and takes its level from the photograph at the rim of the blended
+    region Omega = {A > 0}: a membrane c with c = orig - g on the window pixels with A = 0 (0 outside the window) and a vanishing
+    5-point Laplacian in Omega is added to g before the feathered blend.  The solve is a multigrid V-cycle on the device with a
+    certified stop rule; INTEGRATION section S states the problem, the states and the workspace.
+  * ``Inpainter``: plan, pack, gather -> assemble -> G -> paste, one device-to-host copy per chunk; ``blend='membrane'`` selects the
+    gradient-domain paste-back.
 
 The arithmetic is stated with the kernels (csrc/inpaint.hip) and restated in numpy by tests/inpaint_f64.py."""
 import ctypes
@@ -26,6 +32,9 @@ from ._lib import check
 LDS_BYTES = 49152                    # csrc/inpaint.hip IP_LDS_BYTES
 DESC_INTS = 16                       # csrc/inpaint.hip IP_DESC
 MAX_FEATHER = 32                     # csrc/inpaint.hip IP_MAX_FEATHER
+MEMBRANE_TILE = 32                   # csrc/membrane.hip MB_TILE: the smoother's tile side
+MEMBRANE_COARSEST = 16               # csrc/membrane.hip MB_COARSEST: the largest side of a coarsest level
+MEMBRANE_MAX_CYCLES = 44             # default of membrane_solve: twice the largest count seen, 22
 _WEIGHT_CACHE = {}
 
 
@@ -296,6 +305,241 @@ def paste_back(packed, packed_mask, shapes, windows, fake, k=1, feather=8, out=N
     return out
 
 
+def _r4(n):
+    return (int(n) + 3) // 4 * 4
+
+
+class MembranePlan:
+    """Host side of a ``paste_back_membrane`` call (``membrane_plan``): ``grids`` int32 [B, 6] = (gy0, gx0, gh, gw, float offset, byte
+    offset) per image, the solve grid in window coordinates and where its planes [k][gh][gw][3] (in ``g`` and ``field``) and its Omega
+    bytes [gh][gw] start; ``table`` int32 [B k, 4] = (gh, gw, float offset, byte offset), the solver's problems, row n k + j = sample j of
+    image n (the k samples of an image share its Omega offset); ``n`` int64 [B k], the shorter side of Omega's bounding box (the stop
+    rule's n); ``g_elems`` / ``omega_bytes`` / ``ws_bytes``: the sizes of g and field (floats each), of omega and of the solver's
+    workspace; ``max_h`` / ``max_w``: the largest grid sides."""
+    __slots__ = ('grids', 'table', 'n', 'g_elems', 'omega_bytes', 'ws_bytes', 'max_h', 'max_w', 'k')
+
+
+def membrane_workspace_bytes(P, max_h, max_w):
+    """Bytes of ``membrane_solve``'s workspace for P problems of at most max_h x max_w: per problem the level-0 shadow (12 h w), one
+    float per 32 x 32 tile, and per coarse level (h_l, w_l) = (ceil(h_{l-1} / 2), ceil(w_{l-1} / 2)) 36 h_l w_l + h_l w_l bytes (each
+    array rounded up to 16 bytes) -- about 24.3 bytes per pixel of the largest grid."""
+    n = int(_lib.get_lib().shg_membrane_workspace_bytes(int(P), int(max_h), int(max_w)))
+    if n == 0:
+        raise ValueError(f'membrane: P >= 1 and grid sides in 1..16384 are required (got {P}, {max_h} x {max_w})')
+    return n
+
+
+def membrane_plan(shapes, windows, feather, k, boxes=None):
+    """-> ``MembranePlan``, integers only.  ``boxes``: host int [B, 4] = (ya, yb, xa, xb), a box of image n that holds every hole pixel of
+    its window (``Inpainter`` passes the hole's bounding box).  Omega's bounding box is then the box clipped to the window, grown by
+    ``feather`` and clipped again; the solve grid is that grown by one ring and clipped to the window.  Without ``boxes`` both are the
+    whole window (the same membrane; more workspace)."""
+    geo = _geometry(shapes, windows, 'membrane_plan')
+    k, feather = int(k), int(feather)
+    if k < 1 or not 0 <= feather <= MAX_FEATHER:
+        raise ValueError(f'membrane_plan: k must be >= 1 and feather in 0..{MAX_FEATHER} (got {k}, {feather})')
+    B = geo.shape[0]
+    if boxes is not None:
+        boxes = _host(boxes).astype(np.int64).reshape(-1, 4)
+        if boxes.shape[0] != B:
+            raise ValueError(f'membrane_plan: {B} images but {boxes.shape[0]} boxes')
+    plan = MembranePlan()
+    plan.k = k
+    plan.grids, plan.table, plan.n = np.zeros((B, 6), np.int64), np.zeros((B * k, 4), np.int64), np.zeros(B * k, np.int64)
+    foff = ooff = 0
+    for i, (h, w, off, moff, y0, x0, ch, cw) in enumerate(geo):
+        ya, yb, xa, xb = 0, ch, 0, cw
+        if boxes is not None:
+            ya, yb, xa, xb = max(boxes[i, 0] - y0, 0), min(boxes[i, 1] - y0, ch), max(boxes[i, 2] - x0, 0), min(boxes[i, 3] - x0, cw)
+            if ya >= yb or xa >= xb:
+                raise ValueError(f'membrane_plan: the box of image {i} does not meet its window')
+            ya, yb, xa, xb = max(ya - feather, 0), min(yb + feather, ch), max(xa - feather, 0), min(xb + feather, cw)
+        n = min(yb - ya, xb - xa)
+        gy0, gy1, gx0, gx1 = max(ya - 1, 0), min(yb + 1, ch), max(xa - 1, 0), min(xb + 1, cw)
+        gh, gw = gy1 - gy0, gx1 - gx0
+        plan.grids[i] = (gy0, gx0, gh, gw, foff, ooff)
+        for j in range(k):
+            plan.table[i * k + j] = (gh, gw, foff + j * 3 * gh * gw, ooff)
+            plan.n[i * k + j] = n
+        foff, ooff = _r4(foff + 3 * k * gh * gw), _r4(ooff + gh * gw)
+    if foff >= 2 ** 31:
+        raise ValueError('membrane_plan: the solve grids of a call hold at most 2^31 floats')
+    plan.g_elems, plan.omega_bytes = int(foff), int(ooff)
+    plan.max_h, plan.max_w = int(plan.grids[:, 2].max()), int(plan.grids[:, 3].max())
+    plan.ws_bytes = membrane_workspace_bytes(B * k, plan.max_h, plan.max_w)
+    plan.grids, plan.table = plan.grids.astype(np.int32), plan.table.astype(np.int32)
+    return plan
+
+
+def _f32_flat(launch, t, name, what, elems):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= elems):
+        raise _lib.ShgError(f'{what}: {name} must be a contiguous float32 HIP tensor of at least {elems} elements')
+    launch._own(t, name)
+    return t
+
+
+def _membrane_operands(launch, what, packed, packed_mask, shapes, windows, plan, feather, R):
+    packed = _u8_flat(launch, packed, 'packed', what)
+    packed_mask = _u8_flat(launch, packed_mask, 'packed_mask', what)
+    feather = int(feather)
+    if not 0 <= feather <= MAX_FEATHER:
+        raise _lib.ShgError(f'{what}: feather must lie in 0..{MAX_FEATHER} (got {feather})')
+    geo = _geometry(shapes, windows, what)
+    if not isinstance(plan, MembranePlan) or plan.grids.shape[0] != geo.shape[0]:
+        raise _lib.ShgError(f'{what}: plan must be the MembranePlan of these {geo.shape[0]} images')
+    _check_extent(geo, packed.numel(), packed_mask.numel(), what)
+    table, chunks, bands, lds_bytes = build_paste_table(geo[:, :4], geo[:, 4:], R, feather)
+    return packed, packed_mask, geo, table, chunks, bands, lds_bytes
+
+
+def membrane_setup(packed, packed_mask, shapes, windows, fake, plan, g, field, omega, feather=8, stream=None):
+    """First step of ``paste_back_membrane``: inside the solve grids of ``plan`` write ``g`` (float32 [plan.g_elems]: the resampled, scaled
+    generator output, the bits ``paste_back`` blends), ``field`` (same layout: orig - g where the feather weight A is 0, 0 where A > 0)
+    and ``omega`` (uint8 [plan.omega_bytes]: A > 0).  One launch."""
+    launch = kernels._Launch()
+    B, k = plan.grids.shape[0] if isinstance(plan, MembranePlan) else 0, getattr(plan, 'k', 0)
+    if not isinstance(fake, torch.Tensor) or fake.ndim != 4 or fake.shape[0] != B * k or fake.shape[1] != 3 or fake.shape[2] != fake.shape[3]:
+        raise _lib.ShgError(f'membrane_setup: fake must be float32 [{B * k}, 3, R, R] (got {tuple(getattr(fake, "shape", ()))})')
+    R = fake.shape[2]
+    packed, packed_mask, geo, table, chunks, bands, lds_bytes = _membrane_operands(launch, 'membrane_setup', packed, packed_mask, shapes, windows,
+                                                                                   plan, feather, R)
+    fake = launch.req(fake, 'fake')
+    g = _f32_flat(launch, g, 'g', 'membrane_setup', plan.g_elems)
+    field = _f32_flat(launch, field, 'field', 'membrane_setup', plan.g_elems)
+    if not (isinstance(omega, torch.Tensor) and omega.is_cuda and omega.dtype == torch.uint8 and omega.is_contiguous() and omega.numel() >= plan.omega_bytes):
+        raise _lib.ShgError(f'membrane_setup: omega must be a contiguous uint8 HIP tensor of at least {plan.omega_bytes} bytes')
+    launch._own(omega, 'omega')
+    st = stream if stream is not None else torch.cuda.current_stream(launch.dev)
+    with launch, torch.cuda.stream(st):
+        tab, grids = _upload(table, launch.dev), _upload(plan.grids.reshape(-1), launch.dev)
+        check(_lib.get_lib().shg_inpaint_membrane_setup_f32(kernels._ptr(packed), packed.numel(), kernels._ptr(packed_mask), packed_mask.numel(),
+                                                            kernels._ptr(tab), tab.numel(), kernels._ptr(grids), kernels._ptr(fake), kernels._ptr(g),
+                                                            kernels._ptr(field), g.numel(), kernels._ptr(omega), omega.numel(), B, k, R, int(feather),
+                                                            chunks, bands, lds_bytes, ctypes.c_void_p(st.cuda_stream)), 'membrane_setup')
+
+
+def membrane_solve(field, omega, table, tol=0.25, max_cycles=None, info_out=None, stream=None, n=None, ws=None):
+    """The masked Laplace solver alone.  ``table``: host int [P, 4] = (h, w, float offset into ``field``, byte offset into ``omega``);
+    problem p is field float32 [h][w][3] with omega uint8 [h][w] (non-zero = unknown); neighbours outside the h x w grid count as 0; the
+    problems' slices of ``field`` must not overlap (several may share an omega).  On return ``field`` holds the membrane c in Omega and is
+    untouched elsewhere.  Stop rule: the residual's max norm over Omega and the three channels <= 8 tol / (n + 1)^2, ``n`` (host int [P];
+    default min(h, w)) at least the shorter side of Omega's bounding box: then |c - c*| <= tol everywhere (state 1).  -> info, device
+    int32 [P, 3] = (cycles run, bits of the last residual norm as float32, state 1 certified / 2 stalled at the float32 floor / 0 out of
+    ``max_cycles``, default ``MEMBRANE_MAX_CYCLES``).  ``ws``: an optional uint8 workspace of ``membrane_workspace_bytes`` bytes, its
+    contents irrelevant.  A fixed sequence of launches on ``stream``; nothing is synchronised."""
+    launch = kernels._Launch()
+    table = _host(table).astype(np.int64).reshape(-1, 4)
+    P = table.shape[0]
+    if P < 1 or (table[:, :2] < 1).any() or (table[:, 2:] < 0).any() or np.abs(table).max() >= 2 ** 31:
+        raise _lib.ShgError('membrane_solve: table must be int [P, 4] = (h, w, field offset, omega offset) with h, w >= 1 and offsets >= 0')
+    need_f, need_o = int((table[:, 2] + 3 * table[:, 0] * table[:, 1]).max()), int((table[:, 3] + table[:, 0] * table[:, 1]).max())
+    field = _f32_flat(launch, field, 'field', 'membrane_solve', need_f)
+    if not (isinstance(omega, torch.Tensor) and omega.is_cuda and omega.dtype == torch.uint8 and omega.is_contiguous() and omega.numel() >= need_o):
+        raise _lib.ShgError(f'membrane_solve: omega must be a contiguous uint8 HIP tensor of at least {need_o} bytes')
+    launch._own(omega, 'omega')
+    order = np.argsort(table[:, 2], kind='stable')
+    ends = (table[:, 2] + 3 * table[:, 0] * table[:, 1])[order]
+    if (ends[:-1] > table[order[1:], 2]).any():
+        raise _lib.ShgError('membrane_solve: the problems overlap in field')
+    n = table[:, :2].min(axis=1) if n is None else _host(n).astype(np.int64).reshape(-1)
+    if n.shape[0] != P or (n < 1).any() or not float(tol) > 0.0:
+        raise _lib.ShgError(f'membrane_solve: tol > 0 and one n >= 1 per problem are required (got tol = {tol}, {n.shape[0]} values of n)')
+    res_tol = (8.0 * float(tol) / (n.astype(np.float64) + 1.0) ** 2).astype(np.float32)
+    max_cycles = MEMBRANE_MAX_CYCLES if max_cycles is None else int(max_cycles)
+    if not 0 <= max_cycles <= 1024:
+        raise _lib.ShgError(f'membrane_solve: max_cycles must lie in 0..1024 (got {max_cycles})')
+    max_h, max_w = int(table[:, 0].max()), int(table[:, 1].max())
+    ws_bytes = membrane_workspace_bytes(P, max_h, max_w)
+    if ws is not None:
+        if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= ws_bytes):
+            raise _lib.ShgError(f'membrane_solve: ws must be a contiguous uint8 HIP tensor of at least {ws_bytes} bytes')
+        launch._own(ws, 'ws')
+    if info_out is not None:
+        if not (isinstance(info_out, torch.Tensor) and info_out.is_cuda and info_out.dtype == torch.int32 and info_out.is_contiguous()
+                and tuple(info_out.shape) == (P, 3)):
+            raise _lib.ShgError(f'membrane_solve: info_out must be a contiguous int32 HIP tensor [{P}, 3]')
+        launch._own(info_out, 'info_out')
+    st = stream if stream is not None else torch.cuda.current_stream(launch.dev)
+    with launch, torch.cuda.stream(st):
+        tab = _upload(table.astype(np.int32).reshape(-1), launch.dev)
+        rt = _upload(res_tol, launch.dev)
+        if ws is None:
+            ws = launch.new((ws_bytes,), torch.uint8)
+        info = launch.new((P, 3), torch.int32) if info_out is None else info_out
+        check(_lib.get_lib().shg_membrane_solve_f32(kernels._ptr(field), field.numel(), kernels._ptr(omega), omega.numel(), kernels._ptr(tab), P,
+                                                    kernels._ptr(rt), max_cycles, max_h, max_w, kernels._ptr(ws), ws.numel(), kernels._ptr(info),
+                                                    ctypes.c_void_p(st.cuda_stream)), 'membrane_solve')
+    return info
+
+
+def membrane_paste(packed_mask, shapes, windows, plan, g, field, out, R, feather=8, alpha_out=None, stream=None):
+    """Last step of ``paste_back_membrane``: ``paste_back``'s blend with clamp(g + c, 0, 255) in place of g (``field`` holds c in Omega),
+    into ``out`` uint8 [k, bytes], every row a copy of the packed originals on entry.  One launch."""
+    launch = kernels._Launch()
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.ndim == 2 and out.is_contiguous()
+            and out.shape[0] == getattr(plan, 'k', 0)):
+        raise _lib.ShgError(f'membrane_paste: out must be a contiguous uint8 HIP tensor [{getattr(plan, "k", 0)}, bytes]')
+    k, n = out.shape
+    _, packed_mask, geo, table, chunks, bands, lds_bytes = _membrane_operands(launch, 'membrane_paste', out.view(-1)[:n], packed_mask, shapes, windows,
+                                                                              plan, feather, int(R))
+    g = _f32_flat(launch, g, 'g', 'membrane_paste', plan.g_elems)
+    field = _f32_flat(launch, field, 'field', 'membrane_paste', plan.g_elems)
+    if alpha_out is not None:
+        if not (isinstance(alpha_out, torch.Tensor) and alpha_out.is_cuda and alpha_out.dtype == torch.uint8 and alpha_out.is_contiguous()
+                and alpha_out.numel() == packed_mask.numel()):
+            raise _lib.ShgError(f'membrane_paste: alpha_out must be a contiguous uint8 HIP tensor of {packed_mask.numel()} bytes')
+        launch._own(alpha_out, 'alpha_out')
+    st = stream if stream is not None else torch.cuda.current_stream(launch.dev)
+    with launch, torch.cuda.stream(st):
+        tab, grids = _upload(table, launch.dev), _upload(plan.grids.reshape(-1), launch.dev)
+        if alpha_out is not None:
+            alpha_out.zero_()
+        check(_lib.get_lib().shg_inpaint_membrane_paste_u8(kernels._ptr(out), n, kernels._ptr(packed_mask), packed_mask.numel(), kernels._ptr(tab),
+                                                           tab.numel(), kernels._ptr(grids), kernels._ptr(g), kernels._ptr(field), g.numel(),
+                                                           kernels._ptr(alpha_out), geo.shape[0], k, int(R), int(feather), chunks, bands, lds_bytes,
+                                                           ctypes.c_void_p(st.cuda_stream)), 'membrane_paste')
+    return out
+
+
+def paste_back_membrane(packed, packed_mask, shapes, windows, fake, k=1, feather=8, tol=0.25, out=None, alpha_out=None, info_out=None, stream=None,
+                        boxes=None, max_cycles=None):
+    """``paste_back`` with the gradient-domain blend: same operands, same result layout, the same bytes wherever the feather weight is 0.
+    In Omega = {A > 0} the blended value is clamp(g + c, 0, 255) instead of g, c the membrane of the module's docstring, solved to ``tol``
+    grey levels where float32 allows (``info_out``, int32 [B k, 3], receives ``membrane_solve``'s info; state 2 = the float32 floor, see
+    INTEGRATION section S).  ``boxes``: see ``membrane_plan``.  Workspaces (g, field, omega, the solver's) are allocated per call.
+    Launches on ``stream`` (default: the current stream), no synchronisation."""
+    launch = kernels._Launch()
+    packed = _u8_flat(launch, packed, 'packed', 'paste_back_membrane')
+    k, feather = int(k), int(feather)
+    if k < 1 or not 0 <= feather <= MAX_FEATHER:
+        raise _lib.ShgError(f'paste_back_membrane: k must be >= 1 and feather in 0..{MAX_FEATHER} (got {k}, {feather})')
+    geo = _geometry(shapes, windows, 'paste_back_membrane')
+    B = geo.shape[0]
+    if not isinstance(fake, torch.Tensor) or fake.ndim != 4 or fake.shape[0] != B * k or fake.shape[1] != 3 or fake.shape[2] != fake.shape[3]:
+        raise _lib.ShgError(f'paste_back_membrane: fake must be float32 [{B * k}, 3, R, R] (got {tuple(getattr(fake, "shape", ()))})')
+    n = packed.numel()
+    if out is not None:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (k, n) and out.is_contiguous()):
+            raise _lib.ShgError(f'paste_back_membrane: out must be a contiguous uint8 HIP tensor [{k}, {n}]')
+        if out.data_ptr() < packed.data_ptr() + n and packed.data_ptr() < out.data_ptr() + k * n:
+            raise _lib.ShgError('paste_back_membrane: out overlaps packed')
+        launch._own(out, 'out')
+    plan = membrane_plan(geo[:, :4], geo[:, 4:], feather, k, boxes)
+    st = stream if stream is not None else torch.cuda.current_stream(launch.dev)
+    with launch, torch.cuda.stream(st):
+        g = launch.new((plan.g_elems,), torch.float32)
+        field = launch.new((plan.g_elems,), torch.float32)
+        omega = launch.new((plan.omega_bytes,), torch.uint8)
+        ws = launch.new((plan.ws_bytes,), torch.uint8)
+        if out is None:
+            out = launch.new((k, n), torch.uint8)
+        out.copy_(packed.view(1, n).expand(k, n))
+        membrane_setup(packed, packed_mask, geo[:, :4], geo[:, 4:], fake, plan, g, field, omega, feather, st)
+        membrane_solve(field, omega, plan.table, tol, max_cycles, info_out, st, plan.n, ws)
+        membrane_paste(packed_mask, geo[:, :4], geo[:, 4:], plan, g, field, out, fake.shape[2], feather, alpha_out, st)
+    return out
+
+
 class Inpainter:
     """``Inpainter(G, resolution, device)(images, masks)`` -> the images with their holes filled.
 
@@ -305,15 +549,22 @@ class Inpainter:
     image, or [samples, h, w, 3] when ``samples > 1``.  An image without a hole comes back as a copy and never reaches the device.  Images
     are processed in chunks of ``batch``; a chunk is one upload, the launches (no host synchronisation between them) and one
     device-to-host copy.  ``gather_fn`` / ``paste_fn`` (the signatures of ``gather_windows`` / ``paste_back``) and ``G`` can be replaced,
-    so the flow also runs on the host with reference functions and a stand-in generator."""
+    so the flow also runs on the host with reference functions and a stand-in generator.  ``blend``: 'feather' (``paste_back``) or
+    'membrane' (``paste_back_membrane``, with the holes' bounding boxes as ``boxes``; ``info`` then holds the solver's info of the last
+    call, one int32 [images samples, 3] array per chunk, fetched with a second small copy).  A given ``paste_fn`` is called as
+    ``paste_back`` is, whatever ``blend`` says."""
 
-    def __init__(self, G, resolution, device, context=0.5, feather=8, noise_mode='const', batch=16, gather_fn=None, paste_fn=None):
+    def __init__(self, G, resolution, device, context=0.5, feather=8, noise_mode='const', batch=16, gather_fn=None, paste_fn=None, blend='feather'):
         if int(batch) < 1 or not 0 <= int(feather) <= MAX_FEATHER or int(resolution) < 1:
             raise ValueError(f'Inpainter: batch >= 1, resolution >= 1 and feather in 0..{MAX_FEATHER} are required')
+        if blend not in ('feather', 'membrane'):
+            raise ValueError(f"Inpainter: blend must be 'feather' or 'membrane' (got {blend!r})")
+        self.blend, self.info = blend, []
+        self._own_membrane = blend == 'membrane' and paste_fn is None
         self.G, self.resolution, self.device = G, int(resolution), torch.device(device)
         self.context, self.feather, self.noise_mode, self.batch = float(context), int(feather), noise_mode, int(batch)
         self.gather_fn = gather_windows if gather_fn is None else gather_fn
-        self.paste_fn = paste_back if paste_fn is None else paste_fn
+        self.paste_fn = (paste_back_membrane if blend == 'membrane' else paste_back) if paste_fn is None else paste_fn
 
     def _latents(self, n, samples, seed, first):
         """z of images first .. first + n - 1 of the call: image i, sample j draws from the generator seeded ``seed + i`` (so a result does
@@ -339,8 +590,21 @@ class Inpainter:
                 fake = fake.reshape((-1,) + tuple(fake.shape[2:]))
             else:
                 fake = self.G(x=x, z=z[:, 0], c=z[:, 0, :0], noise_mode=self.noise_mode)
-            out = self.paste_fn(packed, packed_mask, shapes, windows, fake.float(), k=samples, feather=self.feather)
+            if self._own_membrane:
+                boxes = []
+                for mk in masks:
+                    hole = np.asarray(mk) == 0
+                    rows, cols = np.flatnonzero(hole.any(axis=1)), np.flatnonzero(hole.any(axis=0))
+                    boxes.append((rows[0], rows[-1] + 1, cols[0], cols[-1] + 1))
+                launch = kernels._Launch()
+                launch._own(packed, 'packed')
+                info = launch.new((len(images) * samples, 3), torch.int32)
+                out = self.paste_fn(packed, packed_mask, shapes, windows, fake.float(), k=samples, feather=self.feather, info_out=info, boxes=boxes)
+            else:
+                out = self.paste_fn(packed, packed_mask, shapes, windows, fake.float(), k=samples, feather=self.feather)
         host = out.cpu().numpy()                                                    # the chunk's one device-to-host copy (it synchronises)
+        if self._own_membrane:
+            self.info.append(info.cpu().numpy())
         res = []
         for (h, w, off) in shapes[:, :3]:
             a = host[:, off:off + 3 * h * w].reshape(samples, h, w, 3)
@@ -365,6 +629,7 @@ class Inpainter:
             if z.ndim != 3 or z.shape[0] != len(images) or z.shape[1] != samples:
                 raise ValueError(f'Inpainter: z must be [{len(images)}, z_dim] or [{len(images)}, {samples}, z_dim] (got {tuple(z.shape)})')
         result = [None] * len(images)
+        self.info = []
         for i, wnd in enumerate(windows):
             if wnd is None:
                 result[i] = np.broadcast_to(images[i], (samples,) + images[i].shape).copy() if samples > 1 else images[i].copy()
