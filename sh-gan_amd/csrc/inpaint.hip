@@ -3,11 +3,11 @@
 // with a feathered weight (paste_back).  Images are decoded uint8 HWC RGB packed back to back (resize.pack_images), masks uint8 HW packed
 // the same way (1 / non-zero = known, 0 = hole), each image with a window {y0, x0, ch, cw} that lies inside it.
 //
-// gather_windows.  Image: the bytes of Pillow's Image.crop(box).resize((R, R), BICUBIC) -- the integer arithmetic of resize.hip on the
+// gather_windows.  Image: the bytes of Pillow's Image.crop(box).resize((R, R), BICUBIC) -- the integer passes of pillow_resample.h on the
 // fixed-point tables of (cw -> R) and (ch -> R), the source read at the image's own row pitch from the window origin (nothing is copied
 // first).  Mask: output pixel (i, j) is known iff every native pixel of rows [i ch / R, max(ceil((i + 1) ch / R), lo + 1)) x the same
 // columns is known (integers; conservative: no hole pixel lies outside the low-resolution hole).  One workgroup = (image, band of TB
-// output rows, chunk of CW output columns), as in resize.hip.
+// output rows, chunk of CW output columns), as pillow_resample.h tiles a launch.
 //
 // paste_back, for a pixel p of the window, F = feather + 1:
 //   d(p) = Chebyshev distance to the nearest hole pixel inside the window,  A(p) = max(0, F - d(p))              (an integer 0..F)
@@ -37,80 +37,26 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t ip_clip8(int s) {
-    s >>= IP_BITS;
-    return (uint32_t)min(max(s, 0), 255);
-}
+static_assert(IP_THREADS == PIL_THREADS, "gather_windows runs pil_resample_tile on its own block size");
 
 __global__ __launch_bounds__(IP_THREADS) void gather_windows_kernel(const uint8_t* __restrict__ src, long src_bytes,
                                                                     const uint8_t* __restrict__ msk, long msk_bytes,
                                                                     const int* __restrict__ tab, long tab_elems, uint8_t* __restrict__ dst,
                                                                     float* __restrict__ mdst, int R, int lds_bytes) {
     extern __shared__ __attribute__((aligned(16))) uint8_t ip_lds[];
-    uint8_t* mid = ip_lds;
     const int b = blockIdx.z;
     IpDesc d;
     if (!ip_load_desc(tab, tab_elems, b, src_bytes, msk_bytes, true, R, d)) return;
     const int y0 = (int)blockIdx.y * d.TB, c0 = (int)blockIdx.x * d.CW;
     if (y0 >= R || c0 >= R) return;
-    const int y1 = min(y0 + d.TB, R), cn = min(d.CW, R - c0);
-    const int cwp = (cn + 3) & ~3;                                  // LDS row pitch: 4-byte reads in the vertical pass
-    const int sy0 = max(tab[d.vb + 2 * y0], 0);
-    const int sy1 = (int)min((long)tab[d.vb + 2 * (y1 - 1)] + tab[d.vb + 2 * (y1 - 1) + 1], (long)d.ch);
-    const int span = sy1 - sy0;                                     // window rows of the band
-    if (span < 1 || 3L * span * cwp > lds_bytes) return;
+    const int y1 = min(y0 + d.TB, R), rows = y1 - y0, cn = min(d.CW, R - c0);
 
-    // horizontal pass: one lane = one (window row, output column), three channels
+    // image: the window, read at the image's row pitch from the window origin
     const long pitch = (long)d.w * 3;
     const uint8_t* win = src + d.off + (long)d.wy0 * pitch + (long)d.wx0 * 3;
-    for (int e = threadIdx.x; e < span * cn; e += IP_THREADS) {
-        const int r = e / cn, c = e - r * cn, x = c0 + c;
-        int xmin = tab[d.hb + 2 * x], n = tab[d.hb + 2 * x + 1];
-        if (xmin < 0 || n < 0 || n > d.KH || (long)xmin + n > d.cw) xmin = 0, n = 0;
-        const uint8_t* p = win + (long)(sy0 + r) * pitch + xmin * 3;
-        const int* k = tab + d.hk + (long)x * d.KH;
-        int s0 = 1 << (IP_BITS - 1), s1 = s0, s2 = s0;
-        for (int j = 0; j < n; ++j) {
-            const int kj = k[j];
-            s0 += (int)p[3 * j] * kj;
-            s1 += (int)p[3 * j + 1] * kj;
-            s2 += (int)p[3 * j + 2] * kj;
-        }
-        mid[(0 * span + r) * cwp + c] = (uint8_t)ip_clip8(s0);
-        mid[(1 * span + r) * cwp + c] = (uint8_t)ip_clip8(s1);
-        mid[(2 * span + r) * cwp + c] = (uint8_t)ip_clip8(s2);
-    }
-    __syncthreads();
-
-    // vertical pass: one lane = 4 consecutive output columns of one (channel, output row)
-    const int groups = cwp >> 2, rows = y1 - y0;
-    for (int e = threadIdx.x; e < 3 * rows * groups; e += IP_THREADS) {
-        const int g = e % groups, t = e / groups;
-        const int oy = y0 + t % rows, ch = t / rows;
-        int rel = tab[d.vb + 2 * oy] - sy0, n = tab[d.vb + 2 * oy + 1];
-        if (rel < 0 || n < 0 || n > d.KV || (long)rel + n > span) rel = 0, n = 0;
-        const uint8_t* m = mid + (ch * span + rel) * cwp + 4 * g;
-        const int* k = tab + d.vk + (long)oy * d.KV;
-        int a0 = 1 << (IP_BITS - 1), a1 = a0, a2 = a0, a3 = a0;
-        for (int j = 0; j < n; ++j) {
-            const uint32_t v = *reinterpret_cast<const uint32_t*>(m + j * cwp);
-            const int kj = k[j];
-            a0 += (int)(v & 255u) * kj;
-            a1 += (int)((v >> 8) & 255u) * kj;
-            a2 += (int)((v >> 16) & 255u) * kj;
-            a3 += (int)(v >> 24) * kj;
-        }
-        const uint32_t o0 = ip_clip8(a0), o1 = ip_clip8(a1), o2 = ip_clip8(a2), o3 = ip_clip8(a3);
-        const int c = c0 + 4 * g;                                   // first output column of the group (c0 % 4 == 0 on the host's tiling)
-        uint8_t* orow = dst + (((long)b * 3 + ch) * R + oy) * R;
-        const int nv = min(4, c0 + cn - c);
-        if (nv == 4 && (R & 3) == 0 && (c & 3) == 0) {
-            *reinterpret_cast<uint32_t*>(orow + c) = o0 | o1 << 8 | o2 << 16 | o3 << 24;
-        } else {
-            const uint32_t o[4] = {o0, o1, o2, o3};
-            for (int q = 0; q < nv; ++q) orow[c + q] = (uint8_t)o[q];
-        }
-    }
+    if (!pil_resample_tile<false>(ip_lds, lds_bytes, tab, {d.hb, d.hk, d.KH}, {d.vb, d.vk, d.KV}, win, pitch, d.ch, d.cw, y0, y1, c0, cn,
+                                  dst + (long)b * 3 * R * R, R, 0, R, R))
+        return;
 
     // mask: one lane = one output pixel, known iff its whole native footprint is known
     const uint8_t* mwin = msk + d.moff + (long)d.wy0 * d.w + d.wx0;

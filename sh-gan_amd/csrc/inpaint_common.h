@@ -2,14 +2,13 @@
 // descriptor check, the feather weight of a tile, the float32 resample chain of `fake` and the blend.  Both files compute A and g through
 // these functions, so the two paste-backs see the same bits.  The arithmetic is stated at the top of csrc/inpaint.hip.
 #pragma once
-#include "shg_common.h"
+#include "pillow_resample.h"
 
 namespace {
 
 constexpr int IP_THREADS = 256;
 constexpr int IP_LDS_BYTES = 49152;      // inpaint.py LDS_BYTES: the most a launch may ask for
 constexpr int IP_DESC = 16;              // inpaint.py DESC_INTS
-constexpr int IP_BITS = 22;
 constexpr int IP_MAX_FEATHER = 32;
 
 __device__ __forceinline__ int ip_align16(int n) { return (n + 15) & ~15; }
@@ -26,12 +25,9 @@ __device__ __forceinline__ bool ip_load_desc(const int* tab, long tab_elems, int
     if (d.h < 1 || d.w < 1 || d.off < 0 || d.moff < 0 || (long)d.off + (long)d.h * d.w * 3 > img_bytes || (long)d.moff + (long)d.h * d.w > msk_bytes)
         return false;
     if (d.wy0 < 0 || d.wx0 < 0 || d.ch < 1 || d.cw < 1 || (long)d.wy0 + d.ch > d.h || (long)d.wx0 + d.cw > d.w) return false;
-    if (d.TB < 1 || d.CW < 1 || d.TB > 4096 || d.CW > 4096 || d.KH < 1 || d.KV < 1) return false;      // (tile products stay inside int)
+    if (d.TB < 1 || d.CW < 1 || d.TB > 4096 || d.CW > 4096) return false;      // (tile products stay inside int)
     const long nh = out_is_r ? R : d.cw, nv = out_is_r ? R : d.ch;
-    if (d.hb < 0 || d.hk < 0 || d.vb < 0 || d.vk < 0 || (long)d.hb + 2 * nh > tab_elems || (long)d.hk + nh * d.KH > tab_elems ||
-        (long)d.vb + 2 * nv > tab_elems || (long)d.vk + nv * d.KV > tab_elems)
-        return false;
-    return true;
+    return pil_axis_ok(d.hb, d.hk, d.KH, nh, tab_elems) && pil_axis_ok(d.vb, d.vk, d.KV, nv, tab_elems);
 }
 
 // g = clamp(v * 127.5 + 127.5, 0, 255), every operation rounded on its own, as composite_u8_kernel writes it.

@@ -2,17 +2,8 @@
 // PIL Image.resize([R, R], BICUBIC)), with the formatter's horizontal flip of the resized image (FreeFormMaskFormatter, :214-229).
 // src: B packed HWC images of their own sizes; dst: uint8 [B,3,R,R] (NCHW, the evaluation loop's input).
 //
-// Pillow's 8-bit resample is integer arithmetic on fixed-point tables (22 fractional bits) built in double precision on the host
-// (resize.py) and passed in `table`; here only integers are added, so the result is Pillow's byte for byte:
-//   horizontal pass  mid = clip8((1 << 21 + sum_j src[y][xmin+j] * kh[x][j]) >> 22)    (uint8, as Pillow's intermediate image)
-//   vertical pass    out = clip8((1 << 21 + sum_j mid[ymin+j][x] * kv[y][j]) >> 22)
-// An axis that keeps its size carries the one-tap identity table (Pillow skips that pass: the same bytes).
-//
-// One launch.  One workgroup = one (image, band of TB output rows, chunk of CW output columns): the band's source rows are resampled
-// horizontally into LDS as three uint8 planes [rows][CW], then the vertical pass reads 4 columns per lane from LDS and writes them with
-// one 4-byte store per plane row (byte stores when R % 4 != 0 or at a chunk's ragged end).  The host picks TB and CW per image so that
-// the band fits lds_bytes (dynamic LDS, the batch's largest band, <= RS_LDS_BYTES).  No atomics, no inter-workgroup communication:
-// deterministic, and an image's bytes do not depend on its neighbours in the batch.
+// The arithmetic (Pillow's 8-bit fixed-point passes), the tiling of a launch into workgroups and its LDS use are stated in
+// csrc/pillow_resample.h, which holds both passes; the kernels here read their descriptors and call it.
 //
 // table (int32): B descriptors of RS_DESC ints {h, w, byte offset, flip, h-bounds, h-coefs, KH, v-bounds, v-coefs, KV, TB, CW}, then
 // bounds [R][2] = (first tap, taps) and coefficients [R][K] per axis at the offsets the descriptors name.  The kernel checks every
@@ -24,181 +15,45 @@
 // R x R canvas; the formatter's flip mirrors the whole canvas (FreeFormMaskFormatter, :148-166).  The same passes, with descriptors of
 // RS_FIT_DESC ints {the 12 above, h', w'} and per-axis tables [w'][..] / [h'][..]; the grid covers the R x R canvas and the workgroups
 // write the padding zeros themselves, so every byte of dst comes out of the one launch.
-#include "shg_common.h"
+#include "pillow_resample.h"
 
 namespace {
 
-constexpr int RS_THREADS = 256;
 constexpr int RS_LDS_BYTES = 49152;      // resize.py LDS_BYTES: the largest band a launch may ask for
 constexpr int RS_DESC = 12;              // resize.py DESC_INTS
 constexpr int RS_FIT_DESC = 14;          // resize.py FIT_DESC_INTS
-constexpr int RS_BITS = 22;
 
-__device__ __forceinline__ uint32_t rs_clip8(int s) {
-    s >>= RS_BITS;
-    return (uint32_t)min(max(s, 0), 255);
-}
-
-__global__ __launch_bounds__(RS_THREADS) void resize_bicubic_u8_kernel(const uint8_t* __restrict__ src, long src_bytes,
-                                                                       const int* __restrict__ tab, long tab_elems,
-                                                                       uint8_t* __restrict__ dst, int R, int lds_bytes) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t mid[];
+// One workgroup = one (image, band of TB canvas rows, chunk of CW canvas columns).  FIT: the descriptor carries the box (h', w') and the
+// tables describe the box; otherwise the box is the canvas.
+template <bool FIT>
+__device__ __forceinline__ void rs_resize_tile(uint8_t* mid, const uint8_t* __restrict__ src, long src_bytes, const int* __restrict__ tab,
+                                               long tab_elems, uint8_t* __restrict__ dst, int R, int lds_bytes) {
     const int b = blockIdx.z;
-    const int* d = tab + (long)b * RS_DESC;
-    const int h = d[0], w = d[1], off = d[2], flip = d[3];
-    const int hb = d[4], hk = d[5], KH = d[6], vb = d[7], vk = d[8], KV = d[9], TB = d[10], CW = d[11];
-    if (h < 1 || w < 1 || off < 0 || (long)off + (long)h * w * 3 > src_bytes || TB < 1 || CW < 1 || KH < 1 || KV < 1) return;
-    if (hb < 0 || hk < 0 || vb < 0 || vk < 0 || (long)hb + 2L * R > tab_elems || (long)hk + (long)R * KH > tab_elems ||
-        (long)vb + 2L * R > tab_elems || (long)vk + (long)R * KV > tab_elems)
-        return;
-    const int y0 = (int)blockIdx.y * TB, c0 = (int)blockIdx.x * CW;
-    if (y0 >= R || c0 >= R) return;
-    const int y1 = min(y0 + TB, R), cn = min(CW, R - c0);
-    const int cwp = (cn + 3) & ~3;                                  // LDS row pitch: 4-byte reads in the vertical pass
-    const int sy0 = max(tab[vb + 2 * y0], 0);
-    const int sy1 = (int)min((long)tab[vb + 2 * (y1 - 1)] + tab[vb + 2 * (y1 - 1) + 1], (long)h);
-    const int span = sy1 - sy0;                                     // source rows of the band
-    if (span < 1 || 3L * span * cwp > lds_bytes) return;
-
-    // horizontal pass: one lane = one (source row, output column), three channels
-    const uint8_t* img = src + off;
-    const long pitch = (long)w * 3;
-    for (int e = threadIdx.x; e < span * cn; e += RS_THREADS) {
-        const int r = e / cn, c = e - r * cn, x = c0 + c;
-        int xmin = tab[hb + 2 * x], n = tab[hb + 2 * x + 1];
-        if (xmin < 0 || n < 0 || n > KH || (long)xmin + n > w) xmin = 0, n = 0;
-        const uint8_t* p = img + (long)(sy0 + r) * pitch + xmin * 3;
-        const int* k = tab + hk + (long)x * KH;
-        int s0 = 1 << (RS_BITS - 1), s1 = s0, s2 = s0;
-        for (int j = 0; j < n; ++j) {
-            const int kj = k[j];
-            s0 += (int)p[3 * j] * kj;
-            s1 += (int)p[3 * j + 1] * kj;
-            s2 += (int)p[3 * j + 2] * kj;
-        }
-        mid[(0 * span + r) * cwp + c] = (uint8_t)rs_clip8(s0);
-        mid[(1 * span + r) * cwp + c] = (uint8_t)rs_clip8(s1);
-        mid[(2 * span + r) * cwp + c] = (uint8_t)rs_clip8(s2);
-    }
-    __syncthreads();
-
-    // vertical pass: one lane = 4 consecutive output columns of one (channel, output row)
-    const int groups = cwp >> 2, rows = y1 - y0;
-    for (int e = threadIdx.x; e < 3 * rows * groups; e += RS_THREADS) {
-        const int g = e % groups, t = e / groups;
-        const int oy = y0 + t % rows, ch = t / rows;
-        int rel = tab[vb + 2 * oy] - sy0, n = tab[vb + 2 * oy + 1];
-        if (rel < 0 || n < 0 || n > KV || (long)rel + n > span) rel = 0, n = 0;
-        const uint8_t* m = mid + (ch * span + rel) * cwp + 4 * g;
-        const int* k = tab + vk + (long)oy * KV;
-        int a0 = 1 << (RS_BITS - 1), a1 = a0, a2 = a0, a3 = a0;
-        for (int j = 0; j < n; ++j) {
-            const uint32_t v = *reinterpret_cast<const uint32_t*>(m + j * cwp);
-            const int kj = k[j];
-            a0 += (int)(v & 255u) * kj;
-            a1 += (int)((v >> 8) & 255u) * kj;
-            a2 += (int)((v >> 16) & 255u) * kj;
-            a3 += (int)(v >> 24) * kj;
-        }
-        const uint32_t o0 = rs_clip8(a0), o1 = rs_clip8(a1), o2 = rs_clip8(a2), o3 = rs_clip8(a3);
-        const int c = c0 + 4 * g;                                   // first output column of the group (c0 % 4 == 0 on the host's tiling)
-        uint8_t* orow = dst + (((long)b * 3 + ch) * R + oy) * R;
-        const int nv = min(4, c0 + cn - c);
-        if (nv == 4 && (R & 3) == 0 && (c & 3) == 0) {
-            const uint32_t word = flip ? (o3 | o2 << 8 | o1 << 16 | o0 << 24) : (o0 | o1 << 8 | o2 << 16 | o3 << 24);
-            *reinterpret_cast<uint32_t*>(orow + (flip ? R - 4 - c : c)) = word;
-        } else {
-            const uint32_t o[4] = {o0, o1, o2, o3};
-            for (int q = 0; q < nv; ++q) orow[flip ? R - 1 - c - q : c + q] = (uint8_t)o[q];
-        }
-    }
-}
-
-// One workgroup = one (image, band of TB canvas rows, chunk of CW canvas columns).  The part of the tile inside the image's box is
-// resampled as above; rows at or below h' take no taps (sum 1 << 21 -> 0), columns at or right of w' are stored as 0.
-__global__ __launch_bounds__(RS_THREADS) void resize_fit_pad_u8_kernel(const uint8_t* __restrict__ src, long src_bytes,
-                                                                       const int* __restrict__ tab, long tab_elems,
-                                                                       uint8_t* __restrict__ dst, int R, int lds_bytes) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t mid[];
-    const int b = blockIdx.z;
-    const int* d = tab + (long)b * RS_FIT_DESC;
-    const int h = d[0], w = d[1], off = d[2], flip = d[3];
-    const int hb = d[4], hk = d[5], KH = d[6], vb = d[7], vk = d[8], KV = d[9], TB = d[10], CW = d[11], oh = d[12], ow = d[13];
-    if (h < 1 || w < 1 || off < 0 || (long)off + (long)h * w * 3 > src_bytes || TB < 1 || CW < 1 || KH < 1 || KV < 1) return;
+    const int* d = tab + (long)b * (FIT ? RS_FIT_DESC : RS_DESC);
+    const int h = d[0], w = d[1], off = d[2], flip = d[3], TB = d[10], CW = d[11];
+    const PilAxis H = {d[4], d[5], d[6]}, V = {d[7], d[8], d[9]};
+    const int oh = FIT ? d[12] : R, ow = FIT ? d[13] : R;
+    if (h < 1 || w < 1 || off < 0 || (long)off + (long)h * w * 3 > src_bytes || TB < 1 || CW < 1) return;
     if (oh < 1 || oh > R || ow < 1 || ow > R) return;
-    if (hb < 0 || hk < 0 || vb < 0 || vk < 0 || (long)hb + 2L * ow > tab_elems || (long)hk + (long)ow * KH > tab_elems ||
-        (long)vb + 2L * oh > tab_elems || (long)vk + (long)oh * KV > tab_elems)
-        return;
+    if (!pil_axis_ok(H.bounds, H.coefs, H.K, ow, tab_elems) || !pil_axis_ok(V.bounds, V.coefs, V.K, oh, tab_elems)) return;
     const int y0 = (int)blockIdx.y * TB, c0 = (int)blockIdx.x * CW;
     if (y0 >= R || c0 >= R) return;
-    const int y1 = min(y0 + TB, R), cn = min(CW, R - c0);
-    const int cwp = (cn + 3) & ~3;                                  // LDS row pitch: 4-byte reads in the vertical pass
-    const int cc = min(c0 + cn, ow) - c0;                           // columns of the tile inside the box (<= 0: none)
-    const bool inside = y0 < oh && cc > 0;                          // workgroup-uniform
-    int sy0 = 0, span = 0;
-    if (inside) {
-        const int yl = min(y1, oh) - 1;                             // last box row of the band
-        sy0 = max(tab[vb + 2 * y0], 0);
-        const int sy1 = (int)min((long)tab[vb + 2 * yl] + tab[vb + 2 * yl + 1], (long)h);
-        span = sy1 - sy0;
-        if (span < 1 || 3L * span * cwp > lds_bytes) return;
+    pil_resample_tile<FIT>(mid, lds_bytes, tab, H, V, src + off, (long)w * 3, h, w, y0, min(y0 + TB, R), c0, min(CW, R - c0),
+                           dst + (long)b * 3 * R * R, R, flip, oh, ow);
+}
 
-        const uint8_t* img = src + off;
-        const long pitch = (long)w * 3;
-        for (int e = threadIdx.x; e < span * cc; e += RS_THREADS) {
-            const int r = e / cc, c = e - r * cc, x = c0 + c;
-            int xmin = tab[hb + 2 * x], n = tab[hb + 2 * x + 1];
-            if (xmin < 0 || n < 0 || n > KH || (long)xmin + n > w) xmin = 0, n = 0;
-            const uint8_t* p = img + (long)(sy0 + r) * pitch + xmin * 3;
-            const int* k = tab + hk + (long)x * KH;
-            int s0 = 1 << (RS_BITS - 1), s1 = s0, s2 = s0;
-            for (int j = 0; j < n; ++j) {
-                const int kj = k[j];
-                s0 += (int)p[3 * j] * kj;
-                s1 += (int)p[3 * j + 1] * kj;
-                s2 += (int)p[3 * j + 2] * kj;
-            }
-            mid[(0 * span + r) * cwp + c] = (uint8_t)rs_clip8(s0);
-            mid[(1 * span + r) * cwp + c] = (uint8_t)rs_clip8(s1);
-            mid[(2 * span + r) * cwp + c] = (uint8_t)rs_clip8(s2);
-        }
-        __syncthreads();
-    }
+__global__ __launch_bounds__(PIL_THREADS) void resize_bicubic_u8_kernel(const uint8_t* __restrict__ src, long src_bytes,
+                                                                        const int* __restrict__ tab, long tab_elems,
+                                                                        uint8_t* __restrict__ dst, int R, int lds_bytes) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t mid[];
+    rs_resize_tile<false>(mid, src, src_bytes, tab, tab_elems, dst, R, lds_bytes);
+}
 
-    const int groups = cwp >> 2, rows = y1 - y0;
-    for (int e = threadIdx.x; e < 3 * rows * groups; e += RS_THREADS) {
-        const int g = e % groups, t = e / groups;
-        const int oy = y0 + t % rows, ch = t / rows;
-        int rel = 0, n = 0;
-        const int* k = tab;
-        if (inside && oy < oh) {
-            rel = tab[vb + 2 * oy] - sy0, n = tab[vb + 2 * oy + 1];
-            if (rel < 0 || n < 0 || n > KV || (long)rel + n > span) rel = 0, n = 0;
-            k = tab + vk + (long)oy * KV;
-        }
-        const uint8_t* m = mid + (ch * span + rel) * cwp + 4 * g;
-        int a0 = 1 << (RS_BITS - 1), a1 = a0, a2 = a0, a3 = a0;
-        for (int j = 0; j < n; ++j) {
-            const uint32_t v = *reinterpret_cast<const uint32_t*>(m + j * cwp);
-            const int kj = k[j];
-            a0 += (int)(v & 255u) * kj;
-            a1 += (int)((v >> 8) & 255u) * kj;
-            a2 += (int)((v >> 16) & 255u) * kj;
-            a3 += (int)(v >> 24) * kj;
-        }
-        const int c = c0 + 4 * g;                                   // first canvas column of the group
-        const uint32_t o0 = c < ow ? rs_clip8(a0) : 0u, o1 = c + 1 < ow ? rs_clip8(a1) : 0u;
-        const uint32_t o2 = c + 2 < ow ? rs_clip8(a2) : 0u, o3 = c + 3 < ow ? rs_clip8(a3) : 0u;
-        uint8_t* orow = dst + (((long)b * 3 + ch) * R + oy) * R;
-        const int nv = min(4, c0 + cn - c);
-        if (nv == 4 && (R & 3) == 0 && (c & 3) == 0) {
-            const uint32_t word = flip ? (o3 | o2 << 8 | o1 << 16 | o0 << 24) : (o0 | o1 << 8 | o2 << 16 | o3 << 24);
-            *reinterpret_cast<uint32_t*>(orow + (flip ? R - 4 - c : c)) = word;
-        } else {
-            const uint32_t o[4] = {o0, o1, o2, o3};
-            for (int q = 0; q < nv; ++q) orow[flip ? R - 1 - c - q : c + q] = (uint8_t)o[q];
-        }
-    }
+__global__ __launch_bounds__(PIL_THREADS) void resize_fit_pad_u8_kernel(const uint8_t* __restrict__ src, long src_bytes,
+                                                                        const int* __restrict__ tab, long tab_elems,
+                                                                        uint8_t* __restrict__ dst, int R, int lds_bytes) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t mid[];
+    rs_resize_tile<true>(mid, src, src_bytes, tab, tab_elems, dst, R, lds_bytes);
 }
 
 }  // namespace
@@ -214,7 +69,7 @@ extern "C" int shg_resize_bicubic_u8(const void* src, long src_bytes, const int*
                   "resize_bicubic_u8: chunks and bands must lie in [1, R] (got %d, %d)", chunks, bands);
     SHG_CHECK_ARG(lds_bytes >= 12 && lds_bytes <= RS_LDS_BYTES, "resize_bicubic_u8: lds_bytes must lie in [12, %d] (got %d)", RS_LDS_BYTES,
                   lds_bytes);
-    hipLaunchKernelGGL(resize_bicubic_u8_kernel, dim3(chunks, bands, B), dim3(RS_THREADS), (size_t)lds_bytes, (hipStream_t)stream,
+    hipLaunchKernelGGL(resize_bicubic_u8_kernel, dim3(chunks, bands, B), dim3(PIL_THREADS), (size_t)lds_bytes, (hipStream_t)stream,
                        (const uint8_t*)src, src_bytes, table, table_elems, (uint8_t*)dst, R, lds_bytes);
     SHG_CHECK_LAUNCH();
     return SHG_OK;
@@ -236,7 +91,7 @@ extern "C" int shg_resize_fit_pad_u8(const void* src, long src_bytes, const int*
                   "resize_fit_pad_u8: chunks and bands must lie in [1, R] (got %d, %d)", chunks, bands);
     SHG_CHECK_ARG(lds_bytes >= 12 && lds_bytes <= RS_LDS_BYTES, "resize_fit_pad_u8: lds_bytes must lie in [12, %d] (got %d)", RS_LDS_BYTES,
                   lds_bytes);
-    hipLaunchKernelGGL(resize_fit_pad_u8_kernel, dim3(chunks, bands, B), dim3(RS_THREADS), (size_t)lds_bytes, (hipStream_t)stream,
+    hipLaunchKernelGGL(resize_fit_pad_u8_kernel, dim3(chunks, bands, B), dim3(PIL_THREADS), (size_t)lds_bytes, (hipStream_t)stream,
                        (const uint8_t*)src, src_bytes, table, table_elems, (uint8_t*)dst, R, lds_bytes);
     SHG_CHECK_LAUNCH();
     return SHG_OK;

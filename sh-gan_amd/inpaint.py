@@ -28,6 +28,7 @@ import torch
 
 from . import _lib, eval_harness, kernels, resize
 from ._lib import check
+from .resize import _upload, bicubic_weights
 
 LDS_BYTES = 49152                    # csrc/inpaint.hip IP_LDS_BYTES
 DESC_INTS = 16                       # csrc/inpaint.hip IP_DESC
@@ -35,7 +36,6 @@ MAX_FEATHER = 32                     # csrc/inpaint.hip IP_MAX_FEATHER
 MEMBRANE_TILE = 32                   # csrc/membrane.hip MB_TILE: the smoother's tile side
 MEMBRANE_COARSEST = 16               # csrc/membrane.hip MB_COARSEST: the largest side of a coarsest level
 MEMBRANE_MAX_CYCLES = 44             # default of membrane_solve: twice the largest count seen, 22
-_WEIGHT_CACHE = {}
 
 
 def plan_window(mask, R, context=0.5, feather=8):
@@ -78,27 +78,6 @@ def pack_masks(masks):
     return torch.from_numpy(buf), offs
 
 
-def bicubic_weights(n_in, n_out):
-    """-> (bounds int32 [out, 2] = (first tap, taps), w float64 [out, K]): Pillow's bicubic taps along one axis exactly as
-    ``resize.bicubic_coeffs`` has them before its fixed-point rounding (a size that stays gets the one-tap identity); cached."""
-    key = (int(n_in), int(n_out))
-    hit = _WEIGHT_CACHE.get(key)
-    if hit is not None:
-        return hit
-    if key[0] < 1 or key[1] < 1:
-        raise ValueError(f'bicubic_weights: sizes must be >= 1 (got {key[0]} -> {key[1]})')
-    if key[0] == key[1]:
-        bounds = np.stack([np.arange(key[1]), np.ones(key[1], np.int64)], axis=1).astype(np.int32)
-        w = np.ones((key[1], 1), np.float64)
-    else:
-        xmin, n, w = resize.bicubic_taps(*key)
-        bounds = np.stack([xmin, n], axis=1).astype(np.int32)
-    bounds.setflags(write=False)
-    w.setflags(write=False)
-    _WEIGHT_CACHE[key] = (bounds, w)
-    return bounds, w
-
-
 def _host(a):
     return np.asarray(a.numpy() if isinstance(a, torch.Tensor) else a)
 
@@ -124,12 +103,6 @@ def _geometry(shapes, windows, what):
     return geo
 
 
-def _finish_table(desc, parts, pos, what):
-    if pos >= 2 ** 31:
-        raise ValueError(f'{what}: coefficient table too large')
-    return np.concatenate([desc.reshape(-1).astype(np.int32)] + parts)
-
-
 def build_gather_table(shapes, windows, R):
     """Host side of a ``gather_windows`` launch -> (int32 table, chunks, bands, LDS bytes): B descriptors of DESC_INTS ints (h, w, image
     offset, mask offset, y0, x0, ch, cw, horizontal bounds / coefficients / width, vertical bounds / coefficients / width, band rows,
@@ -138,29 +111,16 @@ def build_gather_table(shapes, windows, R):
     R = int(R)
     if R < 1:
         raise ValueError(f'gather_windows: R must be >= 1 (got {R})')
-    B = geo.shape[0]
-    desc = np.zeros((B, DESC_INTS), np.int64)
-    parts, placed, pos = [], {}, B * DESC_INTS
-
-    def place(n_in):
-        nonlocal pos
-        if n_in not in placed:
-            bounds, k = resize.bicubic_coeffs(n_in, R)
-            placed[n_in] = (pos, pos + bounds.size, k.shape[1])
-            parts.extend([bounds.reshape(-1).astype(np.int32), k.reshape(-1).astype(np.int32)])
-            pos += bounds.size + k.size
-        return placed[n_in]
-
-    chunks = bands = lds_bytes = 1
+    t = resize._Table(geo.shape[0], DESC_INTS)
     for i, g in enumerate(geo):
         ch, cw = int(g[6]), int(g[7])
         try:
-            tb, cc, lds = resize._tiling(ch, R)
+            tb, cc, lds = resize._tiling(ch, R, R)
         except ValueError:
             raise ValueError(f'gather_windows: the {ch}-row window of image {i} is too tall to resample to {R} rows in one workgroup band') from None
-        desc[i] = tuple(g) + place(cw) + place(ch) + (tb, cc)
-        chunks, bands, lds_bytes = max(chunks, -(-R // cc)), max(bands, -(-R // tb)), max(lds_bytes, lds)
-    return _finish_table(desc, parts, pos, 'gather_windows'), chunks, bands, max(lds_bytes, 12)
+        t.desc[i] = tuple(g) + t.place(cw, *resize.bicubic_coeffs(cw, R)) + t.place(ch, *resize.bicubic_coeffs(ch, R)) + (tb, cc)
+        t.tile(-(-R // cc), -(-R // tb), lds)
+    return t.finish('gather_windows', 12)
 
 
 def _align16(n):
@@ -193,20 +153,14 @@ def build_paste_table(shapes, windows, R, feather):
     R, feather = int(R), int(feather)
     if R < 1 or not 0 <= feather <= MAX_FEATHER:
         raise ValueError(f'paste_back: R must be >= 1 and feather in 0..{MAX_FEATHER} (got {R}, {feather})')
-    B = geo.shape[0]
-    desc = np.zeros((B, DESC_INTS), np.int64)
-    parts, placed, pos = [], {}, B * DESC_INTS
+    t = resize._Table(geo.shape[0], DESC_INTS)
 
     def place(n_out):
-        nonlocal pos
-        if n_out not in placed:
-            bounds, w = bicubic_weights(R, n_out)
-            placed[n_out] = (pos, pos + bounds.size, w.shape[1])
-            parts.extend([bounds.reshape(-1).astype(np.int32), np.ascontiguousarray(w.astype(np.float32)).reshape(-1).view(np.int32)])
-            pos += bounds.size + w.size
-        return placed[n_out]
+        if n_out in t.placed:                                       # (the float32 rounding below is done once per size)
+            return t.placed[n_out]
+        bounds, w = bicubic_weights(R, n_out)
+        return t.place(n_out, bounds, w.astype(np.float32).view(np.int32))
 
-    chunks = bands = lds_bytes = 1
     for i, g in enumerate(geo):
         ch, cw = int(g[6]), int(g[7])
         tiling = _paste_tiling(ch, cw, R, feather)
@@ -214,22 +168,17 @@ def build_paste_table(shapes, windows, R, feather):
             raise ValueError(f'paste_back: image {i}: {R} rows resampled down to a {ch}-row window do not fit one workgroup band '
                              f'(a window that small is not pasted from a {R} x {R} output)')
         tb, cc, lds = tiling
-        desc[i] = tuple(g) + place(cw) + place(ch) + (tb, cc)
-        chunks, bands, lds_bytes = max(chunks, -(-cw // cc)), max(bands, -(-ch // tb)), max(lds_bytes, lds)
-    if chunks > 65535 or bands > 65535:
+        t.desc[i] = tuple(g) + place(cw) + place(ch) + (tb, cc)
+        t.tile(-(-cw // cc), -(-ch // tb), lds)
+    if t.chunks > 65535 or t.bands > 65535:
         raise ValueError('paste_back: a window has more than 65535 bands or chunks')
-    return _finish_table(desc, parts, pos, 'paste_back'), chunks, bands, max(lds_bytes, 32)
+    return t.finish('paste_back', 32)
 
 
 def _u8_flat(launch, t, name, what):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8):
         raise _lib.ShgError(f'{what}: {name} must be a uint8 HIP tensor: libshgan_hip has no CPU path')
     return launch.req(t, name, dtype=torch.uint8).view(-1)
-
-
-def _upload(table, dev):
-    tab = torch.from_numpy(table)
-    return tab.pin_memory().to(dev, non_blocking=True)
 
 
 def _check_extent(geo, n_img, n_mask, what):

@@ -8,7 +8,7 @@ Pillow's 8-bit resample (``ImagingResample``) is integer arithmetic on coefficie
   * horizontal pass first (only when w != R), vertical second (only when h != R), each ``(1 << 21 + sum u8 * k) >> 22`` clipped to
     0..255 -- the intermediate is uint8.
 The tables are built here (double precision, the taps accumulated in Pillow's order: vectorised over output indices, looped over
-taps), cached per (in, out) pair, and uploaded with the batch; the kernel (csrc/resize.hip) only adds integers, so the device result
+taps), cached per (in, out) pair, and uploaded with the batch; the kernels (csrc/pillow_resample.h) only add integers, so the device result
 is bit-exact by construction.  An axis that keeps its size gets the one-tap identity table (k = 1 << 22), which is Pillow's skipped
 pass in the same arithmetic.  ``resize_reference`` is the same two passes in numpy (CPU tests).
 
@@ -34,6 +34,7 @@ DESC_INTS = 12                       # csrc/resize.hip: per-image descriptor
 FIT_DESC_INTS = 14                   # csrc/resize.hip: per-image descriptor of the fit-and-pad launch (+ h', w')
 RANDCROP_DESC_INTS = 9               # csrc/randcrop.hip: h, w, byte offset, nh, nw, ch, cw, flip_v, flip_h
 _RANDCROP_LUT = {}
+_WEIGHT_CACHE = {}
 _COEF_CACHE = {}
 
 
@@ -66,24 +67,39 @@ def bicubic_taps(n_in, n_out):
     return xmin, n, pre
 
 
+def bicubic_weights(n_in, n_out):
+    """-> (bounds int32 [out, 2] = (first tap, taps), w float64 [out, K]): Pillow's bicubic taps along one axis in double precision,
+    before any rounding (a size that stays gets the one-tap identity: Pillow skips the pass); cached."""
+    key = (int(n_in), int(n_out))
+    hit = _WEIGHT_CACHE.get(key)
+    if hit is not None:
+        return hit
+    if key[0] < 1 or key[1] < 1:
+        raise ValueError(f'bicubic_weights: sizes must be >= 1 (got {key[0]} -> {key[1]})')
+    if key[0] == key[1]:
+        bounds = np.stack([np.arange(key[1]), np.ones(key[1], np.int64)], axis=1).astype(np.int32)
+        w = np.ones((key[1], 1), np.float64)
+    else:
+        xmin, n, w = bicubic_taps(*key)
+        bounds = np.stack([xmin, n], axis=1).astype(np.int32)
+    bounds.setflags(write=False)
+    w.setflags(write=False)
+    _WEIGHT_CACHE[key] = (bounds, w)
+    return bounds, w
+
+
 def bicubic_coeffs(in_size, out_size):
-    """-> (bounds int32 [out, 2] = (xmin, n), k int32 [out, K]) of Pillow's 8-bit bicubic resample along one axis; cached."""
+    """-> (bounds int32 [out, 2] = (xmin, n), k int32 [out, K]) of Pillow's 8-bit bicubic resample along one axis: ``bicubic_weights`` in
+    fixed point (the identity's 1.0 becomes 1 << 22, Pillow's skipped pass in the same arithmetic); cached."""
     key = (int(in_size), int(out_size))
     hit = _COEF_CACHE.get(key)
     if hit is not None:
         return hit
-    n_in, n_out = key
-    if n_in < 1 or n_out < 1:
-        raise ValueError(f'bicubic_coeffs: sizes must be >= 1 (got {n_in} -> {n_out})')
-    if n_in == n_out:                                       # Pillow skips the pass: the identity in the same arithmetic
-        bounds = np.stack([np.arange(n_out), np.ones(n_out, np.int64)], axis=1).astype(np.int32)
-        k = np.full((n_out, 1), 1 << PRECISION_BITS, np.int32)
-    else:
-        xmin, n, pre = bicubic_taps(n_in, n_out)
-        fx = pre * float(1 << PRECISION_BITS)
-        k = np.where(pre < 0, np.trunc(-0.5 + fx), np.trunc(0.5 + fx)).astype(np.int32)
-        bounds = np.stack([xmin, n], axis=1).astype(np.int32)
-    bounds.setflags(write=False)
+    if key[0] < 1 or key[1] < 1:
+        raise ValueError(f'bicubic_coeffs: sizes must be >= 1 (got {key[0]} -> {key[1]})')
+    bounds, w = bicubic_weights(*key)
+    fx = w * float(1 << PRECISION_BITS)
+    k = np.where(w < 0, np.trunc(-0.5 + fx), np.trunc(0.5 + fx)).astype(np.int32)
     k.setflags(write=False)
     _COEF_CACHE[key] = (bounds, k)
     return bounds, k
@@ -143,24 +159,10 @@ def fit_reference(img, R, flip=False):
     return np.ascontiguousarray(canvas.transpose(2, 0, 1))
 
 
-def _tiling(h, R):
-    """(band rows TB, column chunk CW, LDS bytes) of one image: the tallest band (fewest source rows resampled twice by neighbouring
-    bands) whose source rows, resampled to a chunk of at most 128 columns, fit the workgroup's LDS (3 planes x rows x chunk, uint8)."""
-    bounds, _ = bicubic_coeffs(h, R)
-    lo, hi = bounds[:, 0].astype(np.int64), (bounds[:, 0] + bounds[:, 1]).astype(np.int64)
-    for tb in (16, 8, 4, 2, 1):
-        tb = min(tb, R)
-        starts = np.arange(0, R, tb)
-        span = int((hi[np.minimum(starts + tb, R) - 1] - lo[starts]).max())
-        for cw in (min(R, 128), 64, 32, 16):
-            lds = 3 * span * ((cw + 3) // 4 * 4)
-            if cw <= R and lds <= LDS_BYTES:
-                return tb, cw, lds
-    raise ValueError(f'resize: a {h}-row image is too tall to resample to {R} rows in one workgroup band')
-
-
-def _fit_tiling(h, oh, R):
-    """_tiling for an image of h rows resampled to oh <= R box rows on an R-row canvas: the bands cover the canvas, the LDS holds the
+def _tiling(h, oh, R):
+    """(band rows TB, column chunk CW, LDS bytes) of one image of h rows resampled to oh <= R box rows on an R-row canvas (oh = R: the
+    plain resize): the tallest band (fewest source rows resampled twice by neighbouring bands) whose source rows, resampled to a chunk
+    of at most 128 columns, fit the workgroup's LDS (3 planes x rows x chunk, uint8).  The bands cover the canvas, the LDS holds the
     source rows of the box part of a band."""
     bounds, _ = bicubic_coeffs(h, oh)
     lo, hi = bounds[:, 0].astype(np.int64), (bounds[:, 0] + bounds[:, 1]).astype(np.int64)
@@ -175,6 +177,34 @@ def _fit_tiling(h, oh, R):
     raise ValueError(f'resize: a {h}-row image is too tall to resample to {oh} rows in one workgroup band')
 
 
+class _Table:
+    """The int32 table of one launch while it is assembled: ``desc``, B descriptor rows of ``ints`` ints (int64 until ``finish``), then
+    each distinct per-axis (bounds, payload) pair once, with the launch's grid and LDS maxima over the images."""
+
+    def __init__(self, B, ints):
+        self.desc = np.zeros((B, ints), np.int64)
+        self.parts, self.placed, self.pos = [], {}, B * ints
+        self.chunks = self.bands = self.lds_bytes = 1
+
+    def place(self, key, bounds, payload):
+        """Append bounds [n, 2] and payload [n, K] (int32) once per ``key`` -> (bounds offset, payload offset, K)."""
+        if key not in self.placed:
+            self.placed[key] = (self.pos, self.pos + bounds.size, payload.shape[1])
+            self.parts.extend([bounds.reshape(-1), payload.reshape(-1)])
+            self.pos += bounds.size + payload.size
+        return self.placed[key]
+
+    def tile(self, chunks, bands, lds):
+        self.chunks, self.bands, self.lds_bytes = max(self.chunks, chunks), max(self.bands, bands), max(self.lds_bytes, lds)
+
+    def finish(self, what, min_lds):
+        """-> (int32 table, chunks, bands, LDS bytes)."""
+        if self.pos >= 2 ** 31:
+            raise ValueError(f'{what}: coefficient table too large')
+        table = np.concatenate([self.desc.reshape(-1).astype(np.int32)] + [p.astype(np.int32) for p in self.parts])
+        return table, self.chunks, self.bands, max(self.lds_bytes, min_lds)
+
+
 def build_fit_table(shapes, R, flip=None):
     """Host side of one fit-and-pad launch: shapes int [B, 3] = (h, w, byte offset) -> (int32 table, chunks, bands, LDS bytes).
     table = B descriptors of FIT_DESC_INTS ints (build_table's 12, then the box h', w' of ``fit_size``), then each distinct (in, out)
@@ -183,31 +213,16 @@ def build_fit_table(shapes, R, flip=None):
     B = shapes.shape[0]
     R = int(R)
     flip = np.zeros(B, np.int64) if flip is None else np.asarray(flip).astype(np.int64).reshape(B)
-    desc = np.zeros((B, FIT_DESC_INTS), np.int64)
-    parts, placed, pos = [], {}, B * FIT_DESC_INTS
-
-    def place(n_in, n_out):
-        nonlocal pos
-        key = (n_in, n_out)
-        if key not in placed:
-            bounds, k = bicubic_coeffs(n_in, n_out)
-            placed[key] = (pos, pos + bounds.size, k.shape[1])
-            parts.extend([bounds.reshape(-1), k.reshape(-1)])
-            pos += bounds.size + k.size
-        return placed[key]
-
-    chunks = bands = lds_bytes = 1
+    t = _Table(B, FIT_DESC_INTS)
     for i, (h, w, off) in enumerate(shapes):
         if h < 1 or w < 1 or off < 0:
             raise ValueError(f'resize: image {i} has shape {h}x{w} at offset {off}')
         oh, ow = fit_size(h, w, R)
-        tb, cw, lds = _fit_tiling(int(h), oh, R)
-        desc[i] = (h, w, off, flip[i] != 0) + place(int(w), ow) + place(int(h), oh) + (tb, cw, oh, ow)
-        chunks, bands, lds_bytes = max(chunks, -(-R // cw)), max(bands, -(-R // tb)), max(lds_bytes, lds)
-    if pos >= 2 ** 31:
-        raise ValueError('resize: coefficient table too large')
-    table = np.concatenate([desc.reshape(-1).astype(np.int32)] + [p.astype(np.int32) for p in parts])
-    return table, chunks, bands, max(lds_bytes, 12)
+        tb, cw, lds = _tiling(int(h), oh, R)
+        t.desc[i] = ((h, w, off, flip[i] != 0) + t.place((int(w), ow), *bicubic_coeffs(w, ow)) + t.place((int(h), oh), *bicubic_coeffs(h, oh))
+                     + (tb, cw, oh, ow))
+        t.tile(-(-R // cw), -(-R // tb), lds)
+    return t.finish('resize', 12)
 
 
 def build_table(shapes, R, flip=None):
@@ -217,75 +232,53 @@ def build_table(shapes, R, flip=None):
     shapes = np.asarray(shapes, np.int64).reshape(-1, 3)
     B = shapes.shape[0]
     flip = np.zeros(B, np.int64) if flip is None else np.asarray(flip).astype(np.int64).reshape(B)
-    desc = np.zeros((B, DESC_INTS), np.int64)
-    parts, placed, pos = [], {}, B * DESC_INTS
-
-    def place(n_in):
-        nonlocal pos
-        if n_in not in placed:
-            bounds, k = bicubic_coeffs(n_in, R)
-            placed[n_in] = (pos, pos + bounds.size, k.shape[1])
-            parts.extend([bounds.reshape(-1), k.reshape(-1)])
-            pos += bounds.size + k.size
-        return placed[n_in]
-
-    chunks = bands = lds_bytes = 1
+    t = _Table(B, DESC_INTS)
     for i, (h, w, off) in enumerate(shapes):
         if h < 1 or w < 1 or off < 0:
             raise ValueError(f'resize: image {i} has shape {h}x{w} at offset {off}')
-        tb, cw, lds = _tiling(int(h), R)
-        desc[i] = (h, w, off, flip[i] != 0) + place(int(w)) + place(int(h)) + (tb, cw)
-        chunks, bands, lds_bytes = max(chunks, -(-R // cw)), max(bands, -(-R // tb)), max(lds_bytes, lds)
-    if pos >= 2 ** 31:
-        raise ValueError('resize: coefficient table too large')
-    table = np.concatenate([desc.reshape(-1).astype(np.int32)] + [p.astype(np.int32) for p in parts])
-    return table, chunks, bands, max(lds_bytes, 12)
+        tb, cw, lds = _tiling(int(h), R, R)
+        t.desc[i] = (h, w, off, flip[i] != 0) + t.place(int(w), *bicubic_coeffs(w, R)) + t.place(int(h), *bicubic_coeffs(h, R)) + (tb, cw)
+        t.tile(-(-R // cw), -(-R // tb), lds)
+    return t.finish('resize', 12)
+
+
+def _upload(host, dev):
+    """numpy array -> tensor on ``dev`` through pinned memory; the copy is asynchronous on the current stream."""
+    return torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+
+
+def _launch_resize(name, build, packed, shapes, R, flip, stream):
+    """The body of ``resize_bicubic_u8`` / ``resize_fit_pad_u8``: ``build`` makes the launch's table, ``shg_<name>`` consumes it."""
+    if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.uint8):
+        raise _lib.ShgError(f'{name}: packed must be a uint8 HIP tensor: libshgan_hip has no CPU path')
+    packed = packed.contiguous().view(-1)
+    shapes = shapes.numpy() if isinstance(shapes, torch.Tensor) else shapes
+    flip = flip.numpy() if isinstance(flip, torch.Tensor) else flip
+    R = int(R)
+    table, chunks, bands, lds_bytes = build(shapes, R, flip)
+    B = np.asarray(shapes).reshape(-1, 3).shape[0]
+    dev = packed.device
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        tab = _upload(table, dev)
+        out = torch.empty((B, 3, R, R), dtype=torch.uint8, device=dev)
+        check(getattr(_lib.get_lib(), 'shg_' + name)(ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(tab.data_ptr()),
+                                                     tab.numel(), ctypes.c_void_p(out.data_ptr()), B, R, chunks, bands, lds_bytes,
+                                                     ctypes.c_void_p(st.cuda_stream)), name)
+    return out
 
 
 def resize_bicubic_u8(packed, shapes, R, flip=None, stream=None):
     """packed: uint8 HIP tensor holding B HWC RGB images back to back; shapes: host int [B, 3] = (h, w, byte offset) (numpy or a CPU
     tensor); flip: host [B] flags (horizontal flip of the resized image) or None -> uint8 [B, 3, R, R] on packed's device, computed on
     ``stream`` (default: the current stream).  The coefficient table travels with the launch (pinned, asynchronous)."""
-    if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.uint8):
-        raise _lib.ShgError('resize_bicubic_u8: packed must be a uint8 HIP tensor: libshgan_hip has no CPU path')
-    packed = packed.contiguous().view(-1)
-    shapes = shapes.numpy() if isinstance(shapes, torch.Tensor) else shapes
-    flip = flip.numpy() if isinstance(flip, torch.Tensor) else flip
-    R = int(R)
-    table, chunks, bands, lds_bytes = build_table(shapes, R, flip)
-    B = np.asarray(shapes).reshape(-1, 3).shape[0]
-    dev = packed.device
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
-    with torch.cuda.device(dev), torch.cuda.stream(st):
-        tab = torch.from_numpy(table)
-        tab = (tab.pin_memory() if torch.cuda.is_available() else tab).to(dev, non_blocking=True)
-        out = torch.empty((B, 3, R, R), dtype=torch.uint8, device=dev)
-        check(_lib.get_lib().shg_resize_bicubic_u8(ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(tab.data_ptr()),
-                                                   tab.numel(), ctypes.c_void_p(out.data_ptr()), B, R, chunks, bands, lds_bytes,
-                                                   ctypes.c_void_p(st.cuda_stream)), 'resize_bicubic_u8')
-    return out
+    return _launch_resize('resize_bicubic_u8', build_table, packed, shapes, R, flip, stream)
 
 
 def resize_fit_pad_u8(packed, shapes, R, flip=None, stream=None):
     """The OpenImages input: packed / shapes / flip / stream as resize_bicubic_u8 -> uint8 [B, 3, R, R], image i resized to
     ``fit_size(h, w, R)`` at the top-left of a zero canvas (the whole canvas mirrored when flip[i]).  One launch writes every byte."""
-    if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.uint8):
-        raise _lib.ShgError('resize_fit_pad_u8: packed must be a uint8 HIP tensor: libshgan_hip has no CPU path')
-    packed = packed.contiguous().view(-1)
-    shapes = shapes.numpy() if isinstance(shapes, torch.Tensor) else shapes
-    flip = flip.numpy() if isinstance(flip, torch.Tensor) else flip
-    R = int(R)
-    table, chunks, bands, lds_bytes = build_fit_table(shapes, R, flip)
-    B = np.asarray(shapes).reshape(-1, 3).shape[0]
-    dev = packed.device
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
-    with torch.cuda.device(dev), torch.cuda.stream(st):
-        tab = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
-        out = torch.empty((B, 3, R, R), dtype=torch.uint8, device=dev)
-        check(_lib.get_lib().shg_resize_fit_pad_u8(ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(tab.data_ptr()),
-                                                   tab.numel(), ctypes.c_void_p(out.data_ptr()), B, R, chunks, bands, lds_bytes,
-                                                   ctypes.c_void_p(st.cuda_stream)), 'resize_fit_pad_u8')
-    return out
+    return _launch_resize('resize_fit_pad_u8', build_fit_table, packed, shapes, R, flip, stream)
 
 
 def pack_images(images):
@@ -428,7 +421,7 @@ def randcrop_bicubic(src, desc_or_shapes, s, params=None, stream=None):
     fn = _lib.get_lib().shg_randcrop_bicubic_planar_f32 if planar else _lib.get_lib().shg_randcrop_bicubic_ragged_f32
     with torch.cuda.device(dev), torch.cuda.stream(st):
         lut = _randcrop_lut(dev)
-        dd = torch.from_numpy(desc).pin_memory().to(dev, non_blocking=True)
+        dd = _upload(desc, dev)
         out = torch.empty((B, 3, max(s, 0), max(s, 0)), dtype=torch.float32, device=dev)
         check(fn(ctypes.c_void_p(src.data_ptr()), src.numel(), desc.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
                  ctypes.c_void_p(dd.data_ptr()), ctypes.c_void_p(lut.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, s,

@@ -1360,8 +1360,7 @@ SITES = {
     ('precision_recall.py', 'radii'): ['metrics:precision_recall'],
     ('resize.py', 'pack_images'): ['input:randcrop', 'input:resize'],
     ('resize.py', 'randcrop_bicubic'): ['input:randcrop'],
-    ('resize.py', 'resize_bicubic_u8'): ['input:resize'],
-    ('resize.py', 'resize_fit_pad_u8'): ['input:resize'],
+    ('resize.py', '_launch_resize'): ['input:resize'],
     ('vgg16.py', 'fc_relu'): ['vgg16:frontend_pool_detector'],
     ('vgg16.py', 'frontend'): ['vgg16:frontend_pool_detector'],
     ('vgg16.py', 'maxpool2'): ['lpips:vgg_distance', 'vgg16:frontend_pool_detector'],
