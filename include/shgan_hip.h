@@ -626,6 +626,36 @@ int shg_inpaint_membrane_paste_u8(void* out, long img_bytes, const void* mask, l
                                   const int* grids, const float* g, const float* field, long g_elems, void* alpha, int B, int K, int R,
                                   int feather, int chunks, int bands, int lds_bytes, void* stream);
 
+/* ---- Hole groups: one window per group of holes (sh-gan_amd/inpaint.py label_holes / owner_plane / plan_windows; csrc/hole_label.hip;
+ * INTEGRATION section T).  mask as above; shapes: device int32 [B][4] = {h, w, image byte offset, mask byte offset}, every h <= max_h and
+ * w <= max_w.  With r = feather + 1 in 1..33: D = the pixels within Chebyshev distance r of a hole pixel of the same image; a group is an
+ * 8-connected component of D and its root the smallest y w + x over its pixels.
+ * shg_hole_label_i32: labels int32 [mask_bytes] = the root where the pixel lies in D, -1 elsewhere; comps int32 [max_components][8] =
+ *   {image, root, ya, yb, xa, xb, hole pixels, 0} (the half-open box of the group's hole pixels), one row per group in no particular
+ *   order, unused rows zero; counter int32 [2] = {groups found, flags}: bit 0 = more groups than max_components (those beyond it are
+ *   missing from comps; labels is complete), bit 1 = a find / union loop ran into its cap (every loop carries one: no kernel can spin).
+ *   scratch: int32 [mask_bytes], contents irrelevant.  A memset and at most four launches; integer atomics only: the same bits on every
+ *   run.  An image whose descriptor points outside mask is left unwritten.
+ * shg_hole_owner_u8: owner uint8 [mask_bytes] = 0 at a known pixel, at a hole pixel the key its group has in table (device int32
+ *   [n_table][3] = {image, root, key in 1..255}; 0 when the table does not name the group).  labels: what shg_hole_label_i32 wrote.
+ * shg_hole_label_tile: the side of the tile one workgroup labels in LDS.
+ * The keyed paste-backs take `owner` where the mask went and keys (device int [B], 1..255): window b blends the holes whose owner byte is
+ *   keys[b]; the rows of table / grids are per window and the windows of an image may overlap; alpha receives A only where A > 0.  With
+ *   r = feather + 1 no aligned 4-byte word of out or alpha is touched by two windows.  Everything else as the forms above. */
+int shg_hole_label_tile(void);
+int shg_hole_label_i32(const void* mask, long mask_bytes, const int* shapes, int B, int max_h, int max_w, int r, int max_components, int* labels,
+                       int* scratch, int* comps, int* counter, void* stream);
+int shg_hole_owner_u8(const void* mask, long mask_bytes, const int* shapes, int B, int max_h, int max_w, const int* labels, const int* table,
+                      int n_table, int* scratch, void* owner, void* stream);
+int shg_inpaint_paste_keyed_u8(void* out, long img_bytes, const void* owner, long mask_bytes, const int* keys, const int* table, long table_elems,
+                               const float* fake, void* alpha, int B, int K, int R, int feather, int chunks, int bands, int lds_bytes, void* stream);
+int shg_inpaint_membrane_setup_keyed_f32(const void* src, long img_bytes, const void* owner, long mask_bytes, const int* keys, const int* table,
+                                         long table_elems, const int* grids, const float* fake, float* g, float* field, long g_elems, void* omega,
+                                         long omega_bytes, int B, int K, int R, int feather, int chunks, int bands, int lds_bytes, void* stream);
+int shg_inpaint_membrane_paste_keyed_u8(void* out, long img_bytes, const void* owner, long mask_bytes, const int* keys, const int* table,
+                                        long table_elems, const int* grids, const float* g, const float* field, long g_elems, void* alpha, int B,
+                                        int K, int R, int feather, int chunks, int bands, int lds_bytes, void* stream);
+
 /* ---- Training input of Places2, OpenImages and DTD: the "random scale, random crop" formatter (AdvInpaintingFormatter,
  * ds_places2.py:183-207, ds_openimages.py:117-141; InpaintingFormatter, ds_texture.py:121-149).  dst float32 [B,3,s,s]: per image the
  * window [ch:ch+s, cw:cw+s] of torch's bicubic resample (upsample_bicubic2d, align_corners = false, A = -0.75, 4 x 4 clamped taps,

@@ -181,6 +181,13 @@ _SIGS = {
     'shg_inpaint_membrane_setup_f32': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
     'shg_membrane_solve_f32': [c_fp, c_l, c_fp, c_l, c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, ctypes.c_size_t, c_fp, c_fp],
     'shg_inpaint_membrane_paste_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'shg_inpaint_paste_keyed_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_l, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'shg_inpaint_membrane_setup_keyed_f32': [c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_l, c_fp, c_fp, c_fp, c_fp, c_l, c_fp, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
+                                             c_fp],
+    'shg_inpaint_membrane_paste_keyed_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_fp, c_l, c_fp, c_fp, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'shg_hole_label_tile': [],
+    'shg_hole_label_i32': [c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_fp],
+    'shg_hole_owner_u8': [c_fp, c_l, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_fp, c_fp, c_fp],
     'shg_randcrop_bicubic_ragged_f32': [c_fp, c_l, ctypes.POINTER(c_i), c_fp, c_fp, c_fp, c_i, c_i, c_fp],
     'shg_randcrop_bicubic_planar_f32': [c_fp, c_l, ctypes.POINTER(c_i), c_fp, c_fp, c_fp, c_i, c_i, c_fp],
     'shg_ada_params_f32': [c_fp, c_fp, c_fp, ctypes.POINTER(AdaConfig), c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],

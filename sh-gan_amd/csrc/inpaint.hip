@@ -76,11 +76,13 @@ __global__ __launch_bounds__(IP_THREADS) void gather_windows_kernel(const uint8_
 __global__ __launch_bounds__(IP_THREADS) void paste_back_kernel(uint8_t* __restrict__ out, long img_bytes, const uint8_t* __restrict__ msk,
                                                                 long msk_bytes, const int* __restrict__ tab, long tab_elems,
                                                                 const float* __restrict__ fake, uint8_t* __restrict__ alpha, int R, int K,
-                                                                int feather, int lds_bytes) {
+                                                                int feather, int lds_bytes, const int* __restrict__ keys) {
     extern __shared__ __attribute__((aligned(16))) uint8_t ip_lds[];
     const int b = blockIdx.z;
     IpDesc d;
     if (!ip_load_desc(tab, tab_elems, b, img_bytes, msk_bytes, false, R, d)) return;
+    const int key = ip_load_key(keys, b);
+    if (key < 0) return;
     const int y0 = (int)blockIdx.y * d.TB, c0 = (int)blockIdx.x * d.CW;
     if (y0 >= d.ch || c0 >= d.cw) return;
     const int y1 = min(y0 + d.TB, d.ch), rows = y1 - y0, cn = min(d.CW, d.cw - c0);
@@ -92,12 +94,12 @@ __global__ __launch_bounds__(IP_THREADS) void paste_back_kernel(uint8_t* __restr
     ip_tile_make(t, ip_lds, y0, c0, rows, cn, feather);
     if (span < 1 || (long)t.a_bytes + max((long)t.t_bytes + t.r_bytes, 12L * span * cn) > lds_bytes) return;
     // 1.-2. the feather weight; a tile without a hole within `feather` has A = 0 everywhere: nothing to store
-    if (!ip_feather_tile(t, msk, d, feather)) return;
+    if (!ip_feather_tile(t, msk, d, feather, (uint32_t)key)) return;
     const uint8_t* A = t.A;
     float* mid = t.mid;
 
     const int uo = (3 * cn + 6) >> 2;                               // aligned words a destination row of the chunk can touch
-    if (alpha) ip_store_alpha(t, alpha, d);
+    if (alpha) ip_store_alpha(t, alpha, d, keys != nullptr);
 
     // 3. per sample: horizontal pass into LDS, then vertical pass + blend, one lane per destination word
     const long RR = (long)R * R;
@@ -140,6 +142,26 @@ __global__ __launch_bounds__(IP_THREADS) void paste_back_kernel(uint8_t* __restr
     }
 }
 
+int ip_launch_paste(void* out, long img_bytes, const void* mask, long mask_bytes, const int* table, long table_elems, const float* fake, void* alpha,
+                    const int* keys, int B, int K, int R, int feather, int chunks, int bands, int lds_bytes, void* stream) {
+    SHG_CHECK_ARG(out && mask && table && fake, "inpaint_paste: null pointer");
+    SHG_CHECK_ARG(B >= 1 && B <= 65535, "inpaint_paste: B must lie in [1, 65535] (got %d)", B);
+    SHG_CHECK_ARG(K >= 1 && K <= 65535, "inpaint_paste: K must lie in [1, 65535] (got %d)", K);
+    SHG_CHECK_ARG(R >= 1 && R <= 16384, "inpaint_paste: R must lie in [1, 16384] (got %d)", R);
+    SHG_CHECK_ARG(feather >= 0 && feather <= IP_MAX_FEATHER, "inpaint_paste: feather must lie in [0, %d] (got %d)", IP_MAX_FEATHER, feather);
+    SHG_CHECK_ARG(img_bytes >= 3 && img_bytes <= 0x7fffffffL, "inpaint_paste: img_bytes must lie in [3, 2^31) (int32 offsets)");
+    SHG_CHECK_ARG(mask_bytes >= 1 && mask_bytes <= 0x7fffffffL, "inpaint_paste: mask_bytes must lie in [1, 2^31) (int32 offsets)");
+    SHG_CHECK_ARG(table_elems >= (long)B * IP_DESC, "inpaint_paste: the table holds fewer than B descriptors of %d ints", IP_DESC);
+    SHG_CHECK_ARG(chunks >= 1 && chunks <= 65535 && bands >= 1 && bands <= 65535, "inpaint_paste: chunks and bands must lie in [1, 65535] (got %d, %d)",
+                  chunks, bands);
+    SHG_CHECK_ARG(lds_bytes >= 32 && lds_bytes <= IP_LDS_BYTES, "inpaint_paste: lds_bytes must lie in [32, %d] (got %d)", IP_LDS_BYTES, lds_bytes);
+    SHG_CHECK_ARG((reinterpret_cast<uintptr_t>(fake) & 3) == 0, "inpaint_paste: fake must be 4-byte aligned");
+    hipLaunchKernelGGL(paste_back_kernel, dim3(chunks, bands, B), dim3(IP_THREADS), (size_t)lds_bytes, (hipStream_t)stream, (uint8_t*)out,
+                       img_bytes, (const uint8_t*)mask, mask_bytes, table, table_elems, fake, (uint8_t*)alpha, R, K, feather, lds_bytes, keys);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}
+
 }  // namespace
 
 // gather_windows: src / mask as above, dst uint8 [B,3,R,R], mask_dst float32 [B,1,R,R] (1 = known).  table: B descriptors of 16 ints and
@@ -167,20 +189,16 @@ extern "C" int shg_inpaint_gather_u8(const void* src, long src_bytes, const void
 extern "C" int shg_inpaint_paste_u8(void* out, long img_bytes, const void* mask, long mask_bytes, const int* table, long table_elems,
                                     const float* fake, void* alpha, int B, int K, int R, int feather, int chunks, int bands, int lds_bytes,
                                     void* stream) {
-    SHG_CHECK_ARG(out && mask && table && fake, "inpaint_paste: null pointer");
-    SHG_CHECK_ARG(B >= 1 && B <= 65535, "inpaint_paste: B must lie in [1, 65535] (got %d)", B);
-    SHG_CHECK_ARG(K >= 1 && K <= 65535, "inpaint_paste: K must lie in [1, 65535] (got %d)", K);
-    SHG_CHECK_ARG(R >= 1 && R <= 16384, "inpaint_paste: R must lie in [1, 16384] (got %d)", R);
-    SHG_CHECK_ARG(feather >= 0 && feather <= IP_MAX_FEATHER, "inpaint_paste: feather must lie in [0, %d] (got %d)", IP_MAX_FEATHER, feather);
-    SHG_CHECK_ARG(img_bytes >= 3 && img_bytes <= 0x7fffffffL, "inpaint_paste: img_bytes must lie in [3, 2^31) (int32 offsets)");
-    SHG_CHECK_ARG(mask_bytes >= 1 && mask_bytes <= 0x7fffffffL, "inpaint_paste: mask_bytes must lie in [1, 2^31) (int32 offsets)");
-    SHG_CHECK_ARG(table_elems >= (long)B * IP_DESC, "inpaint_paste: the table holds fewer than B descriptors of %d ints", IP_DESC);
-    SHG_CHECK_ARG(chunks >= 1 && chunks <= 65535 && bands >= 1 && bands <= 65535, "inpaint_paste: chunks and bands must lie in [1, 65535] (got %d, %d)",
-                  chunks, bands);
-    SHG_CHECK_ARG(lds_bytes >= 32 && lds_bytes <= IP_LDS_BYTES, "inpaint_paste: lds_bytes must lie in [32, %d] (got %d)", IP_LDS_BYTES, lds_bytes);
-    SHG_CHECK_ARG((reinterpret_cast<uintptr_t>(fake) & 3) == 0, "inpaint_paste: fake must be 4-byte aligned");
-    hipLaunchKernelGGL(paste_back_kernel, dim3(chunks, bands, B), dim3(IP_THREADS), (size_t)lds_bytes, (hipStream_t)stream, (uint8_t*)out,
-                       img_bytes, (const uint8_t*)mask, mask_bytes, table, table_elems, fake, (uint8_t*)alpha, R, K, feather, lds_bytes);
-    SHG_CHECK_LAUNCH();
-    return SHG_OK;
+    return ip_launch_paste(out, img_bytes, mask, mask_bytes, table, table_elems, fake, alpha, nullptr, B, K, R, feather, chunks, bands, lds_bytes, stream);
+}
+
+// paste_back over the windows of hole groups (csrc/hole_label.hip): `owner` (uint8 [mask_bytes]: 0 = known, a group's key at its hole
+// pixels) stands where the mask went and window b blends the holes whose byte equals keys[b] (device int [B], 1..255; a window with
+// another value is left alone).  The rows of `table` are per window; the windows of one image may overlap.  alpha receives A only where
+// A > 0, so the windows of an image fill one plane between them.
+extern "C" int shg_inpaint_paste_keyed_u8(void* out, long img_bytes, const void* owner, long mask_bytes, const int* keys, const int* table,
+                                          long table_elems, const float* fake, void* alpha, int B, int K, int R, int feather, int chunks, int bands,
+                                          int lds_bytes, void* stream) {
+    SHG_CHECK_ARG(keys, "inpaint_paste_keyed: null pointer");
+    return ip_launch_paste(out, img_bytes, owner, mask_bytes, table, table_elems, fake, alpha, keys, B, K, R, feather, chunks, bands, lds_bytes, stream);
 }

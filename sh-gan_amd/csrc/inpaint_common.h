@@ -72,7 +72,8 @@ __device__ __forceinline__ void ip_tile_make(IpTile& t, uint8_t* lds, int y0, in
 // Steps 1-2 of paste_back: the hole flags of the tile and a halo of `feather` pixels (outside the window: not a hole), the row pass and
 // the column pass -> A [rows][cn] in LDS.  Returns false (workgroup-uniform) when no hole lies within `feather` of the tile: A = 0
 // everywhere, and t.A is NOT written.  On return true the flags and row distances are dead and every lane has passed a barrier.
-__device__ __forceinline__ bool ip_feather_tile(const IpTile& t, const uint8_t* __restrict__ msk, const IpDesc& d, int feather) {
+// A pixel is a hole where its byte equals `key`: 0 on the native mask, a group's key (1..255) on an owner plane (csrc/hole_label.hip).
+__device__ __forceinline__ bool ip_feather_tile(const IpTile& t, const uint8_t* __restrict__ msk, const IpDesc& d, int feather, uint32_t key) {
     const int F = feather + 1, HALO = feather, y0 = t.y0, c0 = t.c0, rows = t.rows, cn = t.cn, th = t.th, tw = t.tw, twp = t.twp;
     uint8_t *tile = t.tile, *rowd = t.rowd, *A = t.A;
     // 1. hole flags of the tile and its halo
@@ -94,13 +95,13 @@ __device__ __forceinline__ bool ip_feather_tile(const IpTile& t, const uint8_t* 
             const uint32_t v = *reinterpret_cast<const uint32_t*>(p + lo);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int hole = ((v >> (8 * q)) & 255u) == 0u;
+                const int hole = ((v >> (8 * q)) & 255u) == key;
                 trow[lo + q] = (uint8_t)hole;
                 found |= hole;
             }
         } else {
             for (int q = max(lo, 0); q < min(lo + 4, nbm); ++q) {
-                const int hole = p[q] == 0;
+                const int hole = p[q] == key;
                 trow[q] = (uint8_t)hole;
                 found |= hole;
             }
@@ -134,8 +135,18 @@ __device__ __forceinline__ bool ip_feather_tile(const IpTile& t, const uint8_t* 
     return true;
 }
 
-// A of the tile into `alpha` (packed-mask layout), one lane per aligned 4-byte word of a row.
-__device__ __forceinline__ void ip_store_alpha(const IpTile& t, uint8_t* __restrict__ alpha, const IpDesc& d) {
+// The key of window b in a keyed launch (keys: device int [B], each in 1..255; anything else -> -1, the window is left alone), 0 in a
+// launch on the native mask (keys == nullptr).
+__device__ __forceinline__ int ip_load_key(const int* __restrict__ keys, int b) {
+    if (!keys) return 0;
+    const int k = keys[b];
+    return k >= 1 && k <= 255 ? k : -1;
+}
+
+// A of the tile into `alpha` (packed-mask layout), one lane per aligned 4-byte word of a row.  keyed: several windows of one image
+// write one plane and a window's tile may cover another group's ring, so only A > 0 is stored -- a word whole when its four bytes are
+// non-zero, else its non-zero bytes singly (the rings of two groups are at least 3 bytes apart on a row).
+__device__ __forceinline__ void ip_store_alpha(const IpTile& t, uint8_t* __restrict__ alpha, const IpDesc& d, bool keyed) {
     const int cn = t.cn, ua = (cn + 6) >> 2;
     for (int e = threadIdx.x; e < t.rows * ua; e += IP_THREADS) {
         const int r = e / ua, u = e - r * ua;
@@ -143,10 +154,12 @@ __device__ __forceinline__ void ip_store_alpha(const IpTile& t, uint8_t* __restr
         const int lo = 4 * u - (int)(reinterpret_cast<uintptr_t>(p) & 3);
         if (lo >= cn || lo + 4 <= 0) continue;
         const uint8_t* ar = t.A + r * cn;
-        if (lo >= 0 && lo + 4 <= cn) {
+        const bool whole = lo >= 0 && lo + 4 <= cn;
+        if (whole && (!keyed || (ar[lo] && ar[lo + 1] && ar[lo + 2] && ar[lo + 3]))) {
             *reinterpret_cast<uint32_t*>(p + lo) = (uint32_t)ar[lo] | (uint32_t)ar[lo + 1] << 8 | (uint32_t)ar[lo + 2] << 16 | (uint32_t)ar[lo + 3] << 24;
         } else {
-            for (int q = max(lo, 0); q < min(lo + 4, cn); ++q) p[q] = ar[q];
+            for (int q = max(lo, 0); q < min(lo + 4, cn); ++q)
+                if (!keyed || ar[q]) p[q] = ar[q];
         }
     }
 }

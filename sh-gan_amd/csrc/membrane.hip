@@ -412,11 +412,13 @@ __global__ __launch_bounds__(IP_THREADS) void membrane_setup_kernel(const uint8_
                                                                     const int* __restrict__ grids, const float* __restrict__ fake,
                                                                     float* __restrict__ gws, float* __restrict__ field, long g_elems,
                                                                     uint8_t* __restrict__ omega, long om_bytes, int R, int K, int feather,
-                                                                    int lds_bytes) {
+                                                                    int lds_bytes, const int* __restrict__ keys) {
     extern __shared__ __attribute__((aligned(16))) uint8_t ip_lds[];
     const int b = blockIdx.z;
     IpDesc d;
     if (!ip_load_desc(tab, tab_elems, b, img_bytes, msk_bytes, false, R, d)) return;
+    const int key = ip_load_key(keys, b);
+    if (key < 0) return;
     MbGrid g;
     if (!mb_load_grid(grids, b, d, K, g_elems, om_bytes, g)) return;
     const int y0 = (int)blockIdx.y * d.TB, c0 = (int)blockIdx.x * d.CW;
@@ -431,7 +433,7 @@ __global__ __launch_bounds__(IP_THREADS) void membrane_setup_kernel(const uint8_
     IpTile t;
     ip_tile_make(t, ip_lds, y0, c0, rows, cn, feather);
     if (span < 1 || (long)t.a_bytes + max((long)t.t_bytes + t.r_bytes, 12L * span * cn) > lds_bytes) return;
-    const bool holes = ip_feather_tile(t, msk, d, feather);        // false: A = 0 in the whole tile (t.A is not written)
+    const bool holes = ip_feather_tile(t, msk, d, feather, (uint32_t)key);   // false: A = 0 in the tile (t.A is not written)
     const long RR = (long)R * R, plane = 3L * g.gh * g.gw;
     const int nr = ry1 - ry0, nq = 3 * (rx1 - rx0), nb = 3 * cn;
     const uint8_t* img = src + d.off;
@@ -459,11 +461,13 @@ __global__ __launch_bounds__(IP_THREADS) void membrane_paste_kernel(uint8_t* __r
                                                                     long msk_bytes, const int* __restrict__ tab, long tab_elems,
                                                                     const int* __restrict__ grids, const float* __restrict__ gws,
                                                                     const float* __restrict__ field, long g_elems, uint8_t* __restrict__ alpha,
-                                                                    int R, int K, int feather, int lds_bytes) {
+                                                                    int R, int K, int feather, int lds_bytes, const int* __restrict__ keys) {
     extern __shared__ __attribute__((aligned(16))) uint8_t ip_lds[];
     const int b = blockIdx.z;
     IpDesc d;
     if (!ip_load_desc(tab, tab_elems, b, img_bytes, msk_bytes, false, R, d)) return;
+    const int key = ip_load_key(keys, b);
+    if (key < 0) return;
     MbGrid g;
     if (!mb_load_grid(grids, b, d, K, g_elems, 0x7fffffffL, g)) return;
     const int y0 = (int)blockIdx.y * d.TB, c0 = (int)blockIdx.x * d.CW;
@@ -473,9 +477,9 @@ __global__ __launch_bounds__(IP_THREADS) void membrane_paste_kernel(uint8_t* __r
     IpTile t;
     ip_tile_make(t, ip_lds, y0, c0, rows, cn, feather);
     if ((long)t.a_bytes + t.t_bytes + t.r_bytes > lds_bytes) return;
-    if (!ip_feather_tile(t, msk, d, feather)) return;
+    if (!ip_feather_tile(t, msk, d, feather, (uint32_t)key)) return;
     const uint8_t* A = t.A;
-    if (alpha) ip_store_alpha(t, alpha, d);
+    if (alpha) ip_store_alpha(t, alpha, d, keys != nullptr);
     const int uo = (3 * cn + 6) >> 2;
     const float ff = (float)F;
     const long plane = 3L * g.gh * g.gw;
@@ -527,6 +531,35 @@ int mb_check_paste_args(const char* who, long img_bytes, long mask_bytes, long t
     return SHG_OK;
 }
 
+int mb_launch_setup(const void* src, long img_bytes, const void* mask, long mask_bytes, const int* keys, const int* table, long table_elems,
+                    const int* grids, const float* fake, float* g, float* field, long g_elems, void* omega, long omega_bytes, int B, int K, int R,
+                    int feather, int chunks, int bands, int lds_bytes, void* stream) {
+    SHG_CHECK_ARG(src && mask && table && grids && fake && g && field && omega, "membrane_setup: null pointer");
+    if (int rc = mb_check_paste_args("membrane_setup", img_bytes, mask_bytes, table_elems, B, K, R, feather, chunks, bands, lds_bytes)) return rc;
+    SHG_CHECK_ARG(g_elems >= 3 && g_elems <= 0x7fffffffL && omega_bytes >= 1 && omega_bytes <= 0x7fffffffL,
+                  "membrane_setup: g_elems must lie in [3, 2^31) and omega_bytes in [1, 2^31) (int32 offsets)");
+    SHG_CHECK_ARG(((reinterpret_cast<uintptr_t>(fake) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(field)) & 3) == 0,
+                  "membrane_setup: fake, g and field must be 4-byte aligned");
+    hipLaunchKernelGGL(membrane_setup_kernel, dim3(chunks, bands, B), dim3(IP_THREADS), (size_t)lds_bytes, (hipStream_t)stream, (const uint8_t*)src,
+                       img_bytes, (const uint8_t*)mask, mask_bytes, table, table_elems, grids, fake, g, field, g_elems, (uint8_t*)omega, omega_bytes,
+                       R, K, feather, lds_bytes, keys);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}
+
+int mb_launch_paste(void* out, long img_bytes, const void* mask, long mask_bytes, const int* keys, const int* table, long table_elems, const int* grids,
+                    const float* g, const float* field, long g_elems, void* alpha, int B, int K, int R, int feather, int chunks, int bands,
+                    int lds_bytes, void* stream) {
+    SHG_CHECK_ARG(out && mask && table && grids && g && field, "membrane_paste: null pointer");
+    if (int rc = mb_check_paste_args("membrane_paste", img_bytes, mask_bytes, table_elems, B, K, R, feather, chunks, bands, lds_bytes)) return rc;
+    SHG_CHECK_ARG(g_elems >= 3 && g_elems <= 0x7fffffffL, "membrane_paste: g_elems must lie in [3, 2^31) (int32 offsets)");
+    SHG_CHECK_ARG(((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(field)) & 3) == 0, "membrane_paste: g and field must be 4-byte aligned");
+    hipLaunchKernelGGL(membrane_paste_kernel, dim3(chunks, bands, B), dim3(IP_THREADS), (size_t)lds_bytes, (hipStream_t)stream, (uint8_t*)out, img_bytes,
+                       (const uint8_t*)mask, mask_bytes, table, table_elems, grids, g, field, g_elems, (uint8_t*)alpha, R, K, feather, lds_bytes, keys);
+    SHG_CHECK_LAUNCH();
+    return SHG_OK;
+}
+
 }  // namespace
 
 extern "C" int shg_membrane_tile(void) { return MB_TILE; }
@@ -543,31 +576,35 @@ extern "C" size_t shg_membrane_workspace_bytes(int P, int max_h, int max_w) {
 extern "C" int shg_inpaint_membrane_setup_f32(const void* src, long img_bytes, const void* mask, long mask_bytes, const int* table, long table_elems,
                                               const int* grids, const float* fake, float* g, float* field, long g_elems, void* omega,
                                               long omega_bytes, int B, int K, int R, int feather, int chunks, int bands, int lds_bytes, void* stream) {
-    SHG_CHECK_ARG(src && mask && table && grids && fake && g && field && omega, "membrane_setup: null pointer");
-    if (int rc = mb_check_paste_args("membrane_setup", img_bytes, mask_bytes, table_elems, B, K, R, feather, chunks, bands, lds_bytes)) return rc;
-    SHG_CHECK_ARG(g_elems >= 3 && g_elems <= 0x7fffffffL && omega_bytes >= 1 && omega_bytes <= 0x7fffffffL,
-                  "membrane_setup: g_elems must lie in [3, 2^31) and omega_bytes in [1, 2^31) (int32 offsets)");
-    SHG_CHECK_ARG(((reinterpret_cast<uintptr_t>(fake) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(field)) & 3) == 0,
-                  "membrane_setup: fake, g and field must be 4-byte aligned");
-    hipLaunchKernelGGL(membrane_setup_kernel, dim3(chunks, bands, B), dim3(IP_THREADS), (size_t)lds_bytes, (hipStream_t)stream, (const uint8_t*)src,
-                       img_bytes, (const uint8_t*)mask, mask_bytes, table, table_elems, grids, fake, g, field, g_elems, (uint8_t*)omega, omega_bytes,
-                       R, K, feather, lds_bytes);
-    SHG_CHECK_LAUNCH();
-    return SHG_OK;
+    return mb_launch_setup(src, img_bytes, mask, mask_bytes, nullptr, table, table_elems, grids, fake, g, field, g_elems, omega, omega_bytes, B, K, R,
+                           feather, chunks, bands, lds_bytes, stream);
 }
 
 // out as shg_inpaint_paste_u8; g / field: what setup wrote and the solver turned into c.
 extern "C" int shg_inpaint_membrane_paste_u8(void* out, long img_bytes, const void* mask, long mask_bytes, const int* table, long table_elems,
                                              const int* grids, const float* g, const float* field, long g_elems, void* alpha, int B, int K, int R,
                                              int feather, int chunks, int bands, int lds_bytes, void* stream) {
-    SHG_CHECK_ARG(out && mask && table && grids && g && field, "membrane_paste: null pointer");
-    if (int rc = mb_check_paste_args("membrane_paste", img_bytes, mask_bytes, table_elems, B, K, R, feather, chunks, bands, lds_bytes)) return rc;
-    SHG_CHECK_ARG(g_elems >= 3 && g_elems <= 0x7fffffffL, "membrane_paste: g_elems must lie in [3, 2^31) (int32 offsets)");
-    SHG_CHECK_ARG(((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(field)) & 3) == 0, "membrane_paste: g and field must be 4-byte aligned");
-    hipLaunchKernelGGL(membrane_paste_kernel, dim3(chunks, bands, B), dim3(IP_THREADS), (size_t)lds_bytes, (hipStream_t)stream, (uint8_t*)out, img_bytes,
-                       (const uint8_t*)mask, mask_bytes, table, table_elems, grids, g, field, g_elems, (uint8_t*)alpha, R, K, feather, lds_bytes);
-    SHG_CHECK_LAUNCH();
-    return SHG_OK;
+    return mb_launch_paste(out, img_bytes, mask, mask_bytes, nullptr, table, table_elems, grids, g, field, g_elems, alpha, B, K, R, feather, chunks, bands,
+                           lds_bytes, stream);
+}
+
+// The keyed forms (csrc/hole_label.hip; shg_inpaint_paste_keyed_u8 states the rule): `owner` stands where the mask went, window b takes
+// the holes whose byte equals keys[b] (device int [B], 1..255).  Descriptors, grids and LDS budget are those of the forms above.
+extern "C" int shg_inpaint_membrane_setup_keyed_f32(const void* src, long img_bytes, const void* owner, long mask_bytes, const int* keys,
+                                                    const int* table, long table_elems, const int* grids, const float* fake, float* g, float* field,
+                                                    long g_elems, void* omega, long omega_bytes, int B, int K, int R, int feather, int chunks,
+                                                    int bands, int lds_bytes, void* stream) {
+    SHG_CHECK_ARG(keys, "membrane_setup_keyed: null pointer");
+    return mb_launch_setup(src, img_bytes, owner, mask_bytes, keys, table, table_elems, grids, fake, g, field, g_elems, omega, omega_bytes, B, K, R,
+                           feather, chunks, bands, lds_bytes, stream);
+}
+
+extern "C" int shg_inpaint_membrane_paste_keyed_u8(void* out, long img_bytes, const void* owner, long mask_bytes, const int* keys, const int* table,
+                                                   long table_elems, const int* grids, const float* g, const float* field, long g_elems, void* alpha,
+                                                   int B, int K, int R, int feather, int chunks, int bands, int lds_bytes, void* stream) {
+    SHG_CHECK_ARG(keys, "membrane_paste_keyed: null pointer");
+    return mb_launch_paste(out, img_bytes, owner, mask_bytes, keys, table, table_elems, grids, g, field, g_elems, alpha, B, K, R, feather, chunks, bands,
+                           lds_bytes, stream);
 }
 
 // table: device int32 [P][4] = {h, w, float offset into field, byte offset into omega}, every h <= max_h and w <= max_w (a problem that

@@ -14,7 +14,13 @@ the torch composition:
 Bytes a kernel must move, over its time, beside the 6.0 / 6.3 TB/s of an in-order HBM sweep (MEASUREMENTS.md):
   gather   the windows' image and mask bytes read (4 ch cw) and the outputs written (3 R^2 + 4 R^2);
   paste    the windows' mask bytes, and per sample the generator's output (12 R^2) and the bytes read and written where A > 0 (6 per pixel).
-Prints one JSON line per measurement; ``--out`` also writes them to a file."""
+Prints one JSON line per measurement; ``--out`` also writes them to a file.
+
+``--holes N`` replaces the workload: N marks of about 200 x 150 scattered over each photograph, grouped on the device
+(``inpaint.label_holes``, csrc/hole_label.hip) into one window per group.  Reported: the label sequence (kernels alone on buffers made
+once, and the Python call) with the bytes it must move -- the mask read and the labels written, 5 per pixel -- beside the sweep, and
+``scipy.ndimage.label`` of the same dilated masks on the host (one reading, one thread: scipy's labelling is serial); the owner launch;
+gather and paste over the groups' windows (keyed) against the single window ``plan_window`` puts around all marks of a photograph."""
 import argparse
 import ctypes
 import json
@@ -77,6 +83,101 @@ def torch_paste(imgs, masks, windows, fake, k, feather):
     return outs
 
 
+def holes_bench(a, report_into):
+    import time
+    B, H, W, R, feather, N = a.images, a.height, a.width, a.resolution, a.feather, a.holes
+    rs = np.random.RandomState(1)
+    imgs = [rs.randint(0, 256, size=(H, W, 3), dtype=np.uint8) for _ in range(B)]
+    masks = []
+    for _ in range(B):
+        m = np.ones((H, W), np.uint8)
+        for _ in range(N):
+            bh, bw = 150 + int(rs.randint(-20, 21)), 200 + int(rs.randint(-20, 21))
+            ya, xa = int(rs.randint(0, H - bh)), int(rs.randint(0, W - bw))
+            m[ya:ya + bh, xa:xa + bw] = 0
+        masks.append(m)
+    packed, shapes = resize.pack_images(imgs)
+    pm, moffs = inpaint.pack_masks(masks)
+    shapes = np.concatenate([shapes.numpy().astype(np.int64), moffs[:, None]], axis=1)
+    packed, pm = packed.to(DEV), pm.to(DEV)
+    lib = _lib.get_lib()
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())                    # noqa: E731
+    px = int(pm.numel())
+
+    def report(what, times, nbytes=None, **extra):
+        for name, xs in times.items():
+            xs = sorted(xs)
+            rec = {'what': what, 'timing': name, 'us_median': round(xs[len(xs) // 2], 1), 'us_min': round(xs[0], 1), 'us_max': round(xs[-1], 1),
+                   'rounds': len(xs), 'iters_per_round': a.iters}
+            if name == 'kernel alone' and nbytes:
+                tbs = nbytes / xs[len(xs) // 2] * 1e-6
+                rec.update(bytes_to_move=int(nbytes), TB_per_s=round(tbs, 3), of_sweep=[round(tbs / s, 3) for s in SWEEP_TBS])
+            rec.update(extra)
+            report_into.append(rec)
+            print(json.dumps(rec), flush=True)
+
+    # the label sequence
+    lbl = inpaint.label_holes(pm, shapes, feather)
+    comps = inpaint.fetch_components(lbl)
+    sh = torch.from_numpy(shapes.astype(np.int32).reshape(-1)).to(DEV)
+    scratch = torch.empty(px, dtype=torch.int32, device=DEV)
+
+    def label_kernels():
+        _lib.check(lib.shg_hole_label_i32(ptr(pm), px, ptr(sh), B, H, W, feather + 1, lbl.max_components, ptr(lbl.labels), ptr(scratch),
+                                          ptr(lbl.state[1:]), ptr(lbl.state), st), 'inpaint_bench')
+    times = {'kernel alone': [], 'python call': []}
+    for _ in range(a.rounds):
+        times['kernel alone'].append(timed(label_kernels, 3, a.iters))
+        times['python call'].append(timed(lambda: inpaint.label_holes(pm, shapes, feather), 3, a.iters))
+    report(f'label_holes {B} x {H}x{W}, {N} marks each, feather {feather}', times, 5 * px, groups=int(comps.shape[0]))
+    try:
+        from scipy import ndimage
+        t0 = time.perf_counter()
+        n_host = 0
+        for m in masks:
+            D = ndimage.maximum_filter((m == 0).astype(np.uint8), size=2 * feather + 3, mode='constant', cval=0)
+            n_host += ndimage.label(D, structure=np.ones((3, 3)))[1]
+        host_us = (time.perf_counter() - t0) * 1e6
+        rec = {'what': 'scipy.ndimage maximum_filter + label of the same masks on the host', 'timing': 'one reading, 1 thread', 'us': round(host_us, 1),
+               'groups': int(n_host)}
+        report_into.append(rec)
+        print(json.dumps(rec), flush=True)
+    except ImportError:
+        print(json.dumps({'what': 'scipy is not installed: no host reading'}), flush=True)
+
+    # the owner launch
+    plan = inpaint.plan_windows(comps, shapes, R, 0.5, feather, max_windows=max(N, 1))
+    owner = inpaint.owner_plane(lbl, pm, shapes, plan.table)
+    tabd = torch.from_numpy(plan.table.astype(np.int32).reshape(-1)).to(DEV)
+
+    def owner_kernels():
+        _lib.check(lib.shg_hole_owner_u8(ptr(pm), px, ptr(sh), B, H, W, ptr(lbl.labels), ptr(tabd), plan.table.shape[0], ptr(scratch), ptr(owner), st),
+                   'inpaint_bench')
+    times = {'kernel alone': [], 'python call': []}
+    for _ in range(a.rounds):
+        times['kernel alone'].append(timed(owner_kernels, 3, a.iters))
+        times['python call'].append(timed(lambda: inpaint.owner_plane(lbl, pm, shapes, plan.table), 3, a.iters))
+    report(f'owner_plane {B} x {H}x{W}, {plan.table.shape[0]} groups', times, 10 * px)          # labels read twice, the mask read, the plane written
+
+    # gather + paste: the groups' windows against one window per photograph
+    one = np.array([inpaint.plan_window(m, R, 0.5, feather) for m in masks], np.int64)
+    nw = plan.image.shape[0]
+    wshapes = shapes[plan.image]
+    fake_n = torch.rand(nw, 3, R, R, device=DEV) * 1.6 - 0.8
+    fake_1 = torch.rand(B, 3, R, R, device=DEV) * 1.6 - 0.8
+    out = packed.clone().view(1, -1)
+    times = {'gather, per-group windows': [], 'gather, one window': [], 'paste (keyed), per-group windows': [], 'paste, one window': []}
+    for _ in range(a.rounds):
+        times['gather, per-group windows'].append(timed(lambda: inpaint.gather_windows(packed, pm, wshapes, plan.windows, R), 3, a.iters))
+        times['gather, one window'].append(timed(lambda: inpaint.gather_windows(packed, pm, shapes, one, R), 3, a.iters))
+        times['paste (keyed), per-group windows'].append(timed(lambda: inpaint.paste_back(packed, pm, wshapes, plan.windows, fake_n, feather=feather, out=out,
+                                                                                          owner=owner, keys=plan.key), 3, a.iters))
+        times['paste, one window'].append(timed(lambda: inpaint.paste_back(packed, pm, shapes, one, fake_1, feather=feather, out=out), 3, a.iters))
+    report(f'python calls, {nw} windows of {int((plan.windows[:, 2] * plan.windows[:, 3]).sum())} px against {B} of {int((one[:, 2] * one[:, 3]).sum())} px',
+           times)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--images', type=int, default=8)
@@ -87,9 +188,19 @@ def main():
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--holes', type=int, default=0, help='N > 0: scatter N marks per image and time the hole-group path instead')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('inpaint_bench needs a GPU')
+    if a.holes > 0:
+        records = []
+        holes_bench(a, records)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as fh:
+                for r in records:
+                    fh.write(json.dumps(r) + '\n')
+        return
     B, H, W, R, feather = a.images, a.height, a.width, a.resolution, a.feather
     rs = np.random.RandomState(0)
     imgs = [rs.randint(0, 256, size=(H, W, 3), dtype=np.uint8) for _ in range(B)]
