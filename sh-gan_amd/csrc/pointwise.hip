@@ -719,7 +719,14 @@ extern "C" int shg_modtail_backward_f32(const float* gy, const float* y, const f
 // activations) and its gradient as ONE launch each instead of a product and a cast (90 + 127 library launches per training step).
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void scale_cast_to_half_kernel(const float* x, _Float16* y, long n, float gain) {
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) y[e] = (_Float16)(x[e] * gain);
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
+        // The product stays a float32 value of its own (the empty asm pins it in a register): left to itself the compiler folds the
+        // multiplication and the conversion of the loop's remainder into v_fma_mixlo_f16 x, gain, +0, and (-0) + (+0) = +0 -- a product
+        // of -0 lost its sign there, and only for the elements the remainder handled.
+        float p = x[e] * gain;
+        asm volatile("" : "+v"(p));
+        y[e] = (_Float16)p;
+    }
 }
 __global__ __launch_bounds__(256) void scale_cast_to_float_kernel(const _Float16* x, float* y, long n, float gain) {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) y[e] = (float)x[e] * gain;

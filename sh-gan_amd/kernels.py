@@ -4,6 +4,7 @@ PyTorch is used for device memory and the current HIP stream only; every functio
 its tensors, allocates the output and enqueues exactly the HIP kernels of libshgan_hip.so on the
 current stream of the device that holds the operands.  CPU tensors are rejected (there is no CPU
 path in the product), and so are operands that live on different devices."""
+import collections
 import contextlib
 import ctypes
 import math
@@ -408,31 +409,48 @@ def _fma_operands(L, ts, names):
     return dt
 
 
-def fma(a, b, c=None):
-    """a * b + c with NumPy broadcasting (stylegan_utils/fma.py:15): operands are read through their strides, nothing is expanded.
-    c = None: the product alone (fma.py:41,44).  float32 or float64."""
-    L = _Launch()
-    dt = _fma_operands(L, (a, b, c), 'abc')
+FmaPlan = collections.namedtuple('FmaPlan', 'shape ops cshape strides')
+MulReducePlan = collections.namedtuple('MulReducePlan', 'ops cshape strides nk inner_kept empty')
+
+
+def fma_plan(a, b, c=None):
+    """The host half of ``fma`` (tensors of any device, nothing is launched): -> FmaPlan(shape = the broadcast result shape, ops = the
+    tensors whose pointers the kernel gets, cshape = the collapsed shape (at most six dimensions), strides = one element-stride list per
+    operand).  More than six non-mergeable dimensions: the operands are expanded into contiguous copies and walked as one run."""
     ts = [a, b] + ([c] if c is not None else [])
     shape = torch.broadcast_shapes(*[t.shape for t in ts])
     ex = [t.expand(shape) for t in ts]
-    y = torch.empty(shape, dtype=dt, device=L.dev)
     cshape, cst = _collapse(shape, [t.stride() for t in ex])
     if len(cshape) > 6:
-        ex = [t.contiguous() for t in ex]
-        cshape, cst = [y.numel()], [[1]] * len(ex)
+        ts = [t.contiguous() for t in ex]
+        cshape, cst = [math.prod(shape)], [[1]] * len(ts)
+    return FmaPlan(shape, ts, cshape, cst)
+
+
+def fma(a, b, c=None):
+    """a * b + c with NumPy broadcasting (stylegan_utils/fma.py:15): operands are read through their strides, nothing is expanded
+    (but above six non-mergeable dimensions, ``fma_plan``).  c = None: the product alone (fma.py:41,44).  float32 or float64."""
+    L = _Launch()
+    dt = _fma_operands(L, (a, b, c), 'abc')
+    plan = fma_plan(a, b, c)
+    y = torch.empty(plan.shape, dtype=dt, device=L.dev)
+    if y.numel() == 0:
+        return y                                                          # (a tensor of no elements has no address to hand over)
+    ops, cshape, cst = plan.ops, plan.cshape, plan.strides
     with L:
-        check(_lib.get_lib().shg_fma_bcast(_ptr(a), _ptr(b), _ptr(c), _ptr(y), len(cshape), _larr(cshape), _larr(cst[0]), _larr(cst[1]),
-                                           _larr(cst[2]) if c is not None else None, int(dt == torch.float64), L.stream()), 'fma')
-    del ex
+        check(_lib.get_lib().shg_fma_bcast(_ptr(ops[0]), _ptr(ops[1]), _ptr(ops[2]) if c is not None else None, _ptr(y), len(cshape), _larr(cshape),
+                                           _larr(cst[0]), _larr(cst[1]), _larr(cst[2]) if c is not None else None, int(dt == torch.float64),
+                                           L.stream()), 'fma')
+    del plan, ops
     return y
 
 
-def mul_reduce(g, b, shape):
-    """``_unbroadcast(g * b, shape)`` (fma.py:48-58; b = None: ``_unbroadcast(g, shape)``) in one pass: the product is summed over
-    the dimensions along which an operand of ``shape`` was broadcast to ``g.shape``; returns a tensor of ``shape``."""
-    L = _Launch()
-    dt = _fma_operands(L, (g, b), 'gb')
+def mul_reduce_plan(g, b, shape):
+    """The host half of ``mul_reduce`` (tensors of any device, nothing is launched): -> MulReducePlan(ops = [g] or [g, b expanded] as the
+    kernel reads them, cshape = collapsed sizes KEPT FIRST, REDUCED LAST, strides = one list per operand in that order, nk = the number of
+    kept dimensions, inner_kept = the mapping, empty = g has no element while ``shape`` has some: the result is zeros, nothing to launch).
+    More than six non-mergeable dimensions: contiguous copies first; if that does not do, copies with the kept dimensions in front, which
+    collapse to at most two."""
     shape = tuple(shape)
     extra = g.ndim - len(shape)
     if extra < 0:
@@ -443,30 +461,47 @@ def mul_reduce(g, b, shape):
     for i in range(g.ndim):
         if full[i] not in (1, g.shape[i]):
             raise _lib.ShgError(f'mul_reduce: {shape} does not broadcast to {tuple(g.shape)}')
-    out = torch.empty(shape, dtype=dt, device=L.dev)
     kept = [i for i in range(g.ndim) if i not in red]
-    ops = [g] + ([bx] if bx is not None else [])
-    kshape, kst = _collapse([g.shape[i] for i in kept], [[t.stride(i) for i in kept] for t in ops])
-    rshape, rst = _collapse([g.shape[i] for i in red], [[t.stride(i) for i in red] for t in ops])
-    if len(kshape) + len(rshape) > 6:
-        g = g.contiguous()
-        bx = bx.contiguous() if bx is not None else None
-        ops = [g] + ([bx] if bx is not None else [])
+
+    def collapsed(ops):
         kshape, kst = _collapse([g.shape[i] for i in kept], [[t.stride(i) for i in kept] for t in ops])
         rshape, rst = _collapse([g.shape[i] for i in red], [[t.stride(i) for i in red] for t in ops])
-        if len(kshape) + len(rshape) > 6:
-            raise _lib.ShgError('mul_reduce: more than six non-mergeable dimensions')
-    sg = kst[0] + rst[0]
-    sb = (kst[1] + rst[1]) if bx is not None else None
+        return kshape, kst, rshape, rst
+    ops = [g] + ([bx] if bx is not None else [])
+    kshape, kst, rshape, rst = collapsed(ops)
+    if len(kshape) + len(rshape) > 6:
+        ops = [t.contiguous() for t in ops]
+        kshape, kst, rshape, rst = collapsed(ops)
+    if len(kshape) + len(rshape) > 6:
+        # kept dimensions in front: each group is one contiguous run of the copy (strides read off the permuted view, sizes as before)
+        ops = [t.permute(kept + red).contiguous().permute([(kept + red).index(i) for i in range(g.ndim)]) for t in ops]
+        kshape, kst, rshape, rst = collapsed(ops)
     # the fastest-varying dimension of g (smallest non-zero stride): kept -> thread per output, reduced -> workgroup per output
     def fastest(st):
         v = [abs(x) for x in st if x]
         return min(v) if v else float('inf')
     inner_kept = int(not rshape or (bool(kshape) and fastest(kst[0]) < fastest(rst[0])))
+    return MulReducePlan(ops, kshape + rshape, [k + r for k, r in zip(kst, rst)], len(kshape), inner_kept,
+                         g.numel() == 0 and math.prod(shape) > 0)
+
+
+def mul_reduce(g, b, shape):
+    """``_unbroadcast(g * b, shape)`` (fma.py:48-58; b = None: ``_unbroadcast(g, shape)``) in one pass: the product is summed over
+    the dimensions along which an operand of ``shape`` was broadcast to ``g.shape``; returns a tensor of ``shape``."""
+    L = _Launch()
+    dt = _fma_operands(L, (g, b), 'gb')
+    plan = mul_reduce_plan(g, b, shape)
+    if plan.empty:
+        return torch.zeros(tuple(shape), dtype=dt, device=L.dev)              # a sum of no terms (as torch's _unbroadcast)
+    out = torch.empty(tuple(shape), dtype=dt, device=L.dev)
+    if out.numel() == 0:
+        return out
+    ops, st = plan.ops, plan.strides
     with L:
-        check(_lib.get_lib().shg_mul_reduce(_ptr(g), _ptr(bx), _ptr(out), len(kshape) + len(rshape), len(kshape), _larr(kshape + rshape),
-                                            _larr(sg), _larr(sb) if sb is not None else None, inner_kept, int(dt == torch.float64),
-                                            L.stream()), 'mul_reduce')
+        check(_lib.get_lib().shg_mul_reduce(_ptr(ops[0]), _ptr(ops[1]) if b is not None else None, _ptr(out), len(plan.cshape), plan.nk,
+                                            _larr(plan.cshape), _larr(st[0]), _larr(st[1]) if b is not None else None, plan.inner_kept,
+                                            int(dt == torch.float64), L.stream()), 'mul_reduce')
+    del plan, ops
     return out
 
 

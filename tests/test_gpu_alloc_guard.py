@@ -313,7 +313,7 @@ def test_entry_point(case):
 
 # ------------------------------------------------------------------------------------------------
 # d. entry points whose buffers come from an initialising factory only, so that the fill test has no case for them: the tail of the ADA
-# pipe (``torch.zeros`` results).  The shapes, references and bars are those of tests/test_gpu_ada_tail.py.
+# pipe and the empty reduction of ``mul_reduce`` (``torch.zeros`` results).  The shapes, references and bars are those of tests/test_gpu_ada_tail.py.
 # ------------------------------------------------------------------------------------------------
 
 def ada_tail_apply_case():
@@ -354,9 +354,24 @@ def ada_tail_params_case():
     return (lambda: list(pipe.tail_params((None, None, utd, gtd)))), check
 
 
+def mul_reduce_empty_case():
+    """``mul_reduce`` of a gradient of no elements into a non-empty shape (an empty batch through the backward of the public ``fma``): a sum
+    of no terms, returned from ``torch.zeros`` without a launch; float32 and float64, with and without the second factor."""
+    import shgan_amd  # noqa: F401
+    from shgan_amd import kernels as kk
+    gs = [torch.zeros(0, 3, dtype=dt, device=DEV) for dt in (torch.float32, torch.float64)]
+    bs = [torch.ones(1, 3, dtype=g.dtype, device=DEV) for g in gs]
+
+    def check(out):
+        for k, got in enumerate(out):
+            assert tuple(got.shape) == (1, 3) and got.dtype == gs[k // 2].dtype and torch.equal(got.cpu(), torch.zeros(1, 3, dtype=got.dtype))
+    return (lambda: [kk.mul_reduce(g, b, (1, 3)) for g, bb in zip(gs, bs) for b in (None, bb)]), check
+
+
 ADDED = {
     'ada_tail:apply': ada_tail_apply_case,
     'ada_tail:params': ada_tail_params_case,
+    'ops:mul_reduce_empty': mul_reduce_empty_case,
 }
 
 
@@ -379,6 +394,7 @@ INIT_SITES = {
     ('grad_sync.py', '__init__'): ['optim:adam_ema'],
     ('image_metrics.py', '__init__'): ['metrics:psnr_ssim'],
     ('inception_score.py', 'new_accumulator'): ['metrics:kid_is_fid'],
+    ('kernels.py', 'mul_reduce'): ['ops:mul_reduce_empty'],
     ('losses.py', '__init__'): ['module:loss_Dmain', 'module:loss_Gmain'],
     ('lpips.py', '__call__'): ['lpips:distance', 'lpips:vgg_distance'],
     ('masks.py', 'lama_rasterize'): ['masks:lama'],

@@ -544,10 +544,11 @@ NOT_ROUTED = {
     'weight_scale_kernel / weight_transpose_kernel / weight_sq_kernel (conv_mfma.hip), wino_weight_kernel, wino4_weight_kernel, '
     'poly_weight_kernel': 'weight preparation: one kernel per layout, no choice; every convolution case above consumes its output',
     'fma_kernel, fma_bcast_kernel<float|double>, mul_reduce_kernel<float|double>': 'one kernel per dtype, no shape or alignment '
-    'dispatch; compared with torch in test_gpu_ops.py and test_gpu_parity_r2.py',
+    'dispatch; their grid caps, reduction tails and stride plans are held to float64 in test_gpu_pointwise_edges.py (the plans on the host in '
+    'test_pointwise_plan_cpu.py)',
     'planes_to_image_kernel, modtail_backward_f32_kernel, scale_cast_to_half_kernel, scale_cast_to_float_kernel, sum_partials_kernel, '
     'scale_channels_kernel, composite_u8_kernel, assemble_input_kernel, assemble_input_u8_kernel': 'single-kernel entry points without a '
-    'route choice; covered by test_gpu_ops.py, test_gpu_r6_ops.py, test_gpu_parity_r2.py and test_gpu_eval_loop.py',
+    'route choice; their grid caps, loop remainders, channel slices and argument checks are held to float64 in test_gpu_pointwise_edges.py',
     'float16 kernels of pointwise.hip and conv_f16*.hip': 'the fp16 entry points have a route table of their own, test_gpu_routes_fp16.py (every '
     'launch site of conv_f16*.hip by kernel name, both sides of each predicate, against float64)',
 }
