@@ -506,10 +506,9 @@ static int wgrad_slices(int NB, int I, int O, int OH, int OW, int taps) {
     // 3x3: ONE workgroup per CU in ONE round (238 registers x 512 threads: a CU holds one) -- 256 / 512 / 768 / 1024 workgroups measured
     // 86 / 83 / 80 / 78 TFLOP/s at 64 channels x 512^2 and 34 / 29 / 25 / 23 at 512 channels x 16^2 (every further round re-pays prologue,
     // epilogue and 147 KB of partial sums per workgroup); the thin 1x1 layers are load-bound and want more workgroups in flight
+    // (the partial sums need no byte cap of their own: s >= 2 means fewer tiles than the target, and s slices of `tiles` 64 x 64 blocks hold
+    // less than 2 x 256 x 16 KiB x 9 = 72 MiB at 3x3, 2 x 1024 x 16 KiB = 32 MiB at 1x1 -- tests/test_plan_f32_cpu.py holds that for I, O <= 4096)
     long s = ((taps > 1 ? 256 : 4 * 256) + tiles - 1) / tiles;
-    const long per_slice = (long)O * I * taps * (long)sizeof(float);
-    const long cap = (256L << 20) / per_slice;                   // at most 256 MB of partial sums
-    if (s > cap) s = cap;
     if (s > nchunk) s = nchunk;
     if (s > 1024) s = 1024;
     return s < 1 ? 1 : (int)s;

@@ -31,14 +31,26 @@ def any_hit(pattern, names):
 def launched(fn, expect=(), attempts=3):
     """-> (fn(), kernel names).  The tracer occasionally drops the events of a short region: with ``expect`` given, the call is repeated
     (at most ``attempts`` times) until every expected pattern shows up; the names of the last attempt are returned either way."""
+    out, counts = launch_counts(fn, expect=expect, attempts=attempts)
+    return out, set(counts)
+
+
+def launch_counts(fn, expect=(), attempts=3, want=None):
+    """-> (fn(), {name: launches}), the ``count`` of the profiler's averages (host operator names come along; the patterns name kernels
+    only), for paths that show as a second launch of the same kernel.  ``want``: {pattern: launches}; the call is repeated like ``launched``'s
+    while an expected pattern is absent OR a wanted count is short (the tracer can drop one of two launches as well as both)."""
     from torch.profiler import ProfilerActivity, profile
-    out, names = None, set()
+    out, counts = None, {}
     for _ in range(attempts):
         torch.cuda.synchronize()
         with profile(activities=[ProfilerActivity.CUDA]) as prof:
             out = fn()
             torch.cuda.synchronize()
-        names = {e.key for e in prof.key_averages()}        # (host operator names come along; the patterns name kernels only)
-        if all(any_hit(p, names) for p in expect):
+        counts = {e.key: int(e.count) for e in prof.key_averages()}
+        if all(any_hit(p, counts) for p in expect) and all(count_of(p, counts) >= n for p, n in (want or {}).items()):
             break
-    return out, names
+    return out, counts
+
+
+def count_of(pattern, counts):
+    return sum(n for name, n in counts.items() if hit(pattern, name))

@@ -4,7 +4,12 @@ Every entry point picks one of several HIP kernels -- often one of several templ
 pointers, its epilogue arguments and the module switches.  Each case below names the kernel (or instantiation) that must serve its input and
 the ones that must not, and compares the result with a float64 CPU evaluation of the same math.  The cases sit one step either side of every
 dispatch predicate, so a changed constant or predicate moves a case off its route and fails it.  The last test checks that the table covers
-every kernel these entry points can launch (the hipLaunchKernelGGL sites of the .hip sources)."""
+every kernel these entry points can launch (the hipLaunchKernelGGL sites of the .hip sources).
+
+What happens INSIDE a route -- the tail split of the one-workgroup-per-CU direct kernels, ragged and halved K splits and their grid-stride
+reductions, tile_search's tile shapes, second trips of the plane-walking FIR kernels, partial workgroups of the marching kernels, several chunks
+per weight-gradient slice -- is held to float64 in test_gpu_loop_bounds_fp32.py (the launch plans on the host in plan_f32.py and
+test_plan_f32_cpu.py); the cases here are a few workgroups each and reach none of it."""
 import numpy as np
 import pytest
 import torch
@@ -543,6 +548,8 @@ ROUTE_KERNELS = [
 NOT_ROUTED = {
     'weight_scale_kernel / weight_transpose_kernel / weight_sq_kernel (conv_mfma.hip), wino_weight_kernel, wino4_weight_kernel, '
     'poly_weight_kernel': 'weight preparation: one kernel per layout, no choice; every convolution case above consumes its output',
+    'splitk_reduce_kernel, wino_split_reduce_kernel past their grid caps; the fix launch of conv_mfma_kernel': 'routed above at '
+    'one trip; their second trips, ragged slices and the tail split are loop bounds, held in test_gpu_loop_bounds_fp32.py',
     'fma_kernel, fma_bcast_kernel<float|double>, mul_reduce_kernel<float|double>': 'one kernel per dtype, no shape or alignment '
     'dispatch; their grid caps, reduction tails and stride plans are held to float64 in test_gpu_pointwise_edges.py (the plans on the host in '
     'test_pointwise_plan_cpu.py)',
