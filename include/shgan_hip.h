@@ -468,8 +468,9 @@ int shg_vgg16_maxpool2_f32(const float* x, float* y, int B, int C, int H, int W,
 
 /* ---- LPIPS, AlexNet backbone: `lpips.LPIPS(net='alex')` as lib/evaluator/eva_lpips.py:39-52 calls it (sh-gan_amd/lpips.py drives it;
  * csrc/lpips.hip).  conv2..conv5 and the max pools run on the detector's convolution and pool entry points above.
- * Conv1 weight prep: w [64,3,11,11], bias [64] -> wp [SHG_LPIPS_CONV1_WP_ELEMS] floats ([368][64], k = (ky*11 + kx)*3 + c, zero
- *   rows beyond K = 363), bp [64]; once per network.
+ * Conv1 weight prep: w [64,3,11,11], bias [64] -> wp [SHG_LPIPS_CONV1_WP_ELEMS] floats, bp [64] in the layout of
+ *   shg_inception_weight_prep_f32 for (O, I, kh, kw) = (64, 3, 11, 11), a kernel size that entry point itself refuses: [368][64],
+ *   k = (ky*11 + kx)*3 + c, zero rows beyond K = 363; once per network.
  * Conv1: x [B,3,H,W] -> y [B,64,OH,OW] = relu(conv2d(s(v), w, stride 4, pad 2) + bias), OH = (H + 4 - 11) / 4 + 1, H and W >= 7, on
  *   exact-fp32 MFMA.  v = lut[x] when lut [256] is given (x uint8), else ((x*scale + bias) - 0.5) * 2 with every step rounded to float32
  *   (x float32; x*scale + bias is the evaluator batch's [0, 1] form, the rest eva_lpips.py:39-40); s(v) = (v - shift[c]) * float32(1 /

@@ -10,12 +10,9 @@
 // The epilogue writes at a channel offset of the Mixed block's concat buffer (no concat pass).  Several independent convolutions
 // (the branches of a Mixed block at one depth) are one grouped launch; a group may split K over `splitk` workgroups, whose fp32
 // partial sums go to the workspace and are added in a fixed order (split index ascending) by a second, grouped launch.
-#include "shg_device.h"
+#include "det_conv_tile.h"
 #include "../../include/shgan_hip.h"
 
-#define INC_BM 64        // output channels per workgroup
-#define INC_BN 64        // output pixels per workgroup
-#define INC_BK 16        // K per stage
 #define INC_OUT 299      // the detector's input resolution
 
 struct IncConvArgs {
@@ -27,8 +24,8 @@ struct IncConvArgs {
 };
 
 __global__ __launch_bounds__(256) void inc_conv_kernel(const IncConvArgs a) {
-    __shared__ float Ws[2][INC_BK][INC_BM];
-    __shared__ float Xs[2][INC_BK][INC_BN];
+    __shared__ float Ws[2][DET_BK][DET_BM];
+    __shared__ float Xs[2][DET_BK][DET_BN];
     int gi = 0;
     while (gi + 1 < a.G && (int)blockIdx.x >= a.first_block[gi + 1]) ++gi;
     const shg_inc_conv_desc& g = a.g[gi];
@@ -36,18 +33,15 @@ __global__ __launch_bounds__(256) void inc_conv_kernel(const IncConvArgs a) {
     const int S = g.splitk;
     const int s = local % S;
     local /= S;
-    const int NT = (g.O + INC_BM - 1) / INC_BM, Np = NT * INC_BM;
+    const int NT = (g.O + DET_BM - 1) / DET_BM, Np = NT * DET_BM;
     const int nt = local % NT, mt = local / NT;
     const int OHW = g.OH * g.OW, M = a.B * OHW;
-    const int K = g.I * g.kh * g.kw, KT = (K + INC_BK - 1) / INC_BK;
+    const int K = g.I * g.kh * g.kw, KT = (K + DET_BK - 1) / DET_BK;
     const int chunk = (KT + S - 1) / S, kt0 = s * chunk, kt1 = min(KT, kt0 + chunk);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool fast = (g.I % INC_BK) == 0;
+    const DetRoles t = det_roles();
+    const bool fast = (g.I % DET_BK) == 0;
 
-    // staging roles: X rows kr0 + 4i (i < 4) of pixel px; W row wr, columns wc..wc+3
-    const int px = tid & 63, kr0 = tid >> 6;
-    const int wr = tid >> 4, wc = (tid & 15) * 4;
-    const int m = mt * INC_BN + px;
+    const int m = mt * DET_BN + t.px;
     const bool mvalid = m < M;
     int b = 0, oy = 0, ox = 0;
     if (mvalid) {
@@ -59,19 +53,17 @@ __global__ __launch_bounds__(256) void inc_conv_kernel(const IncConvArgs a) {
     const int iy0 = oy * g.sh - g.ph, ix0 = ox * g.sw - g.pw;
     const long HW = (long)g.H * g.W;
     const float* xb = g.x + ((long)b * g.x_ctot + g.x_coff) * HW;
-    const float* wp = g.w + (long)nt * INC_BM + wc;
+    const float* wp = g.w + (long)nt * DET_BM + t.wc;
 
-    float xr[4];
-    float4 wreg;
-    auto load = [&](int kt) {
-        wreg = *reinterpret_cast<const float4*>(wp + (long)(kt * INC_BK + wr) * Np);
-        const int kb = kt * INC_BK;
+    const f32x16 acc = det_conv_tile(Ws, Xs, kt0, kt1, [&](int kt, float (&xr)[4], float4& wreg) {
+        wreg = *reinterpret_cast<const float4*>(wp + (long)(kt * DET_BK + t.wr) * Np);
+        const int kb = kt * DET_BK;
         if (fast) {
             const int tap = kb / g.I, c0 = kb - tap * g.I;
             const int ky = tap / g.kw, kx = tap - ky * g.kw;
             const int iy = iy0 + ky, ix = ix0 + kx;
             const bool ok = mvalid && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W;
-            const float* p = xb + (long)(c0 + kr0) * HW + (long)iy * g.W + ix;
+            const float* p = xb + (long)(c0 + t.kr0) * HW + (long)iy * g.W + ix;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 xr[i] = 0.f;
@@ -80,7 +72,7 @@ __global__ __launch_bounds__(256) void inc_conv_kernel(const IncConvArgs a) {
         } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int k = kb + kr0 + 4 * i;
+                const int k = kb + t.kr0 + 4 * i;
                 xr[i] = 0.f;
                 if (mvalid && k < K) {
                     const int tap = k / g.I, c = k - tap * g.I;
@@ -90,49 +82,24 @@ __global__ __launch_bounds__(256) void inc_conv_kernel(const IncConvArgs a) {
                 }
             }
         }
-    };
+    });
 
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;     // the wave's channel / pixel sub-tile
-    const int lk = lane >> 5, lj = lane & 31;
-    if (kt0 < kt1) {
-        load(kt0);
-        int buf = 0;
-        for (int kt = kt0; kt < kt1; ++kt) {
-            *reinterpret_cast<float4*>(&Ws[buf][wr][wc]) = wreg;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) Xs[buf][kr0 + 4 * i][px] = xr[i];
-            __syncthreads();
-            if (kt + 1 < kt1) load(kt + 1);                    // next step's loads in flight under this step's MFMAs
-#pragma unroll
-            for (int kk = 0; kk < INC_BK; kk += 2) {
-                const float av = Ws[buf][kk + lk][wm + lj];
-                const float bv = Xs[buf][kk + lk][wn + lj];
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-            }
-            buf ^= 1;
-        }
-    }
-
-    // D[i][j]: channel i = (r&3) + 8(r>>2) + 4(lane>>5), pixel j = lane&31
-    const int mo = mt * INC_BN + wn + lj;
+    const int mo = mt * DET_BN + t.wn + t.lj;
     if (mo >= M) return;
-    const int ob = nt * INC_BM + wm + 4 * lk;
+    const int ob = nt * DET_BM + t.wm;
     if (S == 1) {
         const int bo = mo / OHW, pix = mo - bo * OHW;
         float* yb = g.y + ((long)bo * g.y_ctot + g.y_coff) * OHW + pix;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = ob + (r & 3) + 8 * (r >> 2);
+            const int o = ob + t.row(r);
             if (o < g.O) yb[(long)o * OHW] = fmaxf(acc[r] + g.bias[o], 0.f);
         }
     } else {
         float* wsb = a.ws + a.ws_off[gi] + (long)s * g.O * M + mo;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = ob + (r & 3) + 8 * (r >> 2);
+            const int o = ob + t.row(r);
             if (o < g.O) wsb[(long)o * M] = acc[r];
         }
     }
@@ -168,7 +135,7 @@ static int inc_check_group(const shg_inc_conv_desc& d, int i) {
                   d.x_coff, d.x_coff + d.I, d.x_ctot);
     SHG_CHECK_ARG(d.y_coff >= 0 && d.y_coff + d.O <= d.y_ctot, "inception_conv: group %d: channel offset %d + O %d exceeds the output's %d channels",
                   i, d.y_coff, d.O, d.y_ctot);
-    const int KT = (d.I * d.kh * d.kw + INC_BK - 1) / INC_BK;
+    const int KT = (d.I * d.kh * d.kw + DET_BK - 1) / DET_BK;
     SHG_CHECK_ARG(d.splitk >= 1 && d.splitk <= 16 && (d.splitk - 1) * ((KT + d.splitk - 1) / d.splitk) < KT,
                   "inception_conv: group %d: splitk %d leaves a split without K steps (%d steps)", i, d.splitk, KT);
     return SHG_OK;
@@ -187,7 +154,7 @@ extern "C" size_t shg_inception_conv_workspace_bytes(const shg_inc_conv_desc* gr
 
 extern "C" long shg_inception_packed_weight_elems(int O, int I, int kh, int kw) {
     if (O < 1 || I < 1 || kh < 1 || kw < 1) return -1;
-    const long Kp = ((long)I * kh * kw + INC_BK - 1) / INC_BK * INC_BK, Np = ((long)O + INC_BM - 1) / INC_BM * INC_BM;
+    const long Kp = ((long)I * kh * kw + DET_BK - 1) / DET_BK * DET_BK, Np = ((long)O + DET_BM - 1) / DET_BM * DET_BM;
     return Kp * Np;
 }
 
@@ -211,7 +178,7 @@ extern "C" int shg_inception_conv_f32(const shg_inc_conv_desc* groups, int G, in
         a.ws_off[i] = off;
         off += inc_ws_floats(d, B);
         split |= d.splitk > 1;
-        const long mt = ((long)B * d.OH * d.OW + INC_BN - 1) / INC_BN, nt = (d.O + INC_BM - 1) / INC_BM;
+        const long mt = ((long)B * d.OH * d.OW + DET_BN - 1) / DET_BN, nt = (d.O + DET_BM - 1) / DET_BM;
         blocks += mt * nt * d.splitk;
         SHG_CHECK_ARG(blocks < (1L << 31), "inception_conv: too many workgroups");
         a.first_block[i + 1] = (int)blocks;
@@ -245,24 +212,24 @@ __global__ __launch_bounds__(256) void inc_weight_prep_kernel(const float* w, co
     wp[e] = v;
 }
 
-extern "C" int shg_inception_weight_prep_f32(const float* w, const float* bias, float* wp, float* bp, int O, int I, int kh, int kw, void* stream) {
-    SHG_CHECK_ARG(w && bias && wp && bp, "inception_weight_prep: null pointer");
+int shg_det_weight_prep(const float* w, const float* bias, float* wp, float* bp, int O, int I, int kh, int kw, hipStream_t stream) {
     const long n = shg_inception_packed_weight_elems(O, I, kh, kw);
-    SHG_CHECK_ARG(n > 0 && kh <= 7 && kw <= 7, "inception_weight_prep: bad shape O %d I %d %dx%d", O, I, kh, kw);
-    const int Kp = (I * kh * kw + INC_BK - 1) / INC_BK * INC_BK, Np = (O + INC_BM - 1) / INC_BM * INC_BM;
-    hipLaunchKernelGGL(inc_weight_prep_kernel, dim3(shg_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, w, bias, wp, bp, O, I, kh, kw, Kp, Np);
+    const int Kp = (I * kh * kw + DET_BK - 1) / DET_BK * DET_BK, Np = (O + DET_BM - 1) / DET_BM * DET_BM;
+    hipLaunchKernelGGL(inc_weight_prep_kernel, dim3(shg_cdiv(n, 256)), dim3(256), 0, stream, w, bias, wp, bp, O, I, kh, kw, Kp, Np);
     SHG_CHECK_LAUNCH();
     return SHG_OK;
+}
+
+extern "C" int shg_inception_weight_prep_f32(const float* w, const float* bias, float* wp, float* bp, int O, int I, int kh, int kw, void* stream) {
+    SHG_CHECK_ARG(w && bias && wp && bp, "inception_weight_prep: null pointer");
+    SHG_CHECK_ARG(shg_inception_packed_weight_elems(O, I, kh, kw) > 0 && kh <= 7 && kw <= 7, "inception_weight_prep: bad shape O %d I %d %dx%d", O, I,
+                  kh, kw);
+    return shg_det_weight_prep(w, bias, wp, bp, O, I, kh, kw, (hipStream_t)stream);
 }
 
 // ---- front end: value map, TF1 legacy bilinear resize to 299 x 299 (source = i * size / 299, no half-pixel offset, border clamp),
 // (v - 128) / 128.  The value of a source sample is lut[u8] (uint8 input) or v*scale + bias rounded twice (float input: the reference's
 // `real.float()*127.5 + 127.5`).  Skipped resize when the input is 299 x 299.
-__device__ __forceinline__ float inc_fetch(const void* x, const float* lut, float scale, float bias, long i) {
-    if (lut) return lut[reinterpret_cast<const uint8_t*>(x)[i]];
-    return __fadd_rn(__fmul_rn(reinterpret_cast<const float*>(x)[i], scale), bias);
-}
-
 __global__ __launch_bounds__(256) void inc_frontend_kernel(const void* x, const float* lut, float scale, float bias, float* y, int B, int H, int W) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     const long plane = (long)INC_OUT * INC_OUT;
@@ -272,7 +239,7 @@ __global__ __launch_bounds__(256) void inc_frontend_kernel(const void* x, const 
     const long base = bc * (long)H * W;
     float v;
     if (H == INC_OUT && W == INC_OUT) {
-        v = inc_fetch(x, lut, scale, bias, base + r);
+        v = det_value(x, lut, scale, bias, base + r);
     } else {
         // source = i * size / 299 as an integer part and a fraction (num % 299) / 299: exact to one rounding of the fraction (a float32
         // coordinate would carry an error of ~1e-4 pixel at 1024); at and beyond the last sample the border clamp leaves fraction 0
@@ -281,8 +248,8 @@ __global__ __launch_bounds__(256) void inc_frontend_kernel(const void* x, const 
         if (y0 >= H - 1) { y0 = H - 1; fy = 0.f; }
         if (x0 >= W - 1) { x0 = W - 1; fx = 0.f; }
         const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
-        const float v00 = inc_fetch(x, lut, scale, bias, base + (long)y0 * W + x0), v01 = inc_fetch(x, lut, scale, bias, base + (long)y0 * W + x1);
-        const float v10 = inc_fetch(x, lut, scale, bias, base + (long)y1 * W + x0), v11 = inc_fetch(x, lut, scale, bias, base + (long)y1 * W + x1);
+        const float v00 = det_value(x, lut, scale, bias, base + (long)y0 * W + x0), v01 = det_value(x, lut, scale, bias, base + (long)y0 * W + x1);
+        const float v10 = det_value(x, lut, scale, bias, base + (long)y1 * W + x0), v11 = det_value(x, lut, scale, bias, base + (long)y1 * W + x1);
         v = v00 * ((1.f - fx) * (1.f - fy)) + v01 * (fx * (1.f - fy)) + v10 * ((1.f - fx) * fy) + v11 * (fx * fy);
     }
     y[e] = __fmul_rn(__fsub_rn(v, 128.f), 0.0078125f);

@@ -18,24 +18,32 @@
 // shg_lpips_head_pairs_f32: the same head for a table of P pairs (ia[p], ib[p]) of rows of ONE feature tensor f [M,C,h,w] -- the same
 //   per-tile function, the same butterfly, the same finish: a pair's bits are those of shg_lpips_head_f32 on (f[ia], f[ib]) and depend
 //   neither on P nor on the pair's place in the table.
-#include "shg_device.h"
+#include "det_conv_tile.h"
 #include "../../include/shgan_hip.h"
 
-#define LP_BM 64                        // output channels (all of conv1's)
-#define LP_BN 64                        // output pixels per workgroup
-#define LP_BK 16                        // K per stage
 #define LP_K 363                        // 3 * 11 * 11
-#define LP_KT ((LP_K + LP_BK - 1) / LP_BK)
-#define LP_KP (LP_KT * LP_BK)
+#define LP_KT ((LP_K + DET_BK - 1) / DET_BK)
 #define LP_HEAD_THREADS 256
 
 namespace {
+
+struct LpScale { float shift[3], inv[3]; };     // scaling layer: (v - shift) * inv
+
+// shift, scaling: HOST arrays of 3 floats -> the kernels' form; a scale of 0 is refused
+int lp_scale_make(const float* shift, const float* scaling, const char* who, LpScale* s) {
+    SHG_CHECK_ARG(scaling[0] != 0.f && scaling[1] != 0.f && scaling[2] != 0.f, "%s: a scaling-layer scale of 0", who);
+    for (int c = 0; c < 3; ++c) {
+        s->shift[c] = shift[c];
+        s->inv[c] = (float)(1.0 / (double)scaling[c]);
+    }
+    return SHG_OK;
+}
 
 struct LpConv1Args {
     const void* x;
     const float* lut;                   // uint8 operands: value of every code after `(x - 0.5) * 2`; NULL: float32 elements
     float scale, bias;                  // float32 operands: u = x*scale + bias (the evaluator batch's [0, 1] form), v = (u - 0.5) * 2
-    float shift[3], inv[3];             // scaling layer: (v - shift) * inv
+    LpScale s;
     const float* wp;
     const float* bp;
     float* y;
@@ -46,21 +54,19 @@ __device__ __forceinline__ float lp_scaled(float v, float shift, float inv) { re
 
 template <bool U8>
 __global__ __launch_bounds__(256) void lp_conv1_kernel(const LpConv1Args a) {
-    __shared__ float Ws[2][LP_BK][LP_BM];
-    __shared__ float Xs[2][LP_BK][LP_BN];
+    __shared__ float Ws[2][DET_BK][DET_BM];
+    __shared__ float Xs[2][DET_BK][DET_BN];
     __shared__ float lut3[U8 ? 3 * 256 : 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const DetRoles t = det_roles();
     if (U8) {
+        const int tid = threadIdx.x;
         const float v = a.lut[tid];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) lut3[c * 256 + tid] = lp_scaled(v, a.shift[c], a.inv[c]);
+        for (int c = 0; c < 3; ++c) lut3[c * 256 + tid] = lp_scaled(v, a.s.shift[c], a.s.inv[c]);
         __syncthreads();
     }
     const int OHW = a.OH * a.OW, M = a.B * OHW;
-    // staging roles: X rows kr0 + 4i (i < 4) of pixel px; W row wr, columns wc..wc+3
-    const int px = tid & 63, kr0 = tid >> 6;
-    const int wr = tid >> 4, wc = (tid & 15) * 4;
-    const int m = (int)blockIdx.x * LP_BN + px;
+    const int m = (int)blockIdx.x * DET_BN + t.px;
     const bool mvalid = m < M;
     int b = 0, oy = 0, ox = 0;
     if (mvalid) {
@@ -72,17 +78,14 @@ __global__ __launch_bounds__(256) void lp_conv1_kernel(const LpConv1Args a) {
     const int iy0 = oy * 4 - 2, ix0 = ox * 4 - 2;
     const long HW = (long)a.H * a.W;
     const long xb = (long)b * 3 * HW;
-    const float* wp = a.wp + wc;
+    const float* wp = a.wp + t.wc;
     const uint8_t* x8 = reinterpret_cast<const uint8_t*>(a.x);
-    const float* xf = reinterpret_cast<const float*>(a.x);
 
-    float xr[4];
-    float4 wreg;
-    auto load = [&](int kt) {
-        wreg = *reinterpret_cast<const float4*>(wp + (long)(kt * LP_BK + wr) * LP_BM);
+    const f32x16 acc = det_conv_tile(Ws, Xs, 0, LP_KT, [&](int kt, float (&xr)[4], float4& wreg) {
+        wreg = *reinterpret_cast<const float4*>(wp + (long)(kt * DET_BK + t.wr) * DET_BM);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int k = kt * LP_BK + kr0 + 4 * i;
+            const int k = kt * DET_BK + t.kr0 + 4 * i;
             xr[i] = 0.f;
             if (mvalid && k < LP_K) {
                 const int tap = k / 3, c = k - tap * 3;
@@ -93,64 +96,25 @@ __global__ __launch_bounds__(256) void lp_conv1_kernel(const LpConv1Args a) {
                     if (U8) {
                         xr[i] = lut3[c * 256 + x8[idx]];
                     } else {
-                        const float u = __fadd_rn(__fmul_rn(xf[idx], a.scale), a.bias);
-                        const float v = __fmul_rn(__fsub_rn(u, 0.5f), 2.f);
-                        const float sh = c == 0 ? a.shift[0] : (c == 1 ? a.shift[1] : a.shift[2]);
-                        const float iv = c == 0 ? a.inv[0] : (c == 1 ? a.inv[1] : a.inv[2]);
-                        xr[i] = lp_scaled(v, sh, iv);
+                        const float u = det_value(a.x, nullptr, a.scale, a.bias, idx);
+                        const float sh = c == 0 ? a.s.shift[0] : (c == 1 ? a.s.shift[1] : a.s.shift[2]);
+                        const float iv = c == 0 ? a.s.inv[0] : (c == 1 ? a.s.inv[1] : a.s.inv[2]);
+                        xr[i] = lp_scaled(__fmul_rn(__fsub_rn(u, 0.5f), 2.f), sh, iv);
                     }
                 }
             }
         }
-    };
+    });
 
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;     // the wave's channel / pixel sub-tile
-    const int lk = lane >> 5, lj = lane & 31;
-    load(0);
-    int buf = 0;
-    for (int kt = 0; kt < LP_KT; ++kt) {
-        *reinterpret_cast<float4*>(&Ws[buf][wr][wc]) = wreg;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) Xs[buf][kr0 + 4 * i][px] = xr[i];
-        __syncthreads();
-        if (kt + 1 < LP_KT) load(kt + 1);                      // next step's loads in flight under this step's MFMAs
-#pragma unroll
-        for (int kk = 0; kk < LP_BK; kk += 2) {
-            const float av = Ws[buf][kk + lk][wm + lj];
-            const float bv = Xs[buf][kk + lk][wn + lj];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-        }
-        buf ^= 1;
-    }
-
-    // D[i][j]: channel i = (r&3) + 8(r>>2) + 4(lane>>5), pixel j = lane&31
-    const int mo = (int)blockIdx.x * LP_BN + wn + lj;
+    const int mo = (int)blockIdx.x * DET_BN + t.wn + t.lj;
     if (mo >= M) return;
-    const int ob = wm + 4 * lk;
     const int bo = mo / OHW, pix = mo - bo * OHW;
-    float* yb = a.y + (long)bo * LP_BM * OHW + pix;
+    float* yb = a.y + (long)bo * DET_BM * OHW + pix;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int o = ob + (r & 3) + 8 * (r >> 2);
+        const int o = t.wm + t.row(r);
         yb[(long)o * OHW] = fmaxf(acc[r] + a.bp[o], 0.f);
     }
-}
-
-// w [64][3][11][11], b [64] -> wp [LP_KP][64] (k = (ky*11 + kx)*3 + c; zero rows beyond K), bp [64]
-__global__ __launch_bounds__(256) void lp_conv1_prep_kernel(const float* w, const float* bias, float* wp, float* bp) {
-    const int e = (int)blockIdx.x * 256 + threadIdx.x;
-    if (e < LP_BM) bp[e] = bias[e];
-    if (e >= LP_KP * LP_BM) return;
-    const int k = e / LP_BM, o = e - k * LP_BM;
-    float v = 0.f;
-    if (k < LP_K) {
-        const int tap = k / 3, c = k - tap * 3;
-        v = w[(o * 3 + c) * 121 + tap];
-    }
-    wp[e] = v;
 }
 
 // one 64-pixel tile of one (pred, gt) pair of maps: the wave's float64 sum of d over its pixels (the same value in every lane)
@@ -218,9 +182,7 @@ __global__ __launch_bounds__(LP_HEAD_THREADS) void lp_head_finish_kernel(const d
 
 extern "C" int shg_lpips_conv1_weight_prep_f32(const float* w, const float* bias, float* wp, float* bp, void* stream) {
     SHG_CHECK_ARG(w && bias && wp && bp, "lpips_conv1_weight_prep: null pointer");
-    hipLaunchKernelGGL(lp_conv1_prep_kernel, dim3(shg_cdiv(LP_KP * LP_BM, 256)), dim3(256), 0, (hipStream_t)stream, w, bias, wp, bp);
-    SHG_CHECK_LAUNCH();
-    return SHG_OK;
+    return shg_det_weight_prep(w, bias, wp, bp, DET_BM, 3, 11, 11, (hipStream_t)stream);      // the detector's packing: [368][64], bp [64]
 }
 
 extern "C" int shg_lpips_conv1_f32(const void* x, const float* lut, float scale, float bias, const float* shift, const float* scaling,
@@ -228,19 +190,16 @@ extern "C" int shg_lpips_conv1_f32(const void* x, const float* lut, float scale,
     SHG_CHECK_ARG(x && shift && scaling && wp && bp && y, "lpips_conv1: null pointer");
     SHG_CHECK_ARG(((uintptr_t)wp & 15) == 0, "lpips_conv1: packed weight not 16-byte aligned");
     SHG_CHECK_ARG(B >= 1 && H >= 7 && W >= 7 && H <= 65536 && W <= 65536, "lpips_conv1: bad geometry B %d %dx%d (B >= 1, H and W >= 7)", B, H, W);
-    SHG_CHECK_ARG(scaling[0] != 0.f && scaling[1] != 0.f && scaling[2] != 0.f, "lpips_conv1: a scaling-layer scale of 0");
     LpConv1Args a;
+    const int rc = lp_scale_make(shift, scaling, "lpips_conv1", &a.s);
+    if (rc) return rc;
     a.x = x; a.lut = lut; a.scale = scale; a.bias = bias; a.wp = wp; a.bp = bp; a.y = y;
-    for (int c = 0; c < 3; ++c) {
-        a.shift[c] = shift[c];
-        a.inv[c] = (float)(1.0 / (double)scaling[c]);
-    }
     a.B = B; a.H = H; a.W = W;
     a.OH = (H + 4 - 11) / 4 + 1;
     a.OW = (W + 4 - 11) / 4 + 1;
     const long M = (long)B * a.OH * a.OW;
-    SHG_CHECK_ARG(M * LP_BM < (1L << 31), "lpips_conv1: tensor too large for 32-bit pixel indices");
-    const dim3 grid((unsigned)((M + LP_BN - 1) / LP_BN));
+    SHG_CHECK_ARG(M * DET_BM < (1L << 31), "lpips_conv1: tensor too large for 32-bit pixel indices");
+    const dim3 grid((unsigned)((M + DET_BN - 1) / DET_BN));
     if (lut) hipLaunchKernelGGL((lp_conv1_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((lp_conv1_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, a);
     SHG_CHECK_LAUNCH();
@@ -298,18 +257,13 @@ extern "C" int shg_lpips_head_pairs_f32(const float* f, const int* ia, const int
 // conv1's load: v = lut[x] or ((x*scale + bias) - 0.5) * 2, then (v - shift_c) * float32(1 / scaling_c).
 namespace {
 template <bool U8>
-__global__ __launch_bounds__(256) void lp_scaling_kernel(const void* x, const float* lut, float scale, float bias, LpConv1Args k, float* y, long n,
+__global__ __launch_bounds__(256) void lp_scaling_kernel(const void* x, const float* lut, float scale, float bias, LpScale k, float* y, long n,
                                                          long HW) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= n) return;
     const int c = (int)((e / HW) % 3);
-    float v;
-    if (U8) {
-        v = lut[reinterpret_cast<const uint8_t*>(x)[e]];
-    } else {
-        const float u = __fadd_rn(__fmul_rn(reinterpret_cast<const float*>(x)[e], scale), bias);
-        v = __fmul_rn(__fsub_rn(u, 0.5f), 2.f);
-    }
+    float v = det_value(x, U8 ? lut : nullptr, scale, bias, e);
+    if (!U8) v = __fmul_rn(__fsub_rn(v, 0.5f), 2.f);
     y[e] = lp_scaled(v, k.shift[c], k.inv[c]);
 }
 }  // namespace
@@ -319,12 +273,9 @@ extern "C" int shg_lpips_scaling_f32(const void* x, const float* lut, float scal
     SHG_CHECK_ARG(x && shift && scaling && y, "lpips_scaling: null pointer");
     SHG_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && H <= 65536 && W <= 65536 && (long)B * 3 * H * W < (1L << 38), "lpips_scaling: bad geometry B %d %dx%d",
                   B, H, W);
-    SHG_CHECK_ARG(scaling[0] != 0.f && scaling[1] != 0.f && scaling[2] != 0.f, "lpips_scaling: a scaling-layer scale of 0");
-    LpConv1Args k = {};
-    for (int c = 0; c < 3; ++c) {
-        k.shift[c] = shift[c];
-        k.inv[c] = (float)(1.0 / (double)scaling[c]);
-    }
+    LpScale k;
+    const int rc = lp_scale_make(shift, scaling, "lpips_scaling", &k);
+    if (rc) return rc;
     const long HW = (long)H * W, n = (long)B * 3 * HW;
     const dim3 grid((unsigned)shg_cdiv(n, 256));
     if (lut) hipLaunchKernelGGL((lp_scaling_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, x, lut, scale, bias, k, y, n, HW);

@@ -2,16 +2,11 @@
 // stylegan_metrics/precision_recall.py:64-76; sh-gan_amd/vgg16.py drives this file).  The 13 convolutions (3 x 3, stride 1, pad 1,
 // ReLU) run on the FID detector's convolution (inception.hip), fc1 / fc2 on shg_dense_f32 (dense.hip: a wave per output feature, the
 // weight row read once per slab of up to 16 images).  This file adds what neither has: the area-resize front end and the 2 x 2 pool.
-#include "shg_common.h"
+#include "det_conv_tile.h"
 
 #define VGG_RES 224      // the network's input side
 
-__device__ __forceinline__ float vgg_fetch(const void* x, const float* lut, float scale, float bias, long i) {
-    if (lut) return lut[reinterpret_cast<const uint8_t*>(x)[i]];
-    return __fadd_rn(__fmul_rn(reinterpret_cast<const float*>(x)[i], scale), bias);
-}
-
-// ---- front end: value map (as the FID detector's: lut[u8], or x*scale + bias rounded twice), `F.interpolate(mode='area')` to
+// ---- front end: value map (det_value, as the FID detector's: lut[u8], or x*scale + bias rounded twice), `F.interpolate(mode='area')` to
 // 224 x 224 = adaptive average pooling over the bins [floor(i*H/224), ceil((i+1)*H/224)) (integer arithmetic: exact for any ratio, up-
 // or down-scaling; a 1 x 1 bin at 224), then (v - mean_c) / std_c.  A bin is summed row by row, left to right, in fp32 and divided by
 // its sample count.
@@ -29,7 +24,7 @@ __global__ __launch_bounds__(256) void vgg_frontend_kernel(const void* x, const 
     const int x0 = (int)((long)ox * W / VGG_RES), x1 = (int)(((long)(ox + 1) * W + VGG_RES - 1) / VGG_RES);
     float s = 0.f;
     for (int iy = y0; iy < y1; ++iy)
-        for (int ix = x0; ix < x1; ++ix) s = __fadd_rn(s, vgg_fetch(x, lut, scale, bias, base + (long)iy * W + ix));
+        for (int ix = x0; ix < x1; ++ix) s = __fadd_rn(s, det_value(x, lut, scale, bias, base + (long)iy * W + ix));
     const float v = __fdiv_rn(s, (float)((y1 - y0) * (x1 - x0)));
     y[e] = __fdiv_rn(__fsub_rn(v, nrm.mean[c]), nrm.stdv[c]);
 }

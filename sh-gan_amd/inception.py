@@ -287,19 +287,9 @@ def frontend(images, input_range='0_255'):
     """images [B,3,H,W] uint8 or float32 -> [B,3,299,299] float32 = (resize(v) - 128) / 128 (one launch)."""
     if input_range not in ('0_255', 'pm1'):
         raise ShgError(f"inception: input_range must be '0_255' or 'pm1' (got {input_range!r})")
-    if not isinstance(images, torch.Tensor) or images.ndim != 4 or images.shape[1] != 3:
-        raise ShgError('inception: images must be a [B,3,H,W] tensor')
     L = kernels._Launch()
-    if images.dtype == torch.uint8:
-        x = L.req(images, 'images', dtype=torch.uint8)
-        lut = L.req(value_table(x.device, input_range), 'lut')
-        scale, bias = 1.0, 0.0
-    elif images.dtype == torch.float32:
-        x = L.req(images, 'images')
-        lut = None
-        scale, bias = (127.5, 127.5) if input_range == 'pm1' else (1.0, 0.0)
-    else:
-        raise ShgError(f'inception: images must be uint8 or float32 (got {images.dtype})')
+    x, lut, scale, bias = kernels._image_operand(L, images, 'images', lambda dev: value_table(dev, input_range),
+                                                 (127.5, 127.5) if input_range == 'pm1' else (1.0, 0.0), 'inception')
     B, _, H, W = x.shape
     y = L.new((B, 3, RES, RES))
     with L:

@@ -87,6 +87,25 @@ def _addr(t):
     return t.data_ptr() if t is not None else None
 
 
+def _c3(v):
+    """Three host floats (per-channel constants: mean, std, shift, scale) as the C entry points take them."""
+    return (ctypes.c_float * 3)(*[float(x) for x in v])
+
+
+def _image_operand(L, images, name, table, scale_bias, who):
+    """The image operand of a detector's first kernel (csrc/det_conv_tile.h: det_value): ``images`` [B,3,H,W], uint8 -- its values come
+    from the 256-entry table ``table(device)`` -- or float32 -- ``x*scale + bias`` with ``scale_bias`` -> (x, lut, scale, bias) for the
+    call ``L``.  ``name`` / ``who``: the operand and the module in the messages."""
+    if not isinstance(images, torch.Tensor) or images.ndim != 4 or images.shape[1] != 3:
+        raise _lib.ShgError(f'{who}: images must be a [B,3,H,W] tensor')
+    if images.dtype == torch.uint8:
+        x = L.req(images, name, dtype=torch.uint8)
+        return x, L.req(table(x.device), 'lut'), 1.0, 0.0
+    if images.dtype == torch.float32:
+        return L.req(images, name), None, scale_bias[0], scale_bias[1]
+    raise _lib.ShgError(f'{who}: {name} must be uint8 or float32 (got {images.dtype})')
+
+
 def _act_args(act, gain=1.0, alpha=0.2, act_gain=SQRT2, clamp=256.0):
     """(act_flag, alpha, total_gain, total_clamp) following common/utils.py:135-143:
     total gain = act_gain*gain; clamp = clamp*gain; without activation the layer does x*gain."""

@@ -124,25 +124,38 @@ def _f32(t):
     return torch.as_tensor(t).detach().cpu().to(torch.float32).contiguous()
 
 
+def _canonical(sd, lin_sd, prefixes, out, lin_after_conv):
+    """The tail both backbones share: the convolutions under ``prefixes``, the five ``lin`` vectors (the one-file layout's ``lins.*``
+    duplicates must agree) and the scaling layer's constants (the one-file layout may carry its own) -> ``out``.  Key order:
+    ``lin{k}`` behind ``conv{k}`` (alex: a tap per convolution) or the five behind all convolutions (vgg), as each layout always had it."""
+    full = lin_sd is None
+    lins = sd if full else lin_sd
+
+    def lin(n):
+        out[f'lin{n}'] = _f32(lins[f'lin{n}.model.1.weight']).reshape(-1)
+        dup = f'lins.{n}.model.1.weight'
+        if full and dup in sd and not torch.equal(_f32(sd[dup]).reshape(-1), out[f'lin{n}']):
+            raise ShgError(f'lpips: {dup!r} differs from its duplicate \'lin{n}.model.1.weight\'')
+    for k, key in enumerate(prefixes):
+        out[f'conv{k}.weight'] = _f32(sd[f'{key}.weight'])
+        out[f'conv{k}.bias'] = _f32(sd[f'{key}.bias'])
+        if lin_after_conv:
+            lin(k)
+    if not lin_after_conv:
+        for n in range(5):
+            lin(n)
+    out['shift'] = _f32(sd['scaling_layer.shift']).reshape(-1) if full and 'scaling_layer.shift' in sd else torch.tensor(SHIFT)
+    out['scale'] = _f32(sd['scaling_layer.scale']).reshape(-1) if full and 'scaling_layer.scale' in sd else torch.tensor(SCALE)
+    return out
+
+
 def canonical_weights(sd, lin_sd=None):
     """Either layout (validated) -> {'conv{k}.weight', 'conv{k}.bias', 'lin{k}' [C], 'shift' [3], 'scale' [3]} float32 on the CPU."""
     if lin_sd is None:
         validate_state_dict(sd)
-        prefixes, lins = PACKAGE_CONV_KEYS, sd
     else:
         validate_state_dicts(sd, lin_sd)
-        prefixes, lins = ALEXNET_CONV_KEYS, lin_sd
-    out = collections.OrderedDict()
-    for k, key in enumerate(prefixes):
-        out[f'conv{k}.weight'] = _f32(sd[f'{key}.weight'])
-        out[f'conv{k}.bias'] = _f32(sd[f'{key}.bias'])
-        out[f'lin{k}'] = _f32(lins[f'lin{k}.model.1.weight']).reshape(-1)
-        dup = f'lins.{k}.model.1.weight'
-        if lin_sd is None and dup in sd and not torch.equal(_f32(sd[dup]).reshape(-1), out[f'lin{k}']):
-            raise ShgError(f'lpips: {dup!r} differs from its duplicate \'lin{k}.model.1.weight\'')
-    out['shift'] = _f32(sd['scaling_layer.shift']).reshape(-1) if lin_sd is None and 'scaling_layer.shift' in sd else torch.tensor(SHIFT)
-    out['scale'] = _f32(sd['scaling_layer.scale']).reshape(-1) if lin_sd is None and 'scaling_layer.scale' in sd else torch.tensor(SCALE)
-    return out
+    return _canonical(sd, lin_sd, PACKAGE_CONV_KEYS if lin_sd is None else ALEXNET_CONV_KEYS, collections.OrderedDict(), True)
 
 
 def _validate_vgg(sd, lins, prefixes, ignored_prefixes, what, lin_what):
@@ -153,14 +166,10 @@ def _validate_vgg(sd, lins, prefixes, ignored_prefixes, what, lin_what):
     for key in conv_keys + (lin_keys if same else []):
         if key not in sd:
             raise ShgError(f'lpips: {what} lacks {key!r}')
-    widths, cin, shapes = [], 3, {}
-    for k in prefixes:
-        w = sd[f'{k}.weight']
-        if w.ndim != 4 or w.shape[0] < 1:
-            raise ShgError(f"lpips: '{k}.weight' has shape {tuple(w.shape)}, expected (O, {cin}, 3, 3)")
-        shapes[f'{k}.weight'], shapes[f'{k}.bias'] = (int(w.shape[0]), cin, 3, 3), (int(w.shape[0]),)
-        cin = int(w.shape[0])
-        widths.append(cin)
+    widths, shapes = [], {}
+    for k, cin, o in vgg16.conv_walk(sd, prefixes, 'lpips'):
+        shapes[f'{k}.weight'], shapes[f'{k}.bias'] = (o, cin, 3, 3), (o,)
+        widths.append(o)
     lin_shapes = {f'lin{n}.model.1.weight': (1, widths[t], 1, 1) for n, t in enumerate(VGG_TAPS)}
     optional = {}
     if same:
@@ -186,21 +195,10 @@ def validate_vgg_state_dicts(vgg_sd, lin_sd):
 def canonical_vgg_weights(sd, lin_sd=None):
     """Either vgg layout (validated) -> {'conv{k}.weight', 'conv{k}.bias' (k < 13), 'lin{n}' [C_n], 'shift', 'scale', 'widths'} on the CPU."""
     if lin_sd is None:
-        widths, prefixes, lins = validate_vgg_state_dict(sd), VGG_PACKAGE_CONV_KEYS, sd
+        widths, prefixes = validate_vgg_state_dict(sd), VGG_PACKAGE_CONV_KEYS
     else:
-        widths, prefixes, lins = validate_vgg_state_dicts(sd, lin_sd), VGG_FEATURES_CONV_KEYS, lin_sd
-    out = collections.OrderedDict(widths=tuple(widths))
-    for k, key in enumerate(prefixes):
-        out[f'conv{k}.weight'] = _f32(sd[f'{key}.weight'])
-        out[f'conv{k}.bias'] = _f32(sd[f'{key}.bias'])
-    for n in range(5):
-        out[f'lin{n}'] = _f32(lins[f'lin{n}.model.1.weight']).reshape(-1)
-        dup = f'lins.{n}.model.1.weight'
-        if lin_sd is None and dup in sd and not torch.equal(_f32(sd[dup]).reshape(-1), out[f'lin{n}']):
-            raise ShgError(f'lpips: {dup!r} differs from its duplicate \'lin{n}.model.1.weight\'')
-    out['shift'] = _f32(sd['scaling_layer.shift']).reshape(-1) if lin_sd is None and 'scaling_layer.shift' in sd else torch.tensor(SHIFT)
-    out['scale'] = _f32(sd['scaling_layer.scale']).reshape(-1) if lin_sd is None and 'scaling_layer.scale' in sd else torch.tensor(SCALE)
-    return out
+        widths, prefixes = validate_vgg_state_dicts(sd, lin_sd), VGG_FEATURES_CONV_KEYS
+    return _canonical(sd, lin_sd, prefixes, collections.OrderedDict(widths=tuple(widths)), False)
 
 
 def vgg_out_sizes(h):
@@ -242,12 +240,17 @@ def value_table(device, operand, gt_range='pm1'):
     return _LUTS[key]
 
 
-def _c3(v):
-    return (ctypes.c_float * 3)(*[float(x) for x in v])
+def _operand(L, images, operand, gt_range):
+    """The operand half of ``conv1`` and ``scaling``: the forms of ``Lpips.__call__`` -> (x, lut, scale, bias) for the call ``L``."""
+    if operand not in ('pred', 'gt') or gt_range not in ('pm1', 'unit'):
+        raise ShgError(f"lpips: operand must be 'pred' or 'gt' and gt_range 'pm1' or 'unit' (got {operand!r}, {gt_range!r})")
+    return kernels._image_operand(L, images, operand, lambda dev: value_table(dev, operand, gt_range),
+                                  (0.5, 0.5) if (operand == 'gt' and gt_range == 'pm1') else (1.0, 0.0), 'lpips')
 
 
 def pack_conv1(w, b):
-    """float32 w [64,3,11,11], b [64] on the device -> (wp [368*64], bp [64]) in shg_lpips_conv1_f32's operand layout."""
+    """float32 w [64,3,11,11], b [64] on the device -> (wp [368*64], bp [64]) in shg_lpips_conv1_f32's operand layout: that of
+    ``inception.pack_weight``, whose entry point stops at the 7 x 7 kernels its convolution serves."""
     L = kernels._Launch()
     w, b = L.req(w, 'w'), L.req(b, 'bias')
     if tuple(w.shape) != (64, 3, 11, 11) or tuple(b.shape) != (64,):
@@ -262,20 +265,8 @@ def pack_conv1(w, b):
 def conv1(images, wp, bp, operand='pred', gt_range='pm1', shift=SHIFT, scale=SCALE, y=None):
     """images [B,3,H,W] (uint8 or float32, forms of ``Lpips.__call__``) -> relu(conv1(scaling_layer(value))) [B,64,OH,OW] (one launch);
     ``y``: a contiguous float32 [B,64,OH,OW] view to write into."""
-    if operand not in ('pred', 'gt') or gt_range not in ('pm1', 'unit'):
-        raise ShgError(f"lpips: operand must be 'pred' or 'gt' and gt_range 'pm1' or 'unit' (got {operand!r}, {gt_range!r})")
-    if not isinstance(images, torch.Tensor) or images.ndim != 4 or images.shape[1] != 3:
-        raise ShgError('lpips: images must be a [B,3,H,W] tensor')
     L = kernels._Launch()
-    if images.dtype == torch.uint8:
-        x = L.req(images, operand, dtype=torch.uint8)
-        lut = L.req(value_table(x.device, operand, gt_range), 'lut')
-        s, b = 1.0, 0.0
-    elif images.dtype == torch.float32:
-        x, lut = L.req(images, operand), None
-        s, b = (0.5, 0.5) if (operand == 'gt' and gt_range == 'pm1') else (1.0, 0.0)
-    else:
-        raise ShgError(f'lpips: {operand} must be uint8 or float32 (got {images.dtype})')
+    x, lut, s, b = _operand(L, images, operand, gt_range)
     wp, bp = L.req(wp, 'wp'), L.req(bp, 'bp')
     B, _, H, W = x.shape
     if H < 7 or W < 7:
@@ -287,28 +278,16 @@ def conv1(images, wp, bp, operand='pred', gt_range='pm1', shift=SHIFT, scale=SCA
     if tuple(y.shape) != (B, 64, OH, OW) or not y.is_contiguous() or y.dtype != torch.float32 or not y.is_cuda:
         raise ShgError(f'lpips: conv1 output {tuple(y.shape)} does not fit input {tuple(x.shape)}')
     with L:
-        check(_lib.get_lib().shg_lpips_conv1_f32(kernels._ptr(x), kernels._ptr(lut), s, b, _c3(shift), _c3(scale), kernels._ptr(wp), kernels._ptr(bp),
-                                                 kernels._ptr(y), B, H, W, L.stream()), 'lpips_conv1')
+        check(_lib.get_lib().shg_lpips_conv1_f32(kernels._ptr(x), kernels._ptr(lut), s, b, kernels._c3(shift), kernels._c3(scale),
+                                                 kernels._ptr(wp), kernels._ptr(bp), kernels._ptr(y), B, H, W, L.stream()), 'lpips_conv1')
     return y
 
 
 def scaling(images, operand='pred', gt_range='pm1', shift=SHIFT, scale=SCALE, y=None):
     """images [B,3,H,W] (uint8 or float32, forms of ``Lpips.__call__``) -> scaling_layer(value) [B,3,H,W] float32, the float32 steps of
     conv1's load (one launch); ``y``: a contiguous float32 [B,3,H,W] view to write into."""
-    if operand not in ('pred', 'gt') or gt_range not in ('pm1', 'unit'):
-        raise ShgError(f"lpips: operand must be 'pred' or 'gt' and gt_range 'pm1' or 'unit' (got {operand!r}, {gt_range!r})")
-    if not isinstance(images, torch.Tensor) or images.ndim != 4 or images.shape[1] != 3:
-        raise ShgError('lpips: images must be a [B,3,H,W] tensor')
     L = kernels._Launch()
-    if images.dtype == torch.uint8:
-        x = L.req(images, operand, dtype=torch.uint8)
-        lut = L.req(value_table(x.device, operand, gt_range), 'lut')
-        s, b = 1.0, 0.0
-    elif images.dtype == torch.float32:
-        x, lut = L.req(images, operand), None
-        s, b = (0.5, 0.5) if (operand == 'gt' and gt_range == 'pm1') else (1.0, 0.0)
-    else:
-        raise ShgError(f'lpips: {operand} must be uint8 or float32 (got {images.dtype})')
+    x, lut, s, b = _operand(L, images, operand, gt_range)
     if y is None:
         y = L.new(tuple(x.shape))
     L.view(y, 'y')
@@ -316,8 +295,8 @@ def scaling(images, operand='pred', gt_range='pm1', shift=SHIFT, scale=SCALE, y=
         raise ShgError(f'lpips: scaling output {tuple(y.shape)} does not fit input {tuple(x.shape)}')
     B, _, H, W = x.shape
     with L:
-        check(_lib.get_lib().shg_lpips_scaling_f32(kernels._ptr(x), kernels._ptr(lut), s, b, _c3(shift), _c3(scale), kernels._ptr(y), B, H, W,
-                                                   L.stream()), 'lpips_scaling')
+        check(_lib.get_lib().shg_lpips_scaling_f32(kernels._ptr(x), kernels._ptr(lut), s, b, kernels._c3(shift), kernels._c3(scale),
+                                                   kernels._ptr(y), B, H, W, L.stream()), 'lpips_scaling')
     return y
 
 
@@ -410,14 +389,7 @@ class Lpips:
         if len(mean) != 3 or len(std) != 3 or min(float(v) for v in std) <= 0:
             raise ShgError(f'lpips: mean and std must be three numbers each, std positive (got {mean!r}, {std!r})')
         dev = torch.device(device)
-        ops, cin = [], 3
-        for k, c in enumerate(cw['widths']):
-            w = cw[f'conv{k}.weight']
-            if k == 0 and bgr:           # the net reads BGR planes: RGB images with the flipped weight are the same sum (as vgg16.py)
-                w = w.flip(1).contiguous()
-            wp, bp = inception.pack_weight(w.to(dev), cw[f'conv{k}.bias'].to(dev))
-            ops.append(inception.ConvOp(f'vgg.conv{k}', wp, bp, cin, c, (3, 3), (1, 1), (1, 1)))
-            cin = c
+        ops = vgg16.conv_ops([(f'vgg.conv{k}', cw[f'conv{k}.weight'], cw[f'conv{k}.bias']) for k in range(len(cw['widths']))], dev, bgr)
         lins = [cw[f'lin{n}'].to(dev) for n in range(5)]
         consts = [cw['shift'].tolist(), cw['scale'].tolist(), tuple(mean), tuple(std)]
         if bgr:
@@ -448,16 +420,7 @@ class Lpips:
         taps [N,C,h,w].  No launch plan depends on N."""
         if self.net != 'vgg':
             raise ShgError("lpips: trunk() is the net='vgg' backbone")
-        taps = []
-        for k, op in enumerate(self.ops):
-            y = torch.empty((x.shape[0], op.O) + tuple(x.shape[2:]), dtype=torch.float32, device=self.device)
-            inception.conv_group([(op, x, 0, y, 0)], split_k=False)
-            x = y
-            if k in VGG_TAPS:
-                taps.append(y)
-                if k != VGG_TAPS[-1]:
-                    x = vgg16.maxpool2(y)
-        return taps
+        return vgg16.conv_trunk(self.ops, x, taps=VGG_TAPS)
 
     def features(self, pred, gt, gt_range='pm1'):
         """-> the five taps, each [2B,C,h,w] float32: the preds' features in [:B], the gts' in [B:].  ``gt=None``: the preds alone, [B,C,h,w]."""

@@ -30,7 +30,6 @@ distances at the end (``evaluators.Collective``) instead of a broadcast per batc
 reference's order (batch-major, then rank) and cut to ``num_samples``.  Every rank returns the value (the reference returns NaN on ranks
 other than 0).  ``trimmed_mean`` is the tail :124-127 on the device."""
 import copy
-import ctypes
 
 import torch
 
@@ -40,10 +39,6 @@ from ._lib import ShgError, check
 INPAINTER_REASON = ('the path length walks the latent space of a generator with the image free to change everywhere; a co-modulated '
                     'inpainter (shgan_*, comodgan_*) is conditioned on the known pixels, which a latent step does not move, so the path '
                     'length says nothing about it')
-
-
-def _c3(v):
-    return (ctypes.c_float * 3)(*[float(x) for x in v])
 
 
 def frontend_side(C, H, W, factor, crop):
@@ -73,8 +68,8 @@ def frontend(images, factor, crop=False, mean=(123.68, 116.779, 103.939), std=(1
         if not y.is_contiguous() or (S is not None and tuple(y.shape) != (N, 3, S, S)):
             raise ShgError(f'ppl: y must be a contiguous float32 {(N, 3, S, S)} tensor (got {tuple(y.shape)})')
     with L:
-        check(_lib.get_lib().shg_ppl_frontend_f32(kernels._ptr(x), kernels._ptr(y), N, C, H, W, int(factor), int(bool(crop)), _c3(mean), _c3(std),
-                                                  L.stream()), 'ppl_frontend')
+        check(_lib.get_lib().shg_ppl_frontend_f32(kernels._ptr(x), kernels._ptr(y), N, C, H, W, int(factor), int(bool(crop)), kernels._c3(mean),
+                                                  kernels._c3(std), L.stream()), 'ppl_frontend')
     return y
 
 

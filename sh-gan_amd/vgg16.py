@@ -25,9 +25,6 @@ channel order and taking the features after fc2's ReLU follow the published desc
 ``std`` and ``bgr`` are constructor options.  ``bgr=True`` flips the input-channel axis of the first convolution's weights at load time (and
 the mean / std with it); the image is not touched.  A torchvision ImageNet file needs ``mean = 255 * (0.485, 0.456, 0.406)``,
 ``std = 255 * (0.229, 0.224, 0.225)``."""
-import collections
-import ctypes
-
 import torch
 
 from . import _lib, inception, kernels
@@ -46,6 +43,46 @@ def area_bins(size, out=RES):
     return [(i * size // out, -(-(i + 1) * size // out)) for i in range(out)]
 
 
+def conv_walk(sd, prefixes, who):
+    """The width walk over a state dict's 3 x 3 convolutions ``{prefix}.weight`` (keys present): yields (prefix, input width, output width)
+    per convolution, the input width being the previous output's (3 at first).  Raises ShgError (``who``: the module in the message) at a
+    weight that is no 4-D tensor with at least one output channel."""
+    cin = 3
+    for k in prefixes:
+        w = sd[f'{k}.weight']
+        if w.ndim != 4 or w.shape[0] < 1:
+            raise ShgError(f"{who}: '{k}.weight' has shape {tuple(w.shape)}, expected (O, {cin}, 3, 3)")
+        yield k, cin, int(w.shape[0])
+        cin = int(w.shape[0])
+
+
+def conv_ops(named_wb, device, bgr=False):
+    """[(name, w [O,I,3,3], b [O])] float32 on the CPU, in network order (shapes validated) -> the backbone's ``inception.ConvOp`` list on
+    ``device``.  ``bgr``: the net was trained on BGR planes, its input channel 0 is blue -- reading RGB images with the first weight's
+    input-channel axis flipped is the same sum (the caller flips the per-channel constants, given in the net's own order, with it)."""
+    ops = []
+    for k, (name, w, b) in enumerate(named_wb):
+        if k == 0 and bgr:
+            w = w.flip(1).contiguous()
+        wp, bp = inception.pack_weight(w.to(device), b.to(device))
+        ops.append(inception.ConvOp(name, wp, bp, int(w.shape[1]), int(w.shape[0]), (3, 3), (1, 1), (1, 1)))
+    return ops
+
+
+def conv_trunk(ops, x, taps=None):
+    """The backbone: x [N,3,H,W] float32, a finished network input -> the thirteen convolutions + ReLU (``split_k=False``: no launch plan
+    depends on N) with a 2 x 2 max pool after those of POOL_AFTER.  ``taps=None``: the last pool's output.  ``taps``: indices into ``ops``
+    -> the list of those convolutions' outputs (before the pool); a pool after the last convolution is then not run."""
+    out = []
+    for k, op in enumerate(ops):
+        y = torch.empty((x.shape[0], op.O) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+        inception.conv_group([(op, x, 0, y, 0)], split_k=False)
+        if taps is not None and k in taps:
+            out.append(y)
+        x = maxpool2(y) if k in POOL_AFTER and (taps is None or k + 1 < len(ops)) else y
+    return x if taps is None else out
+
+
 def validate_state_dict(sd):
     """Raises ShgError naming the first missing key, unexpected key or wrong shape; -> (channel widths of the 13 convolutions, F1, F)."""
     keys = [f'features.{i}.{p}' for i in CONV_IDS for p in ('weight', 'bias')] + [f'{k}.{p}' for k in FC_KEYS for p in ('weight', 'bias')]
@@ -59,15 +96,12 @@ def validate_state_dict(sd):
     def expect(key, shape):
         if tuple(sd[key].shape) != tuple(shape):
             raise ShgError(f'vgg16: {key!r} has shape {tuple(sd[key].shape)}, expected {tuple(shape)}')
-    widths, cin = [], 3
-    for i in CONV_IDS:
-        w = sd[f'features.{i}.weight']
-        if w.ndim != 4 or w.shape[0] < 1:
-            raise ShgError(f'vgg16: \'features.{i}.weight\' has shape {tuple(w.shape)}, expected (O, {cin}, 3, 3)')
-        expect(f'features.{i}.weight', (w.shape[0], cin, 3, 3))
-        expect(f'features.{i}.bias', (w.shape[0],))
-        cin = int(w.shape[0])
-        widths.append(cin)
+    widths = []
+    for key, cin, o in conv_walk(sd, [f'features.{i}' for i in CONV_IDS], 'vgg16'):
+        expect(f'{key}.weight', (o, cin, 3, 3))
+        expect(f'{key}.bias', (o,))
+        widths.append(o)
+    cin = widths[-1]
     w1, w2 = sd['classifier.0.weight'], sd['classifier.3.weight']
     if w1.ndim != 2 or w1.shape[0] < 1:
         raise ShgError(f'vgg16: \'classifier.0.weight\' has shape {tuple(w1.shape)}, expected (F1, {cin * 49})')
@@ -80,32 +114,19 @@ def validate_state_dict(sd):
     return widths, int(w1.shape[0]), int(w2.shape[0])
 
 
-def _c3(v):
-    return (ctypes.c_float * 3)(*[float(x) for x in v])
-
-
 def frontend(images, input_range=None, mean=CAFFE_MEAN, std=(1.0, 1.0, 1.0)):
     """images [B,3,H,W] uint8 or float32 -> [B,3,224,224] float32 = (area_resize(v) - mean_c) / std_c (one launch)."""
     input_range = '0_255' if input_range is None else input_range
     if input_range not in ('0_255', 'pm1'):
         raise ShgError(f"vgg16: input_range must be None, '0_255' or 'pm1' (got {input_range!r})")
-    if not isinstance(images, torch.Tensor) or images.ndim != 4 or images.shape[1] != 3:
-        raise ShgError('vgg16: images must be a [B,3,H,W] tensor')
     L = kernels._Launch()
-    if images.dtype == torch.uint8:
-        x = L.req(images, 'images', dtype=torch.uint8)
-        lut = L.req(inception.value_table(x.device, input_range), 'lut')
-        scale, bias = 1.0, 0.0
-    elif images.dtype == torch.float32:
-        x, lut = L.req(images, 'images'), None
-        scale, bias = (127.5, 127.5) if input_range == 'pm1' else (1.0, 0.0)
-    else:
-        raise ShgError(f'vgg16: images must be uint8 or float32 (got {images.dtype})')
+    x, lut, scale, bias = kernels._image_operand(L, images, 'images', lambda dev: inception.value_table(dev, input_range),
+                                                 (127.5, 127.5) if input_range == 'pm1' else (1.0, 0.0), 'vgg16')
     B, _, H, W = x.shape
     y = L.new((B, 3, RES, RES))
     with L:
-        check(_lib.get_lib().shg_vgg16_frontend_f32(kernels._ptr(x), kernels._ptr(lut), scale, bias, _c3(mean), _c3(std), kernels._ptr(y), B, H, W,
-                                                    L.stream()), 'vgg16_frontend')
+        check(_lib.get_lib().shg_vgg16_frontend_f32(kernels._ptr(x), kernels._ptr(lut), scale, bias, kernels._c3(mean), kernels._c3(std),
+                                                    kernels._ptr(y), B, H, W, L.stream()), 'vgg16_frontend')
     return y
 
 
@@ -164,16 +185,7 @@ class Vgg16Features:
             raise ShgError(f'vgg16: mean and std must be three numbers each, std positive (got {mean!r}, {std!r})')
         dev = torch.device(device)
         f32 = lambda t: torch.as_tensor(t).detach().cpu().to(torch.float32).contiguous()      # noqa: E731
-        ops, cin = [], 3
-        for k, (i, c) in enumerate(zip(CONV_IDS, widths)):
-            w = f32(sd[f'features.{i}.weight'])
-            if k == 0 and bgr:
-                # the net was trained on BGR planes: its input channel 0 is blue.  Reading RGB images with the flipped weight is the
-                # same sum; the per-channel mean / std (given in the net's own order) are flipped with it
-                w = w.flip(1).contiguous()
-            wp, bp = inception.pack_weight(w.to(dev), f32(sd[f'features.{i}.bias']).to(dev))
-            ops.append(inception.ConvOp(f'features.{i}', wp, bp, cin, c, (3, 3), (1, 1), (1, 1)))
-            cin = c
+        ops = conv_ops([(f'features.{i}', f32(sd[f'features.{i}.weight']), f32(sd[f'features.{i}.bias'])) for i in CONV_IDS], dev, bgr)
         fcs = [(f32(sd[f'{k}.weight']).to(dev), f32(sd[f'{k}.bias']).to(dev)) for k in FC_KEYS]
         if bgr:
             mean, std = tuple(mean)[::-1], tuple(std)[::-1]
@@ -181,12 +193,7 @@ class Vgg16Features:
 
     def trunk(self, x):
         """x [B,3,224,224] normalised -> [B, F]."""
-        B = x.shape[0]
-        for k, op in enumerate(self.ops):
-            y = torch.empty((B, op.O) + tuple(x.shape[2:]), dtype=torch.float32, device=self.device)
-            inception.conv_group([(op, x, 0, y, 0)], split_k=False)
-            x = maxpool2(y) if k in POOL_AFTER else y
-        x = x.reshape(B, -1)
+        x = conv_trunk(self.ops, x).reshape(x.shape[0], -1)
         for w, b in self.fcs:
             x = fc_relu(x, w, b)
         return x

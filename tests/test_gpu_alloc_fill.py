@@ -1349,7 +1349,6 @@ SITES = {
     ('lpips.py', 'head'): ['lpips:distance', 'lpips:vgg_distance'],
     ('lpips.py', 'pack_conv1'): ['lpips:distance'],
     ('lpips.py', 'scaling'): ['lpips:vgg_distance'],
-    ('lpips.py', 'trunk'): ['lpips:vgg_distance'],
     ('masks.py', 'lama_rasterize'): ['masks:lama'],
     ('masks.py', 'rasterize'): ['harness:eval_loop', 'masks:freeform'],
     ('model_zoo/comodgan.py', '_all_styles'): ['harness:eval_loop', 'module:generator_fp32', 'module:loss_Dmain'],
@@ -1361,10 +1360,10 @@ SITES = {
     ('resize.py', 'pack_images'): ['input:randcrop', 'input:resize'],
     ('resize.py', 'randcrop_bicubic'): ['input:randcrop'],
     ('resize.py', '_launch_resize'): ['input:resize'],
+    ('vgg16.py', 'conv_trunk'): ['lpips:vgg_distance', 'vgg16:frontend_pool_detector'],
     ('vgg16.py', 'fc_relu'): ['vgg16:frontend_pool_detector'],
     ('vgg16.py', 'frontend'): ['vgg16:frontend_pool_detector'],
     ('vgg16.py', 'maxpool2'): ['lpips:vgg_distance', 'vgg16:frontend_pool_detector'],
-    ('vgg16.py', 'trunk'): ['vgg16:frontend_pool_detector'],
 }
 
 # (file, function) -> why the fill has nothing to say about the site

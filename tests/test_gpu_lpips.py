@@ -66,6 +66,34 @@ def test_conv1_against_float64(sd, net, size):
         assert err <= 1e-5, (size, operand, rng, img.dtype, err)
 
 
+def test_conv1_weight_prep_gives_the_detectors_packing():
+    """shg_lpips_conv1_weight_prep_f32 on a seeded [64,3,11,11] weight against ``inception.pack_weight``: both outputs, bit for bit.
+    ``shg_inception_weight_prep_f32`` refuses kernels beyond 7 x 7 (tests/test_inception_cpu.py pins that refusal), so ``pack_weight`` cannot
+    be handed the 11 x 11 weight itself; it packs the same 363 columns as a 1 x 1 convolution over 363 channels laid out in the packing's
+    own K order, k = (ky*11 + kx)*3 + c -- for a 1 x 1 kernel the detector's k IS the channel index, so the two [368][64] tables and the
+    two [64] biases must agree element for element.  ``lpips.pack_conv1`` is that entry point and is held to the same bits."""
+    import ctypes
+    from shgan_amd import _lib, inception, kernels, lpips
+    g = torch.Generator().manual_seed(363)
+    w, b = torch.randn(64, 3, 11, 11, generator=g).to(DEV), torch.randn(64, generator=g).to(DEV)
+    wp, bp = torch.full((368 * 64,), float('nan'), device=DEV), torch.full((64,), float('nan'), device=DEV)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
+    _lib.check(_lib.get_lib().shg_lpips_conv1_weight_prep_f32(kernels._ptr(w), kernels._ptr(b), kernels._ptr(wp), kernels._ptr(bp), stream),
+               'lpips_conv1_weight_prep')
+    with pytest.raises(_lib.ShgError, match='bad shape'):
+        inception.pack_weight(w, b)
+    want_wp, want_bp = inception.pack_weight(w.permute(0, 2, 3, 1).reshape(64, 363, 1, 1).contiguous(), b)
+    assert want_wp.shape == wp.shape and want_bp.shape == bp.shape
+    assert torch.equal(wp, want_wp) and torch.equal(bp, want_bp)
+    # and a table built on the host, which shares no kernel with either side: rows k = (ky*11 + kx)*3 + c, columns o, zero rows to 368
+    host = torch.zeros(368, 64)
+    host[:363] = w.cpu().permute(2, 3, 1, 0).reshape(363, 64)
+    assert torch.equal(wp.cpu().reshape(368, 64), host) and torch.equal(bp.cpu(), b.cpu())
+    assert float(wp.reshape(368, 64)[363:].abs().max()) == 0 and bool((wp.reshape(368, 64)[:363] != 0).all())
+    again = lpips.pack_conv1(w, b)
+    assert torch.equal(again[0], want_wp) and torch.equal(again[1], want_bp)
+
+
 @pytest.mark.parametrize('B', [1, 3])
 @pytest.mark.parametrize('res', [256, 512])
 def test_head_against_float64(res, B):

@@ -55,7 +55,7 @@ def manifold_mode(a):
 
 
 def detector_mode(a):
-    from shgan_amd import inception, vgg16
+    from shgan_amd import vgg16
     import pr_f64
     dev = 'cuda:0'
     det = vgg16.Vgg16Features.from_state_dict(pr_f64.random_state_dict(0, div=1, fc=4096), device=dev)
@@ -70,12 +70,7 @@ def detector_mode(a):
         flat = torch.rand(b, det.fcs[0][0].shape[1], device=dev)
 
         def convs():
-            y = x
-            for k, op in enumerate(det.ops):
-                t = torch.empty((b, op.O) + tuple(y.shape[2:]), dtype=torch.float32, device=dev)
-                inception.conv_group([(op, y, 0, t, 0)], split_k=False)
-                y = vgg16.maxpool2(t) if k in vgg16.POOL_AFTER else t
-            return y
+            return vgg16.conv_trunk(det.ops, x)
 
         def fcs():
             y = flat
