@@ -543,6 +543,30 @@ int shg_adam_tick(const long* table, int nseg, const double* hyper, int ngroups,
 int shg_adam_buckets_f32(const long* table, int nseg, long chunks, const float* scalars, float world, int div_mode, int sanitize, void* stream);
 int shg_ema_lerp_f32(const long* table, int nseg, long chunks, const float* beta, void* stream);
 
+/* ---- what a training run keeps beside the step (sh-gan_amd/training_stats.py, optim.py, train_stage.py; csrc/train_stats.hip and the
+ * health form of the Adam pass in csrc/optim.hip).  No atomics, no host read; every reduction has a shape fixed by its data (lane-strided
+ * partial sums, a tree over the wave, a tree over the four waves), so equal inputs give equal bits.
+ * Moments: table int64 [rows + 1][SHG_STATS_ROW] on the device, row = {address of a contiguous float32 tensor (4-byte aligned), numel >= 1,
+ *   slot in [0, slots), 0}, the last row a sentinel; acc float64 [slots][4] += {count, sum, sum of squares} of the finite elements (each
+ *   widened to float64 before it is squared) and {non-finite count}.  One workgroup per slot walks that slot's rows in table order.
+ *   rows = 0 launches nothing.  The table is checked on the host (training_stats.validate_stats_table) and trusted here.
+ * Adam with health: shg_adam_buckets_f32's pass (same table, same bits in param, exp_avg, exp_avg_sq and grad), which also writes
+ *   workspace float64 [chunks][SHG_HEALTH_COLS] for the chunks of touched segments: {sum g^2 of the averaged, sanitised gradient, elements the
+ *   sanitisation replaced (0 with sanitize off), max |g|, sum p_old^2, sum (p_old - p_new)^2 with the difference taken in float32}.
+ * Reduce: one workgroup per segment folds its chunk rows into health float64 [nseg + 1][SHG_HEALTH_COLS] (sums added, the maximum kept), one
+ *   more folds every touched chunk into row nseg and adds 1 to steps[0]; untouched segments are left alone.
+ * Grid: x [gw * gh, C, H, W] float32, C 1 or 3 -> out uint8 [gh * H, gw * W, C], image n at row n / gw, column n % gw;
+ *   value = (uint8) clip(rint((x - lo) * scale), 0, 255), subtract and multiply rounded one by one in float32, rint to even, NaN -> 0; with
+ *   real [like x] and mask [gw * gh, 1, H, W] (both or neither) x is first replaced by real * mask + x * (1 - mask), each operation rounded. */
+#define SHG_STATS_ROW 4
+#define SHG_HEALTH_COLS 5
+int shg_stats_moments_f64(const long* table, int rows, double* acc, int slots, void* stream);
+int shg_adam_buckets_health_f32(const long* table, int nseg, long chunks, const float* scalars, float world, int div_mode, int sanitize,
+                                double* workspace, void* stream);
+int shg_health_reduce_f64(const long* table, int nseg, long chunks, const double* workspace, double* health, double* steps, void* stream);
+int shg_image_grid_u8(const float* x, const float* real, const float* mask, uint8_t* out, int C, int H, int W, int gw, int gh, float lo,
+                      float scale, void* stream);
+
 /* ---- evaluation image metrics (lib/evaluator/eva_psnr.py, for_dataset=None, rgb_range=1; eva_ssim._ssim, size_average=False).
  * pred, gt [B,C,H,W] contiguous; each operand is uint8 when its lut [256] (value of every code: float64 for pred, float32 for gt) is
  * given, float32 otherwise; the element value is then v*scale + bias (the evaluator's fake/255 and (real+1)/2).  As in the reference's

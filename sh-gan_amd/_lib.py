@@ -169,6 +169,10 @@ _SIGS = {
     'shg_adam_tick': [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp],
     'shg_adam_buckets_f32': [c_fp, c_i, c_l, c_fp, c_f, c_i, c_i, c_fp],
     'shg_ema_lerp_f32': [c_fp, c_i, c_l, c_fp, c_fp],
+    'shg_stats_moments_f64': [c_fp, c_i, c_fp, c_i, c_fp],
+    'shg_adam_buckets_health_f32': [c_fp, c_i, c_l, c_fp, c_f, c_i, c_i, c_fp, c_fp],
+    'shg_health_reduce_f64': [c_fp, c_i, c_l, c_fp, c_fp, c_fp, c_fp],
+    'shg_image_grid_u8': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_fp],
     'shg_image_metrics_scratch_bytes': [c_i] * 4,
     'shg_image_metrics': [c_fp, c_fp, c_f, c_f, c_fp, c_fp, c_f, c_f] + [c_i] * 6 + [c_fp, ctypes.c_size_t, c_fp, c_fp, c_fp],
     'shg_resize_bicubic_u8': [c_fp, c_l, c_fp, c_l, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],

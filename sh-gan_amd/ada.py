@@ -277,6 +277,16 @@ class AdaController:
         self.iters = 0
         self.last_mean = None
 
+    def state_dict(self):
+        """What a resumed run needs to continue the heuristic where it stood (``pipe.p`` is a buffer of the pipe and travels with it)."""
+        return {'acc': None if self.acc is None else self.acc.detach().clone(), 'iters': int(self.iters), 'last_mean': self.last_mean}
+
+    def load_state_dict(self, state):
+        acc = state['acc']
+        self.acc = None if acc is None else acc.detach().clone().to(self.pipe.p.device)
+        self.iters = int(state['iters'])
+        self.last_mean = state['last_mean']
+
     @torch.no_grad()
     def update(self, signs, batch_size):
         """-> the adjustment applied to p at this call (0.0 between intervals)."""

@@ -28,6 +28,7 @@ class Loss:
     that call and before no other -- the buckets then all-reduce under that backward pass.  Without it the gradients are still reduced
     (synchronously, in ``finish()``) and the stage says so once."""
     grad_sync = None
+    collector = None
 
     def accumulate_gradients(self, phase, real_img, real_c, gen_z, gen_c, sync, gain):
         raise NotImplementedError()
@@ -35,8 +36,9 @@ class Loss:
 
 class StyleGAN2Loss(Loss):
     def __init__(self, device, G_mapping, G_synthesis, D, augment_pipe=None, style_mixing_prob=0.9, r1_gamma=10, pl_batch_shrink=2,
-                 pl_decay=0.01, pl_weight=2, batch_critic=True):
+                 pl_decay=0.01, pl_weight=2, batch_critic=True, collector=None):
         super().__init__()
+        self.collector = collector                  # a training_stats.Collector (None: the statistics stay in self.stats only)
         self.batch_critic = batch_critic            # Dmain: generated and real images through the critic as ONE batch (see accumulate_gradients)
         if augment_pipe is not None and not isinstance(augment_pipe, AugmentPipe):
             raise NotImplementedError('ADA augmentation is not part of the HIP path unless augment_pipe is an ada.AugmentPipe')
@@ -86,8 +88,25 @@ class StyleGAN2Loss(Loss):
         logits = self.D(self._augment(torch.cat([gen_img, real_img])), torch.cat([gen_c, real_c]), segments=2)
         return logits[:gen_img.shape[0]], logits[gen_img.shape[0]:]
 
+    # -- state of a run (train_stage.save_snapshot) --------------------------------------------------------------------------
+    def state_dict(self):
+        return {'pl_mean': self.pl_mean.detach().clone()}
+
+    def load_state_dict(self, state):
+        with torch.no_grad():
+            self.pl_mean.copy_(state['pl_mean'].to(self.pl_mean.device, self.pl_mean.dtype))
+
     # -- one phase (stylegan_default_loss.py:53-128) -----------------------------------------------------------------------
     def accumulate_gradients(self, phase, real_img, real_c, gen_z, gen_c, sync=True, gain=1):
+        """With a collector the call ends with ONE ``report_many`` of the statistics this call wrote to ``self.stats`` (the entries whose
+        tensor is new), under the same names; ``self.stats`` itself is what it is without one."""
+        if self.collector is None:
+            return self._accumulate(phase, real_img, real_c, gen_z, gen_c, sync, gain)
+        before = dict(self.stats)
+        self._accumulate(phase, real_img, real_c, gen_z, gen_c, sync, gain)
+        self.collector.report_many({k: v for k, v in self.stats.items() if before.get(k) is not v})
+
+    def _accumulate(self, phase, real_img, real_c, gen_z, gen_c, sync=True, gain=1):
         if phase not in PHASES:
             raise AssertionError(f'unknown phase {phase!r}')
         do_Gmain = phase in ('Gmain', 'Gboth')

@@ -25,6 +25,7 @@ EMA_ROW = 6           # {dst, src, words, kind, 0, first chunk}
 ADAM_SCALARS = 8
 EMA_LERP, EMA_COPY = 0, 1
 DIV_NONE, DIV_RECIPROCAL, DIV_TRUE = 0, 1, 2
+HEALTH_COLS = 5       # csrc/optim.hip HEALTH_COLS: {sum g^2, elements the sanitisation replaced, max |g|, sum p_old^2, sum (p_old - p_new)^2}
 
 
 def _chunk_prefix(numels):
@@ -138,12 +139,16 @@ class ShgAdam(torch.optim.Optimizer):
     this one's state): the step counter is on the device either way.
     ``lr`` / ``betas`` / ``eps`` of a group may be changed between eager steps (the device block is refreshed at the next step); a
     captured step replays with the values it was captured with, like torch's capturable Adam.
-    ``state_dict()`` / ``load_state_dict()`` use ``torch.optim.Adam``'s layout (per-parameter ``step``, ``exp_avg``, ``exp_avg_sq``)."""
+    ``state_dict()`` / ``load_state_dict()`` use ``torch.optim.Adam``'s layout (per-parameter ``step``, ``exp_avg``, ``exp_avg_sq``).
+    ``health=True``: the step is ``shg_adam_buckets_health_f32`` + ``shg_health_reduce_f64`` -- the same pass with the same bits in every
+    parameter and moment, which also leaves gradient-health figures of the values it read anyway in ``health_table()``, float64
+    ``[parameters + 1, HEALTH_COLS]`` on the device (row i = ``_params[i]``, the last row the optimiser's total): sums added and the
+    maximum kept over the steps since ``health_reset()``; no host read, capturable.  Off by default: the plain entry point."""
 
     DIV_MODE = DIV_RECIPROCAL      # how the average is taken for world > 1: as torch's div_ by a host scalar does on the device
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False, foreach=None,
-                 capturable=False, differentiable=False, fused=None, sync=None, bucket_bytes=64 << 20):
+                 capturable=False, differentiable=False, fused=None, sync=None, bucket_bytes=64 << 20, health=False):
         defaults = dict(torch.optim.Adam([torch.nn.Parameter(torch.zeros(1))]).defaults)       # torch's keys, whatever the version
         defaults.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=foreach,
                         capturable=bool(capturable), differentiable=differentiable, fused=fused)
@@ -177,6 +182,12 @@ class ShgAdam(torch.optim.Optimizer):
         self._hyper = torch.zeros(len(self.param_groups) * 4, dtype=torch.float64, device=self.device)
         self._hyper_host = None
         self._tables = {}               # touched set -> (device table, chunks)
+        self.health = bool(health)
+        if self.health:                 # allocated here: a captured step holds the addresses
+            chunks = int(_chunk_prefix([p.numel() for p in self._params])[-1])
+            self._health_ws = torch.zeros([chunks, HEALTH_COLS], dtype=torch.float64, device=self.device)
+            self._health = torch.zeros([n + 1, HEALTH_COLS], dtype=torch.float64, device=self.device)
+            self._health_steps = torch.zeros([1], dtype=torch.float64, device=self.device)
         self._attach_state()
 
     # -- hyper-parameters ------------------------------------------------------------------------------------------------------------
@@ -299,13 +310,72 @@ class ShgAdam(torch.optim.Optimizer):
             st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             check(lib.shg_adam_tick(ctypes.c_void_p(tab.data_ptr()), nseg, ctypes.c_void_p(self._hyper.data_ptr()), len(self.param_groups),
                                     ctypes.c_void_p(self.steps.data_ptr()), ctypes.c_void_p(self._scalars.data_ptr()), st), 'adam_tick')
-            check(lib.shg_adam_buckets_f32(ctypes.c_void_p(tab.data_ptr()), nseg, chunks, ctypes.c_void_p(self._scalars.data_ptr()),
-                                           float(world), self.DIV_MODE if world > 1 else DIV_NONE, int(bool(sync.sanitize)), st),
-                  'adam_buckets_f32')
+            if self.health:
+                if chunks != self._health_ws.shape[0]:
+                    raise ShgError(f'ShgAdam: the table has {chunks} chunks, the health workspace {self._health_ws.shape[0]}')
+                check(lib.shg_adam_buckets_health_f32(ctypes.c_void_p(tab.data_ptr()), nseg, chunks, ctypes.c_void_p(self._scalars.data_ptr()),
+                                                      float(world), self.DIV_MODE if world > 1 else DIV_NONE, int(bool(sync.sanitize)),
+                                                      ctypes.c_void_p(self._health_ws.data_ptr()), st), 'adam_buckets_health_f32')
+                check(lib.shg_health_reduce_f64(ctypes.c_void_p(tab.data_ptr()), nseg, chunks, ctypes.c_void_p(self._health_ws.data_ptr()),
+                                                ctypes.c_void_p(self._health.data_ptr()), ctypes.c_void_p(self._health_steps.data_ptr()), st),
+                      'health_reduce_f64')
+            else:
+                check(lib.shg_adam_buckets_f32(ctypes.c_void_p(tab.data_ptr()), nseg, chunks, ctypes.c_void_p(self._scalars.data_ptr()),
+                                               float(world), self.DIV_MODE if world > 1 else DIV_NONE, int(bool(sync.sanitize)), st),
+                      'adam_buckets_f32')
         sync.rearm()
         for p in sync.untouched():             # as after zero_grad(set_to_none=True)
             p.grad = None
         _bump_versions(p for p in self._params if id(p) in touched)
+
+    # -- gradient health (health=True) -----------------------------------------------------------------------------------------------
+    def _need_health(self):
+        if not self.health:
+            raise ShgError('ShgAdam: built with health=False: there is no health table')
+
+    def health_table(self):
+        """float64 [parameters + 1, HEALTH_COLS] on the device (the tensor the kernels write, not a copy)."""
+        self._need_health()
+        return self._health
+
+    def health_steps(self):
+        """float64 [1] on the device: the steps (with at least one gradient) since the last reset."""
+        self._need_health()
+        return self._health_steps
+
+    @torch.no_grad()
+    def health_reset(self):
+        self._need_health()
+        self._health.zero_()
+        self._health_steps.zero_()
+
+    @torch.no_grad()
+    def health_report(self, collector, prefix):
+        """The optimiser's totals since the last reset as one value each in the collector's slots ``Grad/<prefix>/norm`` (root of the mean
+        over the steps of sum g^2), ``Grad/<prefix>/nonfinite`` (elements the sanitisation replaced), ``Grad/<prefix>/max`` (largest |g|) and
+        ``Update/<prefix>/ratio`` (sqrt(sum dp^2) / sqrt(sum p^2)); then the table is reset.  A few small device operations and one collector
+        launch, no host read; nothing is reported when no step was taken.  Call it once per tick, outside graph captures.  The collector
+        takes float32 tensors, so each total is rounded to float32 once on its way in: a count of replaced elements above 2^24 is then
+        within 6e-8 of itself, no longer exact (``health_table()`` / ``health_rows()`` keep the float64 value)."""
+        self._need_health()
+        tot, steps = self._health[-1], self._health_steps[0].clamp(min=1.0)
+        vals = torch.stack([(tot[0] / steps).sqrt(), tot[1], tot[2], (tot[4] / tot[3].clamp(min=1e-300)).sqrt()]).to(torch.float32)
+        collector.report_many({f'Grad/{prefix}/norm': vals[0:1], f'Grad/{prefix}/nonfinite': vals[1:2], f'Grad/{prefix}/max': vals[2:3],
+                               f'Update/{prefix}/ratio': vals[3:4]})
+        self.health_reset()
+
+    def health_rows(self, names=None):
+        """{name: {'grad_sq', 'nonfinite', 'grad_max', 'param_sq', 'update_sq'}} per parameter since the last reset (one read-back).
+        ``names``: {id(p): name}, e.g. from ``module.named_parameters()``; default: the index in streaming order."""
+        self._need_health()
+        host = self._health.cpu().numpy()
+        keys = ('grad_sq', 'nonfinite', 'grad_max', 'param_sq', 'update_sq')
+        out = {}
+        for i, p in enumerate(self._params):
+            name = str(i) if names is None else names.get(id(p), str(i))
+            out[name] = dict(zip(keys, (float(v) for v in host[i])))
+        out['total'] = dict(zip(keys, (float(v) for v in host[-1])))
+        return out
 
 
 class EmaUpdater:

@@ -10,12 +10,18 @@ Mirrors ``lib/experiments/stylegan_default.py``:
     ``effective_batch_gpu`` samples (``loss.accumulate_gradients(phase, real_img, real_c, gen_z, gen_c, sync, gain=interval)``),
     sanitises the gradients (``nan_to_num(nan=0, posinf=1e5, neginf=-1e5)``) and steps.
   * ``update_ema``   -- :383-390: ``ema_beta = 0.5 ** (batch_size / max(ema_nimg, 1e-8))`` with the ``ema_rampup`` cap, buffers copied.
-  * ``train``        -- the iteration loop :370-396 without its logging / snapshot / metric maintenance (``training_stats``,
-    ``dnnlib`` and the snapshot pickles are not part of the reference tree; ``on_tick`` is the hook for them).
+  * ``train``        -- the iteration loop :370-396; its logging / snapshot / metric maintenance (the tick block :402-575) is opt-in:
+    ``Maintenance`` (status line, metrics, sample grid, snapshot, ``stats.jsonl``), ``save_snapshot`` / ``load_snapshot`` (state_dicts,
+    counters and RNG states: a resumed run continues with the bits of the uninterrupted one) and ``image_grid``
+    (``draw_functor.output`` :74-84 on the device).  ``on_tick`` stays the hook for anything else.
 The reference wraps the networks in DistributedDataParallel (:172-187); here every phase owns a ``grad_sync.BucketedAllReduce`` over
 its module's parameters (RCCL all-reduce launched from backward hooks, averaged and sanitised per bucket) -- with one rank it only
 sanitises, so the same code runs on one GPU and on N."""
+import json
 import os
+import time
+
+import numpy as np
 import torch
 
 from .grad_sync import BucketedAllReduce
@@ -190,7 +196,10 @@ class PhaseGraphs:
         self.warmup = warmup
         if warmup < 1:
             raise ValueError('PhaseGraphs: warmup >= 1 (lazily built constants, Adam state and allocator pools must exist before the capture)')
-        self.split = any(ph.sync is not None and ph.sync.reduce for ph in phases)      # more than one rank: two graphs per phase
+        # more than one rank: two graphs per phase.  Decided per phase (a phase without a reducing sync is one graph, whatever the others
+        # are); ``split`` says whether any phase takes the two-graph form
+        self.split_of = {ph.name: ph.sync is not None and bool(ph.sync.reduce) for ph in phases}
+        self.split = any(self.split_of.values())
         for ph in phases:
             if hasattr(ph.opt, 'step_from_buckets'):       # optim.ShgAdam keeps its step counters on the device by construction
                 continue
@@ -213,11 +222,14 @@ class PhaseGraphs:
                 continue
             self.z[ph.name].copy_(z)
             g = self.graphs.get(ph.name)
+            split = self.split_of[ph.name]
+            if ph.start_event is not None:                   # (around the replay, not inside the graph)
+                ph.start_event.record(torch.cuda.current_stream(self.device))
             if g is None and self.seen[ph.name] < self.warmup:
                 self.seen[ph.name] += 1
                 _phase_body(ph, self.loss, self.real, self.real_c, self.z[ph.name], self.gen_c, self.eff)
             else:
-                if g is None and not self.split:
+                if g is None and not split:
                     self._invalidate()
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g):
@@ -246,13 +258,15 @@ class PhaseGraphs:
                     if float(ok.item()) < 1.0:
                         raise RuntimeError(f'PhaseGraphs: capture of phase {ph.name} failed on ' + ('this rank: ' + repr(err) if err is not None else 'another rank'))
                     g = self.graphs[ph.name] = (ga, gb)
-                if self.split:
+                if split:
                     g[0].replay()
                     ph.sync.reduce_all()
                     g[1].replay()
                 else:
                     g.replay()
                 self._invalidate()
+            if ph.end_event is not None:
+                ph.end_event.record(torch.cuda.current_stream(self.device))
             ran.append(ph.name)
         return ran
 
@@ -275,15 +289,316 @@ def update_ema(G_ema, G, batch_size, cur_nimg, ema_kimg=10.0, ema_rampup=None):
     return beta
 
 
+# ---- what a run keeps: sample grids, snapshots, the tick block (stylegan_default.py:402-575) ---------------------------------------------
+SNAPSHOT_VERSION = 1
+
+
+def _rank_world():
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        return torch.distributed.get_rank(), torch.distributed.get_world_size()
+    return 0, 1
+
+
+def image_grid(images, grid_size, drange=(-1, 1), real=None, mask=None):
+    """``draw_functor.output`` (stylegan_default.py:74-84) on the device: float32 [gw * gh, C, H, W] (C 1 or 3) -> uint8
+    [gh * H, gw * W, C], ``(uint8) clip(rint((x - lo) * (255 / (hi - lo))), 0, 255)`` in float32 with numpy's rounding (ties to even).
+    ``real`` / ``mask`` ([N, C, H, W] / [N, 1, H, W]): the grid of ``real * mask + images * (1 - mask)`` (shgan_default.py:107)."""
+    import ctypes
+    from . import _lib, kernels
+    gw, gh = (int(v) for v in grid_size)
+    lo, hi = (float(v) for v in drange)
+    if not hi > lo:
+        raise ValueError(f'image_grid: drange must be (lo, hi) with hi > lo (got {drange})')
+    if not isinstance(images, torch.Tensor) or images.ndim != 4 or images.shape[1] not in (1, 3):
+        raise ValueError('image_grid: float32 [N, C, H, W] with C 1 or 3 expected')
+    n, c, h, w = images.shape
+    if gw < 1 or gh < 1 or n != gw * gh:
+        raise ValueError(f'image_grid: {n} images do not fill a {gw} x {gh} grid')
+    if (real is None) != (mask is None):
+        raise ValueError('image_grid: real and mask go together')
+    if real is not None and (real.shape != images.shape or mask.shape != (n, 1, h, w)):
+        raise ValueError('image_grid: real like the images and mask [N, 1, H, W] expected')
+    launch = kernels._Launch()               # (``launch``, not ``L``: the allocation tests cover this function from tests/test_gpu_train_run.py)
+    images = launch.req(images, 'images')
+    real, mask = launch.req(real, 'real'), launch.req(mask, 'mask')
+    out = launch.new([gh * h, gw * w, c], torch.uint8)           # every byte is written
+    scale = float(np.float32(255.0 / (hi - lo)))
+    with launch:
+        _lib.check(_lib.get_lib().shg_image_grid_u8(
+            ctypes.c_void_p(images.data_ptr()), ctypes.c_void_p(real.data_ptr() if real is not None else None),
+            ctypes.c_void_p(mask.data_ptr() if mask is not None else None), ctypes.c_void_p(out.data_ptr()), c, h, w, gw, gh, lo, scale,
+            launch.stream()), 'image_grid_u8')
+    return out
+
+
+def save_image_grid(u8, path):
+    """uint8 [H, W, 1 or 3] (device or host) -> a PNG, written atomically (Pillow on the host)."""
+    import PIL.Image
+    arr = u8.cpu().numpy() if isinstance(u8, torch.Tensor) else np.asarray(u8)
+    img = PIL.Image.fromarray(arr[:, :, 0], 'L') if arr.shape[2] == 1 else PIL.Image.fromarray(arr, 'RGB')
+    atomic_write(path, lambda tmp: img.save(tmp, format='PNG'))
+
+
+def atomic_write(path, write_fn):
+    """``write_fn(tmp)`` writes a temporary file in ``path``'s directory, which then takes ``path``'s place in one step (``os.replace``);
+    a writer that raises leaves what was at ``path`` as it was and no temporary file behind."""
+    path = os.fspath(path)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = f'{path}.tmp{os.getpid()}'
+    try:
+        write_fn(tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def _distinct_opts(phases):
+    """[(key, optimiser)], one entry per optimiser object: the phases that share one ('Gmain' / 'Greg') give the key 'Gmain+Greg'."""
+    out = []
+    for ph in phases or ():
+        hit = [e for e in out if e[1] is ph.opt]
+        if hit:
+            hit[0][0].append(ph.name)
+        else:
+            out.append(([ph.name], ph.opt))
+    return [('+'.join(names), opt) for names, opt in out]
+
+
+def health_prefixes(phases):
+    """[(prefix, optimiser)] for the optimisers built with ``health=True``: the stem its phase names share once 'main' / 'reg' / 'both' is
+    taken off ('Gmain+Greg' -> 'G'); an optimiser whose phases share no such stem, or whose stem another optimiser has too, keeps its whole
+    key ('Gmain+Greg'), so that two optimisers never fold into one ``Grad/<prefix>/*`` slot."""
+    stems = []
+    for key, opt in _distinct_opts(phases):
+        if not getattr(opt, 'health', False):
+            continue
+        found = set()
+        for name in key.split('+'):
+            hit = [name[:-len(sfx)] for sfx in ('main', 'reg', 'both') if name.endswith(sfx) and len(name) > len(sfx)]
+            found.add(hit[0] if hit else None)
+        stems.append((found.pop() if len(found) == 1 else None, key, opt))
+    count = {}
+    for stem, _, _ in stems:
+        count[stem] = count.get(stem, 0) + 1
+    return [(stem if stem is not None and count[stem] == 1 else key, opt) for stem, key, opt in stems]
+
+
+def jsonl_fields(stats):
+    """``Collector.as_dict()`` as one ``stats.jsonl`` line holds it: a name that received nothing in the tick is left out (the reference's
+    line holds the reported names only), and a value that is not finite is written as null -- the line is strict JSON."""
+    out = {}
+    for name, d in stats.items():
+        if d['num'] == 0 and not d.get('nonfinite'):
+            continue
+        out[name] = {k: (None if isinstance(v, float) and not np.isfinite(v) else v) for k, v in d.items()}
+    return out
+
+
+def _rng_state(device):
+    kind, keys, pos, has_gauss, cached = np.random.get_state()
+    st = {'torch': torch.get_rng_state(), 'numpy': {'kind': str(kind), 'keys': torch.from_numpy(np.asarray(keys, np.int64).copy()), 'pos': int(pos),
+                                                    'has_gauss': int(has_gauss), 'cached_gaussian': float(cached)}}
+    if device is not None and torch.device(device).type == 'cuda':
+        st['cuda'] = torch.cuda.get_rng_state(device)
+    return st
+
+
+def _set_rng_state(st, device):
+    torch.set_rng_state(st['torch'].cpu())
+    n = st['numpy']
+    np.random.set_state((n['kind'], n['keys'].cpu().numpy().astype(np.uint32), n['pos'], n['has_gauss'], n['cached_gaussian']))
+    if 'cuda' in st and device is not None and torch.device(device).type == 'cuda':
+        torch.cuda.set_rng_state(st['cuda'].cpu(), device)
+
+
+def save_snapshot(path, G, D, G_ema, phases=None, loss=None, ada=None, progress=None, device=None, save_fn=None):
+    """One ``torch.save``d dict of state_dicts (no pickled modules): the three networks, one entry per DISTINCT optimiser of ``phases``,
+    the loss state (``pl_mean``), the loss's augment pipe and ``ada`` (an ``AdaController``), ``progress`` (``cur_nimg``, ``batch_idx``,
+    ``cur_tick``, ``tick_start_nimg``), the RNG states of every rank (host, device, numpy; gathered to rank 0) and the format version and
+    world size.  Rank 0 writes, atomically; beside it ``G_ema-<kimg:06d>.pth``, the bare ``G_ema.state_dict()``.  A collective when
+    ``torch.distributed`` is initialised: every rank calls it.  Returns the dict on rank 0, None elsewhere."""
+    rank, world = _rank_world()
+    rng = _rng_state(device)
+    if world > 1:
+        gathered = [None] * world if rank == 0 else None
+        torch.distributed.gather_object(rng, gathered, dst=0)
+    else:
+        gathered = [rng]
+    if rank != 0:
+        return None
+    progress = dict(progress or {})
+    for k in ('cur_nimg', 'batch_idx', 'cur_tick', 'tick_start_nimg'):
+        progress[k] = int(progress.get(k, 0))
+    pipe = getattr(loss, 'augment_pipe', None)
+    snap = {
+        'version': SNAPSHOT_VERSION, 'world': world, 'progress': progress,
+        'G': G.state_dict(), 'D': D.state_dict(), 'G_ema': G_ema.state_dict(),
+        'opt': {key: opt.state_dict() for key, opt in _distinct_opts(phases)},
+        'loss': loss.state_dict() if hasattr(loss, 'state_dict') else {},
+        'augment_pipe': pipe.state_dict() if pipe is not None else None,
+        'ada': ada.state_dict() if ada is not None else None,
+        'rng': gathered,
+    }
+    save = torch.save if save_fn is None else save_fn
+    atomic_write(path, lambda tmp: save(snap, tmp))
+    ema_path = os.path.join(os.path.dirname(os.path.abspath(path)), 'G_ema-%06d.pth' % (progress['cur_nimg'] // 1000))
+    atomic_write(ema_path, lambda tmp: save(snap['G_ema'], tmp))
+    return snap
+
+
+def load_snapshot(path, G, D, G_ema, phases=None, loss=None, ada=None, device=None):
+    """Restore what ``save_snapshot`` wrote, on every rank (rank r takes RNG entry r).  Raises on another format version or world size,
+    naming both.  Returns the progress dict."""
+    rank, world = _rank_world()
+    snap = torch.load(path, map_location='cpu', weights_only=True)
+    if snap.get('version') != SNAPSHOT_VERSION:
+        raise RuntimeError(f'load_snapshot: {path} has format version {snap.get("version")}, this code reads version {SNAPSHOT_VERSION}')
+    if snap.get('world') != world:
+        raise RuntimeError(f'load_snapshot: {path} was written by {snap.get("world")} ranks, this run has {world} '
+                           '(resuming with another world size is not supported)')
+    G.load_state_dict(snap['G'])
+    D.load_state_dict(snap['D'])
+    G_ema.load_state_dict(snap['G_ema'])
+    opts = _distinct_opts(phases)
+    if sorted(snap['opt']) != sorted(k for k, _ in opts):
+        raise RuntimeError(f'load_snapshot: {path} holds the optimisers {sorted(snap["opt"])}, the phases have {sorted(k for k, _ in opts)}')
+    for key, opt in opts:
+        opt.load_state_dict(snap['opt'][key])
+    if hasattr(loss, 'load_state_dict') and snap['loss']:
+        loss.load_state_dict(snap['loss'])
+    pipe = getattr(loss, 'augment_pipe', None)
+    if (pipe is None) != (snap['augment_pipe'] is None) or (ada is None) != (snap['ada'] is None):
+        raise RuntimeError(f'load_snapshot: {path} and this run differ in whether there is an augment pipe / an ADA controller')
+    if pipe is not None:
+        pipe.load_state_dict(snap['augment_pipe'])
+    if ada is not None:
+        ada.load_state_dict(snap['ada'])
+    _set_rng_state(snap['rng'][rank], device)
+    return dict(snap['progress'])
+
+
+class Maintenance:
+    """The tick block of stylegan_default.py:402-575 for ``train``: conditions (``done or cur_tick % k == 0``; None = never) and order of the
+    reference -- status line, metrics, image, snapshot, statistics.
+    ``metrics``: {name: callable(G_ema) -> {key: float}}, reported as ``Metrics/<key>``.
+    ``grid``: (inputs, (gw, gh)); inputs = {'batches': [kwargs of a G_ema call, ...], 'real': [N, 3, H, W] or None, 'mask': [N, 1, H, W] or
+    None}: ``fakes<kimg>.png`` from the concatenated outputs and, with real and mask, ``fakes<kimg>_combined.png``.
+    Files under ``log_dir``: ``stats.jsonl`` (one line per tick, appended), ``fakes*.png``, ``weight/network-snapshot-<kimg>.pt`` and
+    ``weight/G_ema-<kimg>.pth``.  Rank 0 writes; the collectives (collector all-reduce, RNG gather) run on every rank."""
+
+    def __init__(self, log_dir, snapshot_ticks=None, image_ticks=None, metric_ticks=None, metrics=None, grid=None, drange=(-1, 1),
+                 print_fn=print):
+        self.log_dir = os.fspath(log_dir)
+        self.snapshot_ticks, self.image_ticks, self.metric_ticks = snapshot_ticks, image_ticks, metric_ticks
+        self.metrics = dict(metrics or {})
+        self.grid, self.drange, self.print_fn = grid, drange, print_fn
+        self.start_time = self.tick_start_time = time.time()
+        self.maintenance_time = 0.0
+        self.snapshots, self.images, self.lines = [], [], []          # what this object wrote / logged (paths, paths, dicts)
+
+    @staticmethod
+    def due(ticks, cur_tick, done):
+        return ticks is not None and (done or cur_tick % ticks == 0)
+
+    def snapshot_path(self, cur_nimg):
+        return os.path.join(self.log_dir, 'weight', 'network-snapshot-%06d.pt' % (cur_nimg // 1000))
+
+    @torch.no_grad()
+    def draw_grid(self, G_ema, cur_nimg):
+        inputs, grid_size = self.grid
+        was_training = G_ema.training
+        G_ema.eval()
+        try:
+            images = torch.cat([G_ema(**kw).to(torch.float32) for kw in inputs['batches']])
+        finally:
+            G_ema.train(was_training)
+        out = [os.path.join(self.log_dir, 'fakes%06d.png' % (cur_nimg // 1000))]
+        grids = [image_grid(images, grid_size, self.drange)]
+        if inputs.get('real') is not None and inputs.get('mask') is not None:
+            out.append(os.path.join(self.log_dir, 'fakes%06d_combined.png' % (cur_nimg // 1000)))
+            grids.append(image_grid(images, grid_size, self.drange, real=inputs['real'], mask=inputs['mask']))
+        if _rank_world()[0] == 0:
+            for path, u8 in zip(out, grids):
+                save_image_grid(u8, path)
+                self.images.append(path)
+
+    def tick(self, collector, cur_tick, cur_nimg, batch_idx, tick_start_nimg, done, G, D, G_ema, phases, loss, ada, device):
+        """One tick; ``progress`` in a snapshot is the state the NEXT iteration starts from (``cur_tick + 1``, tick start = ``cur_nimg``)."""
+        rank = _rank_world()[0]
+        now = time.time()
+        pipe = getattr(loss, 'augment_pipe', None)
+        r0 = collector.report0
+        fields = [f"tick {r0('Progress/tick', cur_tick):<5d}", f"kimg {r0('Progress/kimg', cur_nimg / 1e3):<8.1f}",
+                  f"time {r0('Timing/total_sec', now - self.start_time):<10.1f}",
+                  f"sec/tick {r0('Timing/sec_per_tick', now - self.tick_start_time):<7.1f}",
+                  f"sec/kimg {r0('Timing/sec_per_kimg', (now - self.tick_start_time) / max(cur_nimg - tick_start_nimg, 1) * 1e3):<7.2f}",
+                  f"maintenance {r0('Timing/maintenance_sec', self.maintenance_time):<6.1f}",
+                  f"augment {r0('Progress/augment', float(pipe.p.cpu()) if pipe is not None else 0.0):.3f}"]
+        if rank == 0 and self.print_fn is not None:
+            self.print_fn(' '.join(fields))
+        if self.metrics and self.due(self.metric_ticks, cur_tick, done):
+            for name, fn in self.metrics.items():
+                for key, value in fn(G_ema).items():
+                    r0(f'Metrics/{key}', float(value))
+        if self.grid is not None and self.due(self.image_ticks, cur_tick, done):
+            self.draw_grid(G_ema, cur_nimg)
+        if self.due(self.snapshot_ticks, cur_tick, done):
+            path = self.snapshot_path(cur_nimg)
+            save_snapshot(path, G, D, G_ema, phases=phases, loss=loss, ada=ada, device=device,
+                          progress=dict(cur_nimg=cur_nimg, batch_idx=batch_idx, cur_tick=cur_tick + 1, tick_start_nimg=cur_nimg))
+            if rank == 0:
+                self.snapshots.append(path)
+        for ph in phases:                                # per-phase milliseconds of the last run of the phase (make_phases(timing=True))
+            if ph.start_event is not None and ph.end_event is not None:
+                try:
+                    ph.end_event.synchronize()
+                    r0('Timing/' + ph.name, ph.start_event.elapsed_time(ph.end_event))
+                except RuntimeError:                     # an event that was never recorded (a phase that has not run since the resume)
+                    pass
+        for prefix, opt in health_prefixes(phases):
+            opt.health_report(collector, prefix)
+        collector.update()
+        line = dict(jsonl_fields(collector.as_dict()), timestamp=time.time())
+        self.lines.append(line)
+        if rank == 0:
+            os.makedirs(self.log_dir, exist_ok=True)
+            with open(os.path.join(self.log_dir, 'stats.jsonl'), 'at') as fh:
+                fh.write(json.dumps(line, allow_nan=False) + '\n')
+        self.tick_start_time = time.time()
+        self.maintenance_time = self.tick_start_time - now
+        return line
+
+
 def train(G, D, G_ema, loss, batches, phases, z_dim, batch_size, batch_gpu, total_kimg, effective_batch_gpu=None, ema_kimg=10.0,
-          ema_rampup=None, kimg_per_tick=4, on_tick=None, device=None, ema=None, ada=None):
+          ema_rampup=None, kimg_per_tick=4, on_tick=None, device=None, ema=None, ada=None, graphs=None, collector=None, maintenance=None,
+          resume=None):
     """The iteration loop of stylegan_default.py:370-396: ``batches`` yields real images [batch_gpu, C, H, W] for this rank,
     ``batch_size`` is the GLOBAL batch (= batch_gpu * world).  ``ema``: an ``optim.EmaUpdater(G_ema, G)`` (one launch per iteration)
     in place of ``update_ema``.  ``ada``: an ``ada.AdaController`` over the loss's augment pipe, fed the signs of the real logits after the
-    EMA update (stylegan_default.py:397-400).  Returns (cur_nimg, batch_idx)."""
+    EMA update (stylegan_default.py:397-400).  Returns (cur_nimg, batch_idx).
+
+    The run around it, all optional: ``graphs``: a ``PhaseGraphs`` over the same phases and loss, used instead of ``run_phases``.
+    ``maintenance``: a ``Maintenance`` -- the tick block (:402-575); its statistics go through ``collector`` (a
+    ``training_stats.Collector``, the one the loss and ``health_report`` feed; one is made when none is given).  ``resume``: the path of a
+    ``save_snapshot`` file, restored before the first iteration -- networks, optimisers, loss, ADA, counters and RNG states; ``batches`` may
+    then be a callable ``batch_idx -> iterator`` so that the data stream is re-entered where it stood (an iterator is taken as it is)."""
     cur_nimg, batch_idx, cur_tick, tick_start = 0, 0, 0, 0
+    if resume is not None:
+        prog = load_snapshot(resume, G, D, G_ema, phases=phases, loss=loss, ada=ada, device=device)
+        cur_nimg, batch_idx, cur_tick, tick_start = prog['cur_nimg'], prog['batch_idx'], prog['cur_tick'], prog['tick_start_nimg']
+        if cur_nimg >= total_kimg * 1000:
+            return cur_nimg, batch_idx
+    if maintenance is not None and collector is None:
+        from .training_stats import Collector
+        collector = Collector(device if device is not None else next(G.parameters()).device)
+    if callable(batches):
+        batches = batches(batch_idx)
     for real_img in batches:
-        run_phases(real_img, z_dim, phases, batch_idx, loss, batch_gpu, effective_batch_gpu, device)
+        if graphs is not None:
+            graphs.run(real_img, batch_idx)
+        else:
+            run_phases(real_img, z_dim, phases, batch_idx, loss, batch_gpu, effective_batch_gpu, device)
         if ema is not None:
             ema.update(batch_size, cur_nimg, ema_kimg, ema_rampup)
         else:
@@ -294,6 +609,8 @@ def train(G, D, G_ema, loss, batches, phases, z_dim, batch_size, batch_gpu, tota
         batch_idx += 1
         done = cur_nimg >= total_kimg * 1000
         if done or cur_tick == 0 or cur_nimg >= tick_start + kimg_per_tick * 1000:
+            if maintenance is not None:
+                maintenance.tick(collector, cur_tick, cur_nimg, batch_idx, tick_start, done, G, D, G_ema, phases, loss, ada, device)
             if on_tick is not None:
                 on_tick(cur_tick, cur_nimg, batch_idx)
             cur_tick += 1
