@@ -502,6 +502,35 @@ int shg_lpips_head_pairs_f32(const float* f, const int* ia, const int* ib, const
 int shg_lpips_scaling_f32(const void* x, const float* lut, float scale, float bias, const float* shift, const float* scaling, float* y, int B,
                           int H, int W, void* stream);
 
+/* ---- LPIPS as a training loss (sh-gan_amd/lpips.py: Lpips.loss; csrc/lpips_bwd.hip): the backward pass of the frozen network with
+ * respect to the pred image.  Current stream, no atomics, no host synchronisation, fixed summation orders.  ONE masking rule: whoever
+ * writes a gradient into the buffer of a post-ReLU activation y selects it by y > 0 itself (a select, never a multiply).
+ * shg_lpips_dgrad_f32: input gradient of a stride-1 k x k convolution at pad = k / 2 (odd k <= 7) on the detector's exact-fp32 MFMA tile:
+ *   dx [B,O,H,W] = conv2d(g [B,I,H,W], wt, pad) with wt [O,I,k,k] = w.transpose(0,1).flip(2,3) packed by shg_inception_weight_prep_f32
+ *   (16-byte aligned); no bias, no ReLU; ymask [B,O,H,W] given: dx = ymask > 0 ? dx : 0; NULL: stored as it is.  K is never split.
+ * shg_lpips_maxpool_bwd_f32: k x k (k = 2 or 3), stride 2, floor max pool of x [B,C,H,W] (a post-ReLU activation), gy [B,C,OH,OW],
+ *   OH = (H - k) / 2 + 1: dx = x > 0 ? sum of gy over the windows whose first maximum in row-major order the element is : 0.
+ * shg_lpips_head_bwd_f32: one tap's distance head.  f, fr [B,C,h,w] (pred / real tap), w [C], g [B] -> df [B,C,h,w]: per position
+ *   s = sqrt(sum f^2), a = 1 / (s + 1e-10), q_c = 2 w_c (a f_c - fr_c / (|fr| + 1e-10)) g_b / (h w),
+ *   v_c = f_c > 0 ? a q_c - f_c a^2 (sum_j q_j f_j) / s : 0 (an all-zero tap vector gives exact zeros); df = v or, accumulate != 0, df + v.
+ * shg_lpips_conv1_pm1_f32 / shg_lpips_scale_pm1_f32: shg_lpips_conv1_f32 / shg_lpips_scaling_f32 for a float32 image v in [-1, 1] that
+ *   enters the scaling layer as it is, s(v) = (v - shift[c]) * float32(1 / scaling[c]) (HOST arrays of 3 floats).
+ * shg_lpips_conv1_dgrad_f32: g [B,64,OH,OW], w [64,3,11,11] (the caller folds 1 / scaling[c] in) -> dx [B,3,H,W], the transposed 11 x 11
+ *   stride 4 pad 2 convolution; pixels that no window reaches get 0.
+ * shg_l1_mean_f32: out [B] float32 = mean |a - b| over the n elements of image b (float64, fixed order, rounded once; one launch).
+ * shg_l1_mean_bwd_f32: dx [B,n] = sign(a - b) g[b] / n (sign(0) = 0). */
+int shg_lpips_dgrad_f32(const float* g, const float* wp, const float* ymask, float* dx, int B, int I, int O, int H, int W, int k, int pad,
+                        void* stream);
+int shg_lpips_maxpool_bwd_f32(const float* x, const float* gy, float* dx, int B, int C, int H, int W, int k, void* stream);
+int shg_lpips_head_bwd_f32(const float* f, const float* fr, const float* w, const float* g, float* df, int B, int C, int h, int wd, int accumulate,
+                           void* stream);
+int shg_lpips_conv1_pm1_f32(const float* x, const float* shift, const float* scaling, const float* wp, const float* bp, float* y, int B, int H, int W,
+                            void* stream);
+int shg_lpips_scale_pm1_f32(const float* x, const float* shift, const float* scaling, float* y, int B, int H, int W, void* stream);
+int shg_lpips_conv1_dgrad_f32(const float* g, const float* w, float* dx, int B, int H, int W, void* stream);
+int shg_l1_mean_f32(const float* a, const float* b, float* out, int B, long n, void* stream);
+int shg_l1_mean_bwd_f32(const float* a, const float* b, const float* g, float* dx, int B, long n, void* stream);
+
 /* ---- Perceptual path length (`ppl2_wend`, lib/evaluator/stylegan_metrics/perceptual_path_length.py; sh-gan_amd/ppl.py drives it;
  * csrc/ppl.hip): the sampler's image front end (:71-85) in one pass over the synthesis output.  x [N,C,H,W] float32 in [-1, 1], C = 1
  * or 3, H == W -> y [N,3,S,S] float32:

@@ -165,6 +165,14 @@ _SIGS = {
     'shg_lpips_head_pairs_f32': [c_fp, c_fp, c_fp, ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, ctypes.c_size_t, c_fp, c_fp,
                                  c_fp],
     'shg_lpips_scaling_f32': [c_fp, c_fp, c_f, c_f, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp, c_i, c_i, c_i, c_fp],
+    'shg_lpips_dgrad_f32': [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'shg_lpips_maxpool_bwd_f32': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'shg_lpips_head_bwd_f32': [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp],
+    'shg_lpips_conv1_pm1_f32': [c_fp, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
+    'shg_lpips_scale_pm1_f32': [c_fp, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp, c_i, c_i, c_i, c_fp],
+    'shg_lpips_conv1_dgrad_f32': [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp],
+    'shg_l1_mean_f32': [c_fp, c_fp, c_fp, c_i, c_l, c_fp],
+    'shg_l1_mean_bwd_f32': [c_fp, c_fp, c_fp, c_fp, c_i, c_l, c_fp],
     'shg_ppl_frontend_f32': [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_f), ctypes.POINTER(c_f), c_fp],
     'shg_adam_tick': [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp],
     'shg_adam_buckets_f32': [c_fp, c_i, c_l, c_fp, c_f, c_i, c_i, c_fp],

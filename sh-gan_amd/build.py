@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libshgan_hip.so')
-SOURCES = ['capi.hip', 'upfirdn2d.hip', 'pointwise.hip', 'dense.hip', 'conv_mfma.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_wino_poly.hip', 'conv_wgrad.hip', 'conv_wgrad_wino.hip', 'conv_f16.hip', 'conv_wgrad_f16.hip', 'upfirdn2d_f16.hip', 'pointwise_f16.hip', 'conv_f16_ring.hip', 'conv_f16_upring.hip', 'conv_f16_down.hip', 'shu.hip', 'mask_raster.hip', 'mask_lama.hip', 'fid_stats.hip', 'image_metrics.hip', 'resize.hip', 'randcrop.hip', 'ada.hip', 'ada_tail.hip', 'inception.hip', 'lpips.hip', 'optim.hip', 'kid.hip', 'pr.hip', 'vgg16.hip', 'ppl.hip', 'plural.hip', 'svm.hip', 'gemm_f64.hip', 'inpaint.hip', 'membrane.hip', 'hole_label.hip', 'train_stats.hip']
+SOURCES = ['capi.hip', 'upfirdn2d.hip', 'pointwise.hip', 'dense.hip', 'conv_mfma.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_wino_poly.hip', 'conv_wgrad.hip', 'conv_wgrad_wino.hip', 'conv_f16.hip', 'conv_wgrad_f16.hip', 'upfirdn2d_f16.hip', 'pointwise_f16.hip', 'conv_f16_ring.hip', 'conv_f16_upring.hip', 'conv_f16_down.hip', 'shu.hip', 'mask_raster.hip', 'mask_lama.hip', 'fid_stats.hip', 'image_metrics.hip', 'resize.hip', 'randcrop.hip', 'ada.hip', 'ada_tail.hip', 'inception.hip', 'lpips.hip', 'lpips_bwd.hip', 'optim.hip', 'kid.hip', 'pr.hip', 'vgg16.hip', 'ppl.hip', 'plural.hip', 'svm.hip', 'gemm_f64.hip', 'inpaint.hip', 'membrane.hip', 'hole_label.hip', 'train_stats.hip']
 # per-source extras: the Winograd weight-gradient transforms are scalar fp32 chains beside MFMAs -- SLP-packed (v_pk_*) forms cost register
 # moves and issue slots there
 SRC_FLAGS = {'conv_wgrad_wino.hip': ['-fno-slp-vectorize']}

@@ -1328,3 +1328,64 @@ def shu_split_irfft2(y, cw, gauss, outs, accumulate):
             check(_lib.get_lib().shg_shu_split_irfft2_n_f32(_ptr(y), _ptr(cw), g_arr, o_arr, s_arr, n, c, bands, int(bool(accumulate)),
                                                             size, res_arr, nl, L.stream()), 'shu_split_irfft2')
     return outs
+
+
+class _FirstOrderOnly(torch.autograd.Function):
+    """Identity on ``grad`` whose own backward raises: hung behind the gradient of a first-order operator when it is taken with
+    ``create_graph=True``, with an edge to the operator's input ``wrt`` so that a second derivative with respect to it reaches the node."""
+
+    @staticmethod
+    def forward(ctx, grad, wrt, who):
+        ctx.who = who
+        return grad.view_as(grad)
+
+    @staticmethod
+    def backward(ctx, _):
+        raise _lib.ShgError(f'{ctx.who} is first order only: a second derivative through it was requested')
+
+
+def first_order_only(grad, wrt, who):
+    """``grad`` as a first-order operator's backward returns it: unchanged unless a graph is being recorded (``create_graph=True``)."""
+    if grad is None or not torch.is_grad_enabled() or not wrt.requires_grad:
+        return grad
+    return _FirstOrderOnly.apply(grad, wrt, who)
+
+
+class _L1Mean(torch.autograd.Function):
+    """``l1_mean``: one launch each way (csrc/lpips_bwd.hip); first order only."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        launch = _Launch()     # (``launch``: see the note above plural_composite_u8)
+        ctx.save_for_backward(a, b)
+        a, b = launch.req(a.detach(), 'a'), launch.req(b.detach(), 'b')
+        B, n = a.shape[0], a[0].numel()
+        out = launch.new((B,))
+        with launch:
+            check(_lib.get_lib().shg_l1_mean_f32(_ptr(a), _ptr(b), _ptr(out), B, n, launch.stream()), 'l1_mean')
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _once(ctx, g):
+        launch = _Launch()     # (``launch``: see the note above plural_composite_u8)
+        a, b = (launch.req(t.detach(), name) for t, name in zip(ctx.saved_tensors, 'ab'))        # (a strided operand is copied, as in forward)
+        g = launch.req(g.to(torch.float32), 'g')
+        da = launch.new(tuple(a.shape))
+        with launch:
+            check(_lib.get_lib().shg_l1_mean_bwd_f32(_ptr(a), _ptr(b), _ptr(g), _ptr(da), a.shape[0], a[0].numel(), launch.stream()), 'l1_mean_bwd')
+        return (da if ctx.needs_input_grad[0] else None), (-da if ctx.needs_input_grad[1] else None)
+
+    @staticmethod
+    def backward(ctx, g):
+        da, db = _L1Mean._once(ctx, g)
+        a, b = ctx.saved_tensors
+        return first_order_only(da, a, 'l1_mean'), first_order_only(db, b, 'l1_mean')
+
+
+def l1_mean(a, b):
+    """a, b float32 [B, ...] of one shape -> float32 [B]: the mean of ``|a - b|`` over each image, accumulated in float64 in a fixed order
+    and rounded once.  Differentiable once: ``sign(a - b) g_b / n`` (0 where ``a == b``); a second derivative raises."""
+    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)) or a.ndim < 2 or tuple(a.shape) != tuple(b.shape) or a.numel() == 0:
+        raise _lib.ShgError('l1_mean: a and b must be [B, ...] tensors of one shape with at least one element per image')
+    return _L1Mean.apply(a, b)

@@ -16,6 +16,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import kernels
+from ._lib import ShgError
 from .ada import AugmentPipe
 from .model_zoo.stylegan_utils import conv2d_gradfix
 
@@ -74,6 +76,11 @@ class StyleGAN2Loss(Loss):
         ws = self._style_mix(self.G_mapping(z, c), z, c)
         return self.G_synthesis(ws), ws
 
+    def _gmain_terms(self, gen_img, real_img):
+        """Further terms of Gmain's objective, added to the mean adversarial loss before the gain and the ONE backward (None: no term,
+        no launch)."""
+        return None
+
     def _augment(self, img):
         """The critic's input through the ADA pipe (one parameter launch + one fused launch for the whole batch)."""
         if self.augment_pipe is None:
@@ -119,8 +126,12 @@ class StyleGAN2Loss(Loss):
                 gen_logits = self.run_D(gen_img, gen_c)
                 loss_Gmain = F.softplus(-gen_logits)                 # -log(sigmoid(logits))
                 self.stats.update({'Loss/scores/fake': gen_logits.detach(), 'Loss/G/loss': loss_Gmain.detach()})
+                total = loss_Gmain.mean()
+                extra = self._gmain_terms(gen_img, real_img)         # (None here; InpaintingLoss: its perceptual and L1 terms)
+                if extra is not None:
+                    total = total + extra
                 self._arm(sync and not do_Gpl)                       # (may get synced by Gpl, :56)
-                loss_Gmain.mean().mul(gain).backward()
+                total.mul(gain).backward()
 
             if do_Gpl:                                               # path-length regularisation on a shrunk batch
                 n = gen_z.shape[0] // self.pl_batch_shrink
@@ -200,15 +211,41 @@ class InpaintingLoss(StyleGAN2Loss):
         trained on pixels that are thrown away at evaluation time.  ``composite_fake=False`` is the raw-output objective; the
         full-width reference-autograd fixtures (``tests/golden/config5_step512.npz``, generated by feeding the reference's modules
         the raw output) are evaluated in that mode, the composite itself is pinned by ``tests/test_gpu_config5.py``.
-    CoModGAN's optional L1 term on the known region is not part of ``stylegan_default_loss.py`` and is not added.
+      * ``perceptual`` (an ``lpips.Lpips``, frozen, constructed by the user), ``perceptual_weight``, ``l1_weight`` (keyword-only, off by
+        default): Gmain alone minimises ``(softplus(-logits).mean() + perceptual_weight * lp.mean() + l1_weight * l1.mean()) * gain`` in
+        one backward, ``lp = perceptual.loss(img, real)`` and ``l1 = kernels.l1_mean(img, real)`` comparing ``run_G``'s image with
+        ``real_img[:, 1:4]``.  With ``composite_fake=True`` the known pixels of the two images are equal, so both terms act on the hole
+        alone; with False they act on the whole raw output.  ``Loss/G/perceptual`` and ``Loss/G/l1`` appear in ``self.stats`` only while
+        their weight is non-zero; with both weights 0 the call issues the launches it issues without the arguments.  Greg, Dmain and Dreg
+        never see the terms (first-order operators: the path-length and R1 graphs must not contain them).  The loss's ``state_dict`` does
+        not include the network.
     ``noise_mode`` is the synthesis noise ('random' in training; tests pin 'const')."""
 
-    def __init__(self, device, G, D, *, composite_fake, noise_mode='random', **kw):
+    def __init__(self, device, G, D, *, composite_fake, noise_mode='random', perceptual=None, perceptual_weight=0.0, l1_weight=0.0, **kw):
         super().__init__(device, G.mapping, None, D, **kw)
+        from .lpips import Lpips
+        if perceptual is not None and not isinstance(perceptual, Lpips):
+            raise ShgError(f'InpaintingLoss: perceptual must be an lpips.Lpips (got {type(perceptual).__name__})')
+        if perceptual_weight != 0 and perceptual is None:
+            raise ShgError('InpaintingLoss: a non-zero perceptual_weight needs perceptual=<lpips.Lpips>')
         self.G = G
         self.noise_mode = noise_mode
         self.composite_fake = composite_fake
+        self.perceptual, self.perceptual_weight, self.l1_weight = perceptual, float(perceptual_weight), float(l1_weight)
         self._m05 = self._x = None
+
+    def _gmain_terms(self, gen_img, real_img):
+        extra = None
+        real = real_img[:, 1:4].detach()
+        if self.perceptual_weight != 0:
+            lp = self.perceptual.loss(gen_img, real.contiguous())
+            self.stats['Loss/G/perceptual'] = lp.detach()
+            extra = lp.mean() * self.perceptual_weight
+        if self.l1_weight != 0:
+            l1 = kernels.l1_mean(gen_img, real)
+            self.stats['Loss/G/l1'] = l1.detach()
+            extra = l1.mean() * self.l1_weight if extra is None else extra + l1.mean() * self.l1_weight
+        return extra
 
     def accumulate_gradients(self, phase, real_img, real_c, gen_z, gen_c, sync=True, gain=1):
         if real_img.ndim != 4 or real_img.shape[1] != 4:

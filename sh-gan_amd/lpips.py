@@ -355,6 +355,173 @@ def head_pairs(f, ia, ib, w, out, err=None):
     return out
 
 
+# ---- the training loss: operands in [-1, 1] straight into the scaling layer, and the backward pass with respect to the pred image
+# (csrc/lpips_bwd.hip).  ONE masking rule: whoever writes a gradient into the buffer of a post-ReLU activation y selects it by y > 0.
+# (``launch``, not ``L``, in these functions: see the note above kernels.plural_composite_u8 -- the allocation tables of
+# tests/test_gpu_alloc_fill.py and tests/test_gpu_alloc_guard.py are older than they are.)
+
+def _pm1(launch, x, name='x'):
+    x = launch.req(x, name)
+    if x.ndim != 4 or x.shape[1] != 3:
+        raise ShgError(f'lpips: {name} must be a float32 [B,3,H,W] tensor (got {tuple(x.shape)})')
+    return x
+
+
+def scale_pm1(x, shift=SHIFT, scale=SCALE):
+    """x [B,3,H,W] float32 in [-1, 1] -> scaling_layer(x) = (x - shift_c) * float32(1 / scale_c) (one launch)."""
+    launch = kernels._Launch()
+    x = _pm1(launch, x)
+    B, _, H, W = x.shape
+    y = launch.new(tuple(x.shape))
+    with launch:
+        check(_lib.get_lib().shg_lpips_scale_pm1_f32(kernels._ptr(x), kernels._c3(shift), kernels._c3(scale), kernels._ptr(y), B, H, W, launch.stream()),
+              'lpips_scale_pm1')
+    return y
+
+
+def conv1_pm1(x, wp, bp, shift=SHIFT, scale=SCALE):
+    """x [B,3,H,W] float32 in [-1, 1] -> relu(conv1(scaling_layer(x))) [B,64,OH,OW] (one launch): ``conv1`` with the plain operand."""
+    launch = kernels._Launch()
+    x, wp, bp = _pm1(launch, x), launch.req(wp, 'wp'), launch.req(bp, 'bp')
+    B, _, H, W = x.shape
+    if H < 7 or W < 7:
+        raise ShgError(f'lpips: conv1 needs H, W >= 7 (got {H} x {W})')
+    y = launch.new((B, 64, inception.out_size(H, 11, 4, 2), inception.out_size(W, 11, 4, 2)))
+    with launch:
+        check(_lib.get_lib().shg_lpips_conv1_pm1_f32(kernels._ptr(x), kernels._c3(shift), kernels._c3(scale), kernels._ptr(wp), kernels._ptr(bp),
+                                                     kernels._ptr(y), B, H, W, launch.stream()), 'lpips_conv1_pm1')
+    return y
+
+
+def unpack_weight(wp, O, I, kh, kw):
+    """The inverse of ``inception.pack_weight``: wp [Kp*Np] -> w [O,I,kh,kw] (a torch view + copy; once per network)."""
+    Np = (O + 63) // 64 * 64
+    return wp.reshape(-1, Np)[:I * kh * kw, :O].reshape(kh, kw, I, O).permute(3, 2, 0, 1).contiguous()
+
+
+def pack_dgrad_weight(w, fold=None):
+    """Forward weight w [O,I,k,k] on the device -> the packed operand of ``dgrad``: ``w.transpose(0,1).flip(2,3)`` [I,O,k,k] through
+    ``inception.pack_weight``.  ``fold`` [I]: a factor per INPUT channel of the forward convolution (the scaling layer's 1 / scale_c)."""
+    wt = w.transpose(0, 1).flip(2, 3)
+    if fold is not None:
+        wt = wt * fold.to(wt).reshape(-1, 1, 1, 1)
+    wt = wt.contiguous()
+    return inception.pack_weight(wt, wt[:, 0, 0, 0].contiguous())[0]      # (the packing wants a bias [O]; dgrad has none and drops it)
+
+
+def dgrad(g, wp, O, k, ymask=None):
+    """Input gradient of a stride-1 k x k convolution at pad k // 2: g [B,I,H,W], wp = ``pack_dgrad_weight(w)`` -> dx [B,O,H,W], selected
+    by ``ymask > 0`` (a [B,O,H,W] post-ReLU activation) when given (one launch on the detector's tile, K never split)."""
+    launch = kernels._Launch()
+    g, wp, ymask = launch.req(g, 'g'), launch.req(wp, 'wp'), launch.req(ymask, 'ymask')
+    if g.ndim != 4:
+        raise ShgError(f'lpips: dgrad takes g [B,I,H,W] (got {tuple(g.shape)})')
+    B, I, H, W = g.shape
+    n = int(_lib.get_lib().shg_inception_packed_weight_elems(O, I, k, k))
+    if n <= 0 or wp.numel() != n:
+        raise ShgError(f'lpips: dgrad weight of {wp.numel()} elements does not fit O {O} I {I} {k}x{k}')
+    if ymask is not None and tuple(ymask.shape) != (B, O, H, W):
+        raise ShgError(f'lpips: dgrad ymask {tuple(ymask.shape)} does not fit the output {(B, O, H, W)}')
+    dx = launch.new((B, O, H, W))
+    with launch:
+        check(_lib.get_lib().shg_lpips_dgrad_f32(kernels._ptr(g), kernels._ptr(wp), kernels._ptr(ymask), kernels._ptr(dx), B, I, O, H, W, k, k // 2,
+                                                 launch.stream()), 'lpips_dgrad')
+    return dx
+
+
+def maxpool_bwd(x, gy, k):
+    """Backward of the k x k / stride 2 / floor max pool (k = 2 or 3) of the post-ReLU activation x [B,C,H,W], gather form: gy [B,C,OH,OW]
+    -> dx [B,C,H,W] = x > 0 ? the gradients of the windows whose first maximum (row-major) the element is : 0 (one launch)."""
+    launch = kernels._Launch()
+    x, gy = launch.req(x, 'x'), launch.req(gy, 'gy')
+    if x.ndim != 4 or k not in (2, 3) or min(x.shape[2:]) < k or tuple(gy.shape) != tuple(x.shape[:2]) + ((x.shape[2] - k) // 2 + 1, (x.shape[3] - k) // 2 + 1):
+        raise ShgError(f'lpips: maxpool_bwd operands x {tuple(x.shape)}, gy {tuple(gy.shape)}, window {k} do not fit')
+    B, C, H, W = x.shape
+    dx = launch.new(tuple(x.shape))
+    with launch:
+        check(_lib.get_lib().shg_lpips_maxpool_bwd_f32(kernels._ptr(x), kernels._ptr(gy), kernels._ptr(dx), B, C, H, W, k, launch.stream()), 'lpips_maxpool_bwd')
+    return dx
+
+
+def head_bwd(f, fr, w, g, df=None):
+    """One tap's head backward: f, fr [B,C,h,w] (pred / real tap), w [C], g [B] float32 -> df [B,C,h,w], selected by f > 0.  ``df`` given:
+    accumulated into it (a tap whose buffer its downstream consumer has written); else a new tensor (one launch)."""
+    launch = kernels._Launch()
+    f, fr, w, g = launch.req(f, 'f'), launch.req(fr, 'fr'), launch.req(w, 'w'), launch.req(g, 'g')
+    if f.ndim != 4 or tuple(f.shape) != tuple(fr.shape) or w.numel() != f.shape[1] or g.numel() != f.shape[0]:
+        raise ShgError(f'lpips: head_bwd operands {tuple(f.shape)}, {tuple(fr.shape)}, w {tuple(w.shape)}, g {tuple(g.shape)} do not fit')
+    acc = df is not None
+    if acc:
+        launch.req(df, 'df')
+        if tuple(df.shape) != tuple(f.shape) or not df.is_contiguous():
+            raise ShgError(f'lpips: head_bwd df {tuple(df.shape)} must be a contiguous tensor of the shape of f {tuple(f.shape)}')
+    else:
+        df = launch.new(tuple(f.shape))
+    B, C, h, wd = f.shape
+    with launch:
+        check(_lib.get_lib().shg_lpips_head_bwd_f32(kernels._ptr(f), kernels._ptr(fr), kernels._ptr(w), kernels._ptr(g), kernels._ptr(df), B, C, h, wd,
+                                                    int(acc), launch.stream()), 'lpips_head_bwd')
+    return df
+
+
+def conv1_dgrad(g, w, H, W):
+    """AlexNet conv1's input gradient: g [B,64,OH,OW], w [64,3,11,11] (1 / scale_c folded in) -> dx [B,3,H,W]; the transposed 11 x 11
+    stride 4 pad 2 convolution, 0 at the pixels no window reaches (one launch)."""
+    launch = kernels._Launch()
+    g, w = launch.req(g, 'g'), launch.req(w, 'w')
+    if g.ndim != 4 or tuple(g.shape[1:]) != (64, inception.out_size(H, 11, 4, 2), inception.out_size(W, 11, 4, 2)) or tuple(w.shape) != (64, 3, 11, 11):
+        raise ShgError(f'lpips: conv1_dgrad operands g {tuple(g.shape)}, w {tuple(w.shape)} do not fit an image of {H} x {W}')
+    dx = launch.new((g.shape[0], 3, H, W))
+    with launch:
+        check(_lib.get_lib().shg_lpips_conv1_dgrad_f32(kernels._ptr(g), kernels._ptr(w), kernels._ptr(dx), g.shape[0], H, W, launch.stream()), 'lpips_conv1_dgrad')
+    return dx
+
+
+def _conv_relu(op, x):
+    """One stride-1 'same' convolution + ReLU of the backbone into a new tensor (``split_k`` off: no launch plan depends on the batch)."""
+    launch = kernels._Launch()
+    launch.view(x, 'x')
+    y = launch.new((x.shape[0], op.O) + tuple(x.shape[2:]))
+    inception.conv_group([(op, x, 0, y, 0)], split_k=False)
+    return y
+
+
+class _LpipsLoss(torch.autograd.Function):
+    """``Lpips.loss``: the value from the forward heads (float64, rounded once), the gradient with respect to ``fake`` from
+    csrc/lpips_bwd.hip.  First order only."""
+
+    @staticmethod
+    def forward(ctx, fake, real, net):
+        B = fake.shape[0]
+        ctx.save_for_backward(fake)
+        fake, real = fake.detach(), real.detach()
+        real_taps = net._taps_pm1(real)
+        acts = net._acts_pm1(fake, keep=ctx.needs_input_grad[0])     # every post-ReLU activation of the pred half, in network order
+        launch = kernels._Launch()
+        launch.view(fake, 'fake')
+        out = launch.new((B,), torch.float64).zero_()
+        for k, tr, w in zip(net.tap_ids, real_taps, net.lins):
+            head(acts[k], tr, w, out)
+        ctx.net, ctx.acts, ctx.real_taps, ctx.size = net, acts, real_taps, tuple(fake.shape[2:])
+        return out.to(torch.float32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _once(ctx, g):
+        net, acts, real_taps = ctx.net, ctx.acts, ctx.real_taps
+        if acts is None:
+            raise ShgError('lpips: the activations Lpips.loss saved were freed by its first backward pass: it cannot run backward a second '
+                           'time (retain_graph=True does not keep them)')
+        ctx.acts = ctx.real_taps = None
+        return net._backward(acts, real_taps, g.to(torch.float32).contiguous(), ctx.size)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        return kernels.first_order_only(_LpipsLoss._once(ctx, g), ctx.saved_tensors[0], 'Lpips.loss'), None, None
+
+
 class Lpips:
     """``net(pred, gt, gt_range='pm1', out=None) -> float64 [B]``.  pred: uint8 composite or float32 in [0, 1]; gt: float32 in [-1, 1] or
     decoded uint8 pixels ('pm1'), or float32 in [0, 1] / uint8 with ``gt_range='unit'`` -- the operand forms of
@@ -372,6 +539,7 @@ class Lpips:
         # net='vgg' only: the normalisation of a 0..255 image for ``trunk``'s other caller (ppl.py), in the order the image is read (RGB)
         self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
         self.widths = tuple(op.O for op in ops) if net == 'vgg' else None
+        self._dgrad, self.loss_calls = None, 0      # the transposed weights (packed at the first ``loss``); how often ``loss`` ran
 
     @classmethod
     def _from_canonical(cls, cw, device, split_k):
@@ -450,6 +618,104 @@ class Lpips:
         """images [B,3,H,W] in the 'pred' operand form (uint8 composite or float32 in [0, 1]) -> the five taps [B,C,h,w]: ONE pass of the
         backbone over the batch, the launches ``features`` issues for its pred half (no launch plan depends on the batch size)."""
         return self.features(images, None)
+
+    # -- the training loss (first order; csrc/lpips_bwd.hip) ------------------------------------------------------------------------------
+    @property
+    def tap_ids(self):
+        """Index of each tap in the list of post-ReLU activations ``_acts_pm1`` returns."""
+        return VGG_TAPS if self.net == 'vgg' else (0, 1, 2, 3, 4)
+
+    def _acts_pm1(self, x, keep=True):
+        """x [B,3,H,W] float32 in [-1, 1], straight into the scaling layer -> every post-ReLU activation in network order (vgg: 13, alex:
+        5), the saving variant of ``features`` / ``vgg16.conv_trunk``: the same launches, pooled tensors dropped.  ``keep=False``: a
+        non-tap activation is dropped as soon as its consumer has read it (None in the list)."""
+        acts = []
+        if self.net == 'vgg':
+            x = scale_pm1(x, self.shift, self.scale)
+            for k, op in enumerate(self.ops):
+                y = _conv_relu(op, x)
+                acts.append(y if keep or k in VGG_TAPS else None)
+                x = vgg16.maxpool2(y) if k in vgg16.POOL_AFTER and k + 1 < len(self.ops) else y
+            return acts
+        y = conv1_pm1(x, *self.conv1_wb, self.shift, self.scale)
+        acts.append(y)
+        x = inception.pool(y, 'max', 2, 0)
+        for k, op in enumerate(self.ops, start=1):
+            y = _conv_relu(op, x)
+            acts.append(y)
+            x = inception.pool(y, 'max', 2, 0) if k == 1 else y
+        return acts
+
+    def _taps_pm1(self, x):
+        """The real half: the five taps only."""
+        acts = self._acts_pm1(x, keep=False)
+        return [acts[k] for k in self.tap_ids]
+
+    def _dgrad_weights(self):
+        """The transposed weights, packed once per network (from the packed forward operands): [(wp, O, k)] per convolution whose dgrad
+        runs on the tile; 1 / scale_c folded into the first (vgg) or into conv1's plain weight (alex: ``_conv1_wt``)."""
+        if self._dgrad is None:
+            inv = torch.tensor([float(np.float32(1.0 / float(np.float32(s)))) for s in self.scale], dtype=torch.float32, device=self.device)
+            packs = []
+            for n, op in enumerate(self.ops):
+                w = unpack_weight(op.wp, op.O, op.I, op.k[0], op.k[1])
+                packs.append((pack_dgrad_weight(w, inv if (self.net == 'vgg' and n == 0) else None), op.I, op.k[0]))
+            if self.net == 'alex':
+                self._conv1_wt = (unpack_weight(self.conv1_wb[0], 64, 3, 11, 11) * inv.reshape(1, 3, 1, 1)).contiguous()
+            self._dgrad = packs
+        return self._dgrad
+
+    def _backward(self, acts, real_taps, g, size):
+        """g [B] float32 -> d(sum_b g_b loss_b) / d fake [B,3,H,W].  Every activation gradient is written once -- by the dgrad or the pool
+        backward downstream of it, which selects by y > 0 -- accumulated into once by the head where it is a tap, and read once."""
+        packs = self._dgrad_weights()
+        taps = {k: n for n, k in enumerate(self.tap_ids)}
+        last = len(acts) - 1
+        gy = head_bwd(acts[last], real_taps[4], self.lins[4], g)
+        if self.net == 'vgg':
+            for k in range(last, 0, -1):
+                wp, O, ks = packs[k]
+                pooled = (k - 1) in vgg16.POOL_AFTER
+                gy = dgrad(gy, wp, O, ks, None if pooled else acts[k - 1])
+                if pooled:
+                    gy = maxpool_bwd(acts[k - 1], gy, 2)
+                if (k - 1) in taps:
+                    head_bwd(acts[k - 1], real_taps[taps[k - 1]], self.lins[taps[k - 1]], g, df=gy)
+                acts[k] = None
+            wp, O, ks = packs[0]
+            return dgrad(gy, wp, O, ks, None)
+        for k in range(4, 0, -1):                                    # acts[k] is the output of self.ops[k - 1]
+            wp, O, ks = packs[k - 1]
+            pooled = k <= 2
+            gy = dgrad(gy, wp, O, ks, None if pooled else acts[k - 1])
+            if pooled:
+                gy = maxpool_bwd(acts[k - 1], gy, 3)
+            head_bwd(acts[k - 1], real_taps[k - 1], self.lins[k - 1], g, df=gy)
+            acts[k] = None
+        return conv1_dgrad(gy, self._conv1_wt, size[0], size[1])
+
+    def _check_pair(self, a, b, names):
+        if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)) or a.ndim != 4 or tuple(a.shape) != tuple(b.shape) or a.shape[1] != 3:
+            raise ShgError(f'lpips: {names[0]} and {names[1]} must be [B,3,H,W] tensors of one shape')
+        if not (a.is_cuda and b.is_cuda):
+            raise ShgError(f'lpips: {names[0]} and {names[1]} must reside on a HIP (cuda) device: there is no CPU path')
+        H, W = a.shape[2:]
+        if H < self.min_size or W < self.min_size:
+            why = 'the AlexNet taps need H, W >= 31 (the second max pool must see 3 x 3)' if self.net == 'alex' else \
+                'the VGG16 taps need H, W >= 16 (four 2 x 2 pools before the last one)'
+            raise ShgError(f'lpips: images of {H} x {W} are too small: {why}')
+
+    def loss(self, fake, real):
+        """The distance as a training loss: ``fake``, ``real`` float32 [B,3,H,W] in [-1, 1] on the device -> float32 [B], the distance
+        ``__call__`` computes (accumulated in float64, rounded once) except that both operands enter the scaling layer ``(v - shift) /
+        scale`` as they are.  ``fake`` may require grad; ``real`` never gets a gradient.  First order only: a second derivative raises.
+        The pred half keeps every post-ReLU activation until backward, the real half only its taps.  ``split_k`` is off on this route."""
+        self._check_pair(fake, real, ('fake', 'real'))
+        if fake.dtype != torch.float32 or real.dtype != torch.float32:
+            raise ShgError(f'lpips: loss takes float32 images in [-1, 1] (got {fake.dtype}, {real.dtype})')
+        self.loss_calls += 1
+        self._dgrad_weights()
+        return _LpipsLoss.apply(fake, real, self)
 
     def __call__(self, pred, gt, gt_range='pm1', out=None):
         if gt_range not in ('pm1', 'unit'):
